@@ -5,9 +5,16 @@ observations, batch 256 per GPU (BASELINE.json metric; configs[1] = config/gripp
 
 One step = draw a minibatch from the HBM-resident replay (device Philox) + normalise + 3 CNN forwards + heads +
 losses + backward through both trainable CNNs + 3 Adam applies + Polyak update, replayed as one hipGraph
-(DESIGN.md section 4).  Inputs are resident in HBM before the timed region.  A timed block is exactly --steps updates
-per call between barrier + synchronize, the call repeated back to back until the block holds >= 50 ms of work
-(`repeats.calls_per_block`); --repeats blocks, `value` is the MEDIAN block.  The timed call shape is warmed untimed.
+(DESIGN.md section 4).  Inputs are resident in HBM before the timed region.  The timed region is exactly --steps updates,
+one call between barrier + synchronize, after --warmup untimed updates and an untimed call that instantiates the graphs
+of the timed call shape; `value` = updates / s of that region, `ms_per_step` = its milliseconds per update.  All inputs
+are seeded: the same arguments give the same inputs in every run, and `--dump-outputs DIR` writes what the timed path
+computed in its last step (parameters, metrics, ...) as DIR/<name>.npy for output-for-output comparisons of two builds.
+
+A plain run does nothing else.  `--full` adds, after the headline: --repeats further blocks of --steps-update calls back
+to back (each >= 50 ms of work, `repeats`), the `roofline` (an eager profile pass), the CPU-oracle `cpu_baseline`, and per
+workload the learn loop and success rate (sac_depth), the encoder latency (sac_rgbd), device identities and the configs[4]
+pass (N > 1); --no-profile, --no-cpu-baseline, --no-learn-loop, --no-success and --no-configs4 leave parts of it out.
 
 N > 1: one process per GPU, data parallel, gradients all-reduced over RCCL per update.  Default per-GPU batch 256
 (weak scaling, `value` = N x global steps/s); `--global-batch G` fixes the GLOBAL batch (G/N per GPU, strong
@@ -22,7 +29,7 @@ Other workloads (`--workload`), each with its own roofline and CPU-oracle baseli
   bdq_per     configs[2]: BDQ 5 branches x 33 bins on 101-d observations, batch 64, prioritised replay over 1 M
   ae_train    auto-encoder training step, batch 128 (config/encoder.yaml)
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -120,11 +127,83 @@ def fill_replay_on_device(eng, n, seed, device, kind="depth", act_dim=5):
     return st
 
 
+WARM_MAX = 4096
+
+
+def warm_shape(steps):
+    """Length of the untimed call that runs the GPU up to speed and instantiates every hipGraph a call of `steps` updates
+    replays: `steps` itself up to WARM_MAX, else the longest n' <= WARM_MAX with n' = steps (mod 64).  A call of n updates
+    with the device RNG replays one graph per n when n <= 32, else a first and a last graph around groups of up to 64
+    updates per graph (power-of-two groups, csrc/engine.hip run_repeated / run_ride; the auto-encoder goes in calls of
+    at most 8): calls of n and n' updates replay the same graphs when n' = n (mod 64) and both are at least 66."""
+    return steps if steps <= WARM_MAX else steps - 64 * -(-(steps - WARM_MAX) // 64)
+
+
+def timed_steps(run, barrier, steps, warmup, world, device):
+    """The headline measurement: exactly `steps` updates, ONE call `run(steps)` between barrier + synchronize, MAX over
+    ranks.  Untimed before it: `run(warmup)` and a call that instantiates the graphs of the timed call shape
+    (warm_shape).  Returns the seconds of the `steps` updates."""
+    import torch
+    import torch.distributed as dist
+    if warmup > 0:
+        run(warmup)
+    run(warm_shape(steps))
+    barrier()
+    t0 = time.perf_counter()
+    run(steps)
+    barrier()
+    dt = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([dt], dtype=torch.float64, device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    return dt
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> array) as `path/<name>.npy`, float64 for float64 and integer arrays, float32
+    otherwise.  At most DUMP_LIMIT_BYTES in all: past that, every array of more than 4096 elements is replaced by a fixed
+    sample of its flattened elements (seeded, sorted indices: the same sample in every run).  Returns the file names."""
+    import re
+    import numpy as np
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 or np.issubdtype(a.dtype, np.integer) else np.float32)
+        conv[re.sub(r"[^A-Za-z0-9_.-]+", "_", name).strip("_")] = a
+    if len(conv) != len(arrays):
+        raise ValueError("output names collide after sanitising: %s" % sorted(arrays))
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        large = sum(a.nbytes for a in conv.values() if a.size > 4096)
+        keep = (DUMP_LIMIT_BYTES - (total - large)) / large
+        for name, a in conv.items():
+            if a.size > 4096:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * keep), replace=False))
+                conv[name] = a.reshape(-1)[idx]
+    os.makedirs(path, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(n + ".npy" for n in conv)
+
+
+def engine_outputs(eng, extra=None):
+    """What a caller of the timed path receives after its last step: every parameter (`get_parameters`), the step's
+    metrics (`metrics`), and `extra` (name -> array) where the path hands out more."""
+    out = {"param/" + k: v for k, v in eng.get_parameters().items()}
+    out.update({"metric/" + k: float(v) for k, v in eng.metrics().items()})
+    out.update(extra or {})
+    return out
+
+
 MIN_BLOCK_S = 0.050         # a timed block holds at least this much work (the driver's --steps 20 is 3.6 ms of updates)
 
 
 def timed_blocks(run, barrier, steps, warmup, repeats, world, device):
-    """`repeats` timed blocks (barrier + synchronize on both sides, MAX over ranks).  A block is `calls` back-to-back
+    """--full: `repeats` timed blocks (barrier + synchronize on both sides, MAX over ranks).  A block is `calls` back-to-back
     `run(steps)` calls -- each exactly `steps` updates, the call shape the command line names -- with `calls` chosen so that
     a block holds >= MIN_BLOCK_S of work (1 when `steps` is large enough on its own).  Returns (seconds per `steps` updates
     of every block, calls).  Untimed before the first block: `run(warmup)` AND the exact timed shape, `run(steps)`, twice --
@@ -163,6 +242,16 @@ def block_note(calls, steps):
     return {"calls_per_block": calls, "updates_per_block": calls * steps,
             "block_ms_is": "milliseconds per %d updates: a block is %d back-to-back call(s) of exactly %d updates between barrier + "
                            "synchronize, its time divided by the calls; the timed call shape was warmed untimed" % (steps, calls, steps)}
+
+
+def repeats_note(times, calls, steps, per=1):
+    """--full: the repeated blocks beside the headline; `median_value` = the rate of the median block, counted as `value` is
+    (`per` = the number of GPUs under weak scaling, else 1)."""
+    import numpy as np
+    return {"n": len(times), "block_ms": [round(1e3 * t, 3) for t in times],
+            "median_value": round(per * steps / float(np.median(times)), 2),
+            "value_is": "the headline: one call of exactly --steps updates, timed after the untimed warm-up; these blocks follow it",
+            **block_note(calls, steps)}
 
 
 def profile_pass(eng, go, n):
@@ -603,7 +692,8 @@ def run_sac(args, wl_name, world, rank, device):
     eng = build_sac_engine(wl, replay, rank, device)
     dp, dp_kind, dp_chosen, devices = None, "dp%d" % world, None, None
     if world > 1:
-        devices = device_identities(world, rank, device, args.same_device)
+        if args.full:
+            devices = device_identities(world, rank, device, args.same_device)
         dp, dp_kind, dp_chosen = make_data_parallel(eng, args.dp, world, rank, device, init_parameters(eng.table, seed=0),
                                                     inject_ipc_failure=args.inject_ipc_failure)
 
@@ -619,9 +709,10 @@ def run_sac(args, wl_name, world, rank, device):
         if world > 1:
             dist.barrier()
 
-    times, calls = timed_blocks(run, barrier, args.steps, args.warmup, args.repeats, world, device)
-    dt = float(np.median(times))
+    dt = timed_steps(run, barrier, args.steps, args.warmup, world, device)
     metrics = eng.metrics()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engine_outputs(eng))
     out = {"metric": wl["metric"] if not strong else "SAC grad-steps/sec (64x64 depth, global batch %d)" % args.global_batch,
            "value": None, "unit": "grad-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True,
@@ -634,16 +725,21 @@ def run_sac(args, wl_name, world, rank, device):
                                                                         % (args.global_batch, world) if strong else ""),
                      "global_batch": wl["batch"] * world, "parallelism": dp_kind,
                      "global_steps_per_s": round(args.steps / dt, 2)}
-    out["repeats"] = {"n": args.repeats, "block_ms": [round(1e3 * t, 3) for t in times], "value_is": "median block", **block_note(calls, args.steps)}
     if args.same_device and world > 1:
         out["config"]["validation_only"] = "all %d ranks share cuda:0 (--same-device): not a scaling measurement" % world
     out["losses"] = {k: round(float(v), 6) for k, v in metrics.items()}
+    out["roofline"] = out["cpu_baseline"] = None
+    if not args.full:
+        if dp is not None and hasattr(dp, "close"):
+            dp.close(disconnect=True)
+        eng.close()
+        return out
+    times, calls = timed_blocks(run, barrier, args.steps, args.warmup, args.repeats, world, device)
+    out["repeats"] = repeats_note(times, calls, args.steps, world if not strong else 1)
     if rank == 0 and not args.no_profile:
         n = min(args.steps, 50)
         prof = profile_pass(eng, eng.train_device, n)
         out["roofline"] = roofline_of(prof, n, dt / args.steps, wl_name if not strong else wl_name + "_gb%d" % args.global_batch)
-    else:
-        out["roofline"] = None
     if wl_name == "sac_rgbd" and rank == 0 and world == 1:
         # "+ pretrained autoencoder features" (configs[3]): latency of the encoder forward the env side calls per step
         from grasp_rl.autoencoder import glorot_uniform_params
@@ -655,10 +751,8 @@ def run_sac(args, wl_name, world, rank, device):
         for _ in range(200):
             eng.encode(frames)
         out["ae_encode_us_per_call_16_frames"] = round(1e6 * (time.perf_counter() - t0) / 200, 1)
-    cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline_sac(wl)
-    out["cpu_baseline"] = cpu
+        out["cpu_baseline"] = cpu_baseline_sac(wl)
     if devices is not None:
         out["config"]["devices"] = devices
         out["config"]["exchange"] = dp_chosen
@@ -767,8 +861,13 @@ def run_bdq(args, device, prioritized=True):
     def barrier():
         eng.synchronize()
         torch.cuda.synchronize(device)
-    times, calls = timed_blocks(go, barrier, args.steps, args.warmup, args.repeats, 1, device)
-    dt = float(np.median(times))
+    dt = timed_steps(go, barrier, args.steps, args.warmup, 1, device)
+    if args.dump_outputs:
+        extra = {}
+        if prioritized:         # what PrioritizedReplayBuffer.sample / update_priorities hand out for the last minibatch
+            extra = {"sampled_indices": eng.sampled_indices(), "importance_weights": eng.importance_weights(),
+                     "priorities": eng.priorities()}
+        dump_outputs(args.dump_outputs, engine_outputs(eng, extra))
     out = {"metric": "BDQ grad-steps/sec (101-d observations, 5 x 33 bins, batch 64, %s replay)" % ("prioritised" if prioritized else "uniform"),
            "value": round(args.steps / dt, 2), "unit": "grad-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -777,13 +876,16 @@ def run_bdq(args, device, prioritized=True):
                                   "64, lr 1e-4, %s) on 101-d auto-encoder observations, %d-transition ring%s in HBM, device RNG"
                                   % ("prioritized_replay: True" if prioritized else "prioritized_replay: False as gripper_grasp.yaml:106 ships it", replay,
                                      " + priorities" if prioritized else "")},
-           "repeats": {"n": args.repeats, "block_ms": [round(1e3 * t, 3) for t in times], "value_is": "median block", **block_note(calls, args.steps)},
-           "losses": {k: round(float(v), 6) for k, v in eng.metrics().items()}}
-    if not args.no_profile:
-        prof = profile_pass(eng, go, 50)
-        out["roofline"] = roofline_of(prof, 50, dt / args.steps, "bdq_per" if prioritized else "bdq_uniform")
-        out["roofline"]["note"] = "every launch of this update is latency-bound (0.01 GFLOP, < 5 MB): fractions are informational"
-    out["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline_bdq()
+           "losses": {k: round(float(v), 6) for k, v in eng.metrics().items()}, "roofline": None, "cpu_baseline": None}
+    if args.full:
+        times, calls = timed_blocks(go, barrier, args.steps, args.warmup, args.repeats, 1, device)
+        out["repeats"] = repeats_note(times, calls, args.steps)
+        if not args.no_profile:
+            prof = profile_pass(eng, go, 50)
+            out["roofline"] = roofline_of(prof, 50, dt / args.steps, "bdq_per" if prioritized else "bdq_uniform")
+            out["roofline"]["note"] = "every launch of this update is latency-bound (0.01 GFLOP, < 5 MB): fractions are informational"
+        if not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline_bdq()
     eng.close()
     return out
 
@@ -809,20 +911,24 @@ def run_ae(args, device):
         eng.synchronize()
         torch.cuda.synchronize(device)
     eng.be.stream.wait_stream(torch.cuda.current_stream(device))
-    times, calls = timed_blocks(go, barrier, args.steps, args.warmup, args.repeats, 1, device)
-    dt = float(np.median(times))
+    dt = timed_steps(go, barrier, args.steps, args.warmup, 1, device)
+    if args.dump_outputs:       # (+ the decoder output of the last minibatch)
+        dump_outputs(args.dump_outputs, engine_outputs(eng, {"reconstruction": eng.reconstruction()}))
     out = {"metric": "auto-encoder train-steps/sec (64x64x1 depth, batch 128)", "value": round(args.steps / dt, 2),
            "unit": "train-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
            "dtype": "f32", "data": "synthetic",
            "config": {"workload": "SURVEY 8f-3: SimpleAutoEncoder fit step (encoders.py:40-50,70-136; config/encoder.yaml: batch 128, "
                                   "lr 2e-4): encoder + decoder forward, MSE, backward, Keras-Adam; minibatches resident in HBM"},
-           "repeats": {"n": args.repeats, "block_ms": [round(1e3 * t, 3) for t in times], "value_is": "median block", **block_note(calls, args.steps)},
-           "losses": {"reconstruction_mse": round(float(eng.metrics()["policy_loss"]), 6)}}
-    if not args.no_profile:
-        prof = profile_pass(eng, go, 16)
-        out["roofline"] = roofline_of(prof, 16, dt / args.steps, "ae_train")
-    out["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline_ae()
+           "losses": {"reconstruction_mse": round(float(eng.metrics()["policy_loss"]), 6)}, "roofline": None, "cpu_baseline": None}
+    if args.full:
+        times, calls = timed_blocks(go, barrier, args.steps, args.warmup, args.repeats, 1, device)
+        out["repeats"] = repeats_note(times, calls, args.steps)
+        if not args.no_profile:
+            prof = profile_pass(eng, go, 16)
+            out["roofline"] = roofline_of(prof, 16, dt / args.steps, "ae_train")
+        if not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline_ae()
     eng.close()
     return out
 
@@ -832,7 +938,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps updates; value = median block")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: repeated timed blocks, roofline (eager profile "
+                         "pass), CPU-oracle baseline, learn loop and success rate (sac_depth), encoder latency (sac_rgbd), "
+                         "device identities and the configs[4] pass (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (parameters, metrics, "
+                         "...) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=5, help="--full: timed blocks of --steps updates after the headline")
     ap.add_argument("--workload", default="sac_depth", choices=["sac_depth", "sac_rgbd", "sac_depth_128", "sac_nature", "sac_mlp", "bdq_per", "bdq_uniform", "ae_train"])
     ap.add_argument("--global-batch", type=int, default=None, help="fix the GLOBAL batch (strong scaling); per-GPU batch = G / N")
     ap.add_argument("--replay", type=int, default=None)

@@ -23,7 +23,7 @@ if [ "$1" = build ]; then
   exit
 fi
 shift
-q() { python $R/bench.py --no-learn-loop --no-success --no-cpu-baseline --repeats 3 "$@" 2>/dev/null | tail -1 | python -c "
+q() { python $R/bench.py --full --no-learn-loop --no-success --no-cpu-baseline --repeats 3 "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['roofline']['step_kernel_ms']
 print('%9.1f | ' % d['value'] + ' '.join('%s %.1f' % (n.replace('_fwd','F').replace('_bwd','B'), 1e3*v) for n, v in sorted(k.items(), key=lambda kv: -kv[1])))"; }
 cp $LIB $R/build/libgrl_this.so

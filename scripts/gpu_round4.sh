@@ -17,7 +17,7 @@ for st in $STAGES; do
     bench)
       for W in ${WORKLOADS-sac_depth}; do
         echo "== bench $W" >> $LOG
-        timeout 900 python bench.py --workload $W --steps ${BENCH_STEPS:-200} --warmup 20 ${BENCH_ARGS-} > $R/gpurun_out/bench_$W.json 2> $R/gpurun_out/bench_$W.err
+        timeout 900 python bench.py --workload $W --steps ${BENCH_STEPS:-200} --warmup 20 --full ${BENCH_ARGS-} > $(dirname $LOG)/bench_$W.json 2> $(dirname $LOG)/bench_$W.err
         echo "rc=$?" >> $LOG; tail -3 $R/gpurun_out/bench_$W.err >> $LOG; cut -c1-3500 $R/gpurun_out/bench_$W.json >> $LOG
       done
       ;;
@@ -29,7 +29,7 @@ for st in $STAGES; do
       for N in ${REHEARSAL_N-2 4 8}; do
         echo "== bench.py --gpus $N --dist-backend gloo --same-device (dress rehearsal of the driver's SCALE run)" >> $LOG
         timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py \
-          --gpus $N --steps 64 --warmup 16 --repeats 3 --dist-backend gloo --same-device --no-profile ${REHEARSAL_ARGS-} > $R/gpurun_out/rehearsal_$N.json 2> $R/gpurun_out/rehearsal_$N.err
+          --gpus $N --steps 64 --warmup 16 --full --repeats 3 --dist-backend gloo --same-device --no-profile ${REHEARSAL_ARGS-} > $(dirname $LOG)/rehearsal_$N.json 2> $(dirname $LOG)/rehearsal_$N.err
         echo "rc=$?" >> $LOG; grep -v "^W0\|^\[Gloo\]\|^$" $R/gpurun_out/rehearsal_$N.err | tail -8 >> $LOG; cut -c1-1500 $R/gpurun_out/rehearsal_$N.json >> $LOG
       done
       ;;

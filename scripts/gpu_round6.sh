@@ -12,7 +12,7 @@ for st in ${STAGES-tests bench}; do
       local name=$1 N=$2; shift 2
       echo "== python -m torch.distributed.run --nproc-per-node $N bench.py --gpus $N --steps 20 --warmup 5 --dist-backend gloo --same-device $*" >> $LOG
       timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29700 + N + RANDOM % 50)) bench.py \
-        --gpus $N --steps 20 --warmup 5 --dist-backend gloo --same-device --no-profile "$@" > $R/gpurun_out/r06_dp_rehearsal_$name.json 2> $R/gpurun_out/r06_dp_rehearsal_$name.err
+        --gpus $N --steps 20 --warmup 5 --full --dist-backend gloo --same-device --no-profile "$@" > $(dirname $LOG)/r06_dp_rehearsal_$name.json 2> $(dirname $LOG)/r06_dp_rehearsal_$name.err
       echo "rc=$?" >> $LOG; grep -v "^W0\|^\[Gloo\]\|^$\|amdgpu.ids" $R/gpurun_out/r06_dp_rehearsal_$name.err | tail -12 >> $LOG
       python3 -c "
 import json,sys

@@ -5,7 +5,7 @@ cd $R
 for W in ${WORKLOADS:-sac_depth}; do
   for V in ${VALUES:-1}; do
     for rep in $(seq 1 ${REPS:-1}); do
-      GRL_TUNE="${KEY}=${V}${EXTRA_TUNE:+,$EXTRA_TUNE}" python bench.py --workload $W --steps ${STEPS:-200} --warmup 20 --repeats 3 --no-cpu-baseline --no-learn-loop --no-success ${BENCH_ARGS-} 2>/dev/null | tail -1 | python3 -c "
+      GRL_TUNE="${KEY}=${V}${EXTRA_TUNE:+,$EXTRA_TUNE}" python bench.py --workload $W --steps ${STEPS:-200} --warmup 20 --full --repeats 3 --no-cpu-baseline --no-learn-loop --no-success ${BENCH_ARGS-} 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d['roofline']['step_kernel_ms'] if d.get('roofline') else {}

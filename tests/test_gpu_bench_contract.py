@@ -1,6 +1,7 @@
 """The line `bench.py` prints is what the driver reads: one JSON object with the contract's keys, the BASELINE metric and
-workload, a `roofline` whose numbers follow from each other, and a `cpu_baseline` from the oracle (the only place outside
-tests/ and smoke() where oracle/ runs -- never inside the timed region)."""
+workload; with --full also a `roofline` whose numbers follow from each other, and a `cpu_baseline` from the oracle (the only
+place outside tests/ and smoke() where oracle/ runs -- never inside the timed region).  A plain run times exactly --steps
+updates and does nothing else; --dump-outputs writes what the timed path computed, the same in every run."""
 import json
 import os
 import subprocess
@@ -24,7 +25,7 @@ def _bench(*args, env=None):
 
 
 def test_bench_line_contract():
-    d = _bench("--gpus", "1", "--steps", "40", "--warmup", "5", "--no-learn-loop", "--no-success")
+    d = _bench("--gpus", "1", "--steps", "40", "--warmup", "5", "--full", "--no-learn-loop", "--no-success")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -46,6 +47,32 @@ def test_bench_line_contract():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and "sample" in c
     assert d["value"] > 20 * c["value"]          # a GPU path that routed through the CPU oracle could not be this far ahead
+
+
+def test_plain_bench_times_only_the_steps_and_dumps_the_same_outputs_every_run(tmp_path):
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = _bench("--gpus", "1", "--steps", "40", "--warmup", "5", "--replay", "20000", "--dump-outputs", str(tmp_path / str(k)))
+        assert d["steps"] == 40 and d["warmup"] == 5 and "grad-steps" in d["metric"] and d["unit"] == "grad-steps/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 0.01
+        assert d["roofline"] is None and d["cpu_baseline"] is None       # --full only
+        assert not {"repeats", "learn_loop", "success_rate"} & set(d)
+        runs.append(d)
+    names = sorted(os.listdir(tmp_path / "0"))
+    assert names == sorted(os.listdir(tmp_path / "1")) and all(n.endswith(".npy") for n in names)
+    assert any(n.startswith("param_") for n in names) and "metric_policy_loss.npy" in names
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "0" / n), np.load(tmp_path / "1" / n)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape, n
+        assert np.array_equal(a, b), n
+        assert np.all(np.isfinite(a)), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    pl = float(np.load(tmp_path / "0" / "metric_policy_loss.npy"))      # the line's losses are the dumped step's
+    assert abs(pl - runs[0]["losses"]["policy_loss"]) <= 1e-6 * max(1.0, abs(pl))
 
 
 def test_bench_refuses_a_substituted_library():

@@ -366,12 +366,12 @@ def test_monitor_logs_are_readable_by_results_plotter(tmp_path):
     assert list(df.columns[:3]) == ["r", "l", "t"] and len(df) == 3 and np.all(df.l.values == 4)
     x, y = ts2xy(df, "timesteps")
     assert list(x) == [4, 8, 12] and len(y) == 3
-    shipped = "/root/reference/trained_models/SAC_depth_1mbuffer"
-    if os.path.isdir(shipped):
-        ref = load_results(shipped)
-        assert {"r", "l", "t", "s"} <= set(ref.columns) and len(ref) > 1000
-        xs, ys = ts2xy(ref, "timesteps", y_column="s")
-        assert np.all(np.diff(xs) > 0) and ys.min() >= 0.0 and ys.max() <= 1.0        # running success rate
+    # the first 1 500 episodes of the monitor log the reference ships (trained_models/SAC_depth_1mbuffer/log_file.monitor.csv)
+    shipped = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sac_depth_1mbuffer_monitor")
+    ref = load_results(shipped)
+    assert {"r", "l", "t", "s"} <= set(ref.columns) and len(ref) > 1000
+    xs, ys = ts2xy(ref, "timesteps", y_column="s")
+    assert np.all(np.diff(xs) > 0) and ys.min() >= 0.0 and ys.max() <= 1.0        # running success rate
 
 
 def test_running_statistics_on_the_device_equal_the_host_wrapper(hostemu_lib, emulated_engine):
