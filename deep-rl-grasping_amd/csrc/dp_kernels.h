@@ -173,6 +173,13 @@ __global__ __launch_bounds__(256) void dp_reduce_slabs_kernel(const ReduceDesc* 
   }
   gather_norm_dispatch<GROUPED>(ga, gx, (int)(x - before));
 }
+// (gx == 0: no gather rides, ga is not read)
+static inline void launch_dp_reduce_slabs(const ReduceDesc* descs, const int2* tiles, int n_tiles, const LossArgs& la, int has_loss,
+                                          const AdamArgs& aa, const DpArgs& a, const GatherArgs& ga, int gx, hipStream_t s) {
+  const dim3 grid(n_tiles + has_loss + (gx > 0 ? gather_blocks(ga, gx) : 0));
+  if (gx > 0 && ga.rows > 1) hipLaunchKernelGGL(dp_reduce_slabs_kernel<true>, grid, dim3(256), 0, s, descs, tiles, n_tiles, la, has_loss, aa, a, ga, gx);
+  else hipLaunchKernelGGL(dp_reduce_slabs_kernel<false>, grid, dim3(256), 0, s, descs, tiles, n_tiles, la, has_loss, aa, a, ga, gx);
+}
 
 // W: the only kernel that waits.  One wave: announce `ready` (which = 0) or `done` (which = 1) for the current exchange in
 // every rank's flags, wait for every rank's.  It also keeps next_buf in step (the source buffer of the NEXT exchange).

@@ -112,263 +112,131 @@ struct GatherArgs {
 // workgroups of a gather launch with gx tiles per row
 static inline int gather_blocks(const GatherArgs& a, int gx) { return a.rows > 1 ? gx * (2 * a.B / a.rows) : gx * a.B * 2; }
 
-// y / scale_div as TF's float32 division gives it.  For the one divisor the image paths use, 255, the quotient is formed
-// without the division sequence: q = y r, r = RN(1 / 255), one FMA refinement step q + fma(-255, q, y) r -- bit for bit the
-// IEEE quotient for EVERY float |y| <= 2^22, subnormal quotients included (checked exhaustively on the host: 1.26e9 values,
-// no mismatch; gfx950 keeps float32 subnormals): three full-rate instructions for about ten.
-__device__ __forceinline__ float scale_elem(float y, float scale_div) {
+// ---- normalise arithmetic: ONE copy of each core; every form of the gather below is a schedule over these
+// y / 255 as TF's float32 division gives it, without the division sequence: q = y r, r = RN(1 / 255), one FMA refinement step
+// q + fma(-255, q, y) r -- bit for bit the IEEE quotient for EVERY float |y| <= 2^22, subnormal quotients included (checked
+// exhaustively on the host: 1.26e9 values, no mismatch; gfx950 keeps float32 subnormals): three full-rate instructions for
+// about ten.
+__device__ __forceinline__ float div255_exact(float y) {
 #pragma clang fp contract(off)
-  if (scale_div == 255.f && __builtin_fabsf(y) <= 4194304.f) {
-    const float r = 1.f / 255.f;
-    const float q = y * r;
-    return __builtin_fmaf(__builtin_fmaf(-255.f, q, y), r, q);
-  }
+  const float r = 1.f / 255.f;
+  const float q = y * r;
+  return __builtin_fmaf(__builtin_fmaf(-255.f, q, y), r, q);
+}
+// y / scale_div for any divisor: 255, the one the image paths use, by div255_exact inside its range
+__device__ __forceinline__ float scale_elem(float y, float scale_div) {
+  if (scale_div == 255.f && __builtin_fabsf(y) <= 4194304.f) return div255_exact(y);
   return scale_div != 1.f ? y / scale_div : y;
 }
-
-__device__ __forceinline__ float norm_elem(float x, double mu, double sd, int normalize, double clip,
-                                           float scale_div) {
-  float y = x;
-  if (normalize) {
-    double z = ((double)x - mu) / sd;
-    z = __builtin_fmax(__builtin_fmin(z, clip), -clip);      // (np.clip; z is never a NaN: sd >= sqrt(eps) > 0)
-    y = (float)z;
-  }
-  return scale_elem(y, scale_div);
+__device__ __forceinline__ double clip_sym(double z, double clip) {      // (np.clip; z is never a NaN: sd >= sqrt(eps) > 0)
+  return __builtin_fmax(__builtin_fmin(z, clip), -clip);
 }
-
-// The same value with the float64 division (x - mu) / sd replaced by two FMA refinement steps on (x - mu) * r, r = RN(1 / sd):
-// q0 = d r; e = fma(-sd, q, d); q = fma(e, r, q), twice.  The first step leaves q within an ulp of d / sd, and with the
-// CORRECTLY ROUNDED reciprocal the second then yields the correctly rounded quotient (Markstein's theorem; the residual
-// e is exact in an FMA) -- the bits of the IEEE division, which a workgroup that owns several rows of the same element
-// positions (gather_norm_rows_body) pays once per position instead of once per element: on gfx950 the division expands to ~13
-// float64 instructions, three of them quarter rate, against these six (sub, mul, four FMAs).  400 000 000 random and adversarial
-// (x, mu, sd) on the host: no mismatch even after ONE step.  Ranges: d, sd, r normal numbers (sd >= sqrt(norm_eps)).
-__device__ __forceinline__ float norm_elem_rcp(float x, double mu, double sd, double r, double clip, float scale_div) {
+// d / sd in float64 by two FMA refinement steps on d * r, r = RN(1 / sd): q0 = d r; e = fma(-sd, q, d); q = fma(e, r, q), twice.
+// The first step leaves q within an ulp of d / sd, and with the CORRECTLY ROUNDED reciprocal the second then yields the
+// correctly rounded quotient (Markstein's theorem; the residual e is exact in an FMA) -- the bits of the IEEE division, which a
+// workgroup that owns several rows of the same element positions (gather_norm_rows_body) pays once per position instead of once
+// per element: on gfx950 the division expands to ~13 float64 instructions, three of them quarter rate, against these six (sub,
+// mul, four FMAs).  400 000 000 random and adversarial (x, mu, sd) on the host: no mismatch even after ONE step.
+// PRECONDITION: d, sd, r finite normal numbers (sd >= sqrt(norm_eps)) -- finite replay contents and statistics.  Outside it the
+// forms of the gather part: x = -inf gives the residual fma(-sd, -inf, -inf) = NaN, which clip_sym turns into +clip where the
+// division's -inf becomes -clip (and a NaN observation leaves clip_sym as +clip in every form, where np.clip keeps the NaN).
+// "The same bits in every form" is a statement about finite inputs.
+__device__ __forceinline__ double quot_refined(double d, double sd, double r) {
 #pragma clang fp contract(off)
-  const double d = (double)x - mu;
   double q = d * r;
   double e = __builtin_fma(-sd, q, d);
   q = __builtin_fma(e, r, q);
   e = __builtin_fma(-sd, q, d);
   q = __builtin_fma(e, r, q);
-  q = __builtin_fmax(__builtin_fmin(q, clip), -clip);
-  return scale_elem((float)q, scale_div);
+  return q;
 }
 
-// The same for the shape every CNN policy has -- normalised, divisor 255, clip <= 2^22 (so |y| is inside scale_elem's exact range
-// by construction) -- WITHOUT the per-element branch to the general division: that branch ends the basic block after every
-// element, so the compiler cannot interleave the float64 chains of the independent elements a thread holds (10 dependent float64
-// instructions each).  Measured on the riders of the head launch, one wave per SIMD: ~350 cycles per element with the branch.
+// FAST255: the shape every CNN policy has -- normalised, divisor 255, clip <= 2^22 (so |y| is inside div255_exact's range by
+// construction; norm_fast255, which the CALLER tests once, outside its element loop) -- WITHOUT the per-element branch to the
+// general division: that branch ends the basic block after every element, so the compiler cannot interleave the float64 chains
+// of the independent elements a thread holds (10 dependent float64 instructions each).  Measured on the riders of the head
+// launch, one wave per SIMD: ~350 cycles per element with the branch.  (normalize and scale_div are not read then.)
 __device__ __forceinline__ bool norm_fast255(int normalize, double clip, float scale_div) {
   return normalize && scale_div == 255.f && clip >= 0.0 && clip <= 4194304.0;
 }
-__device__ __forceinline__ float norm_elem_div255(float x, double mu, double sd, double clip) {      // (the division itself)
+// VecNormalize.normalize_obs on one element -- float64 as in the NumPy reference path, rounded to float32 once -- then the
+// float32 division by scale_div TF performs
+template <bool FAST255 = false>
+__device__ __forceinline__ float norm_elem(float x, double mu, double sd, int normalize, double clip, float scale_div) {
 #pragma clang fp contract(off)
-  double q = ((double)x - mu) / sd;
-  q = __builtin_fmax(__builtin_fmin(q, clip), -clip);
-  const float y = (float)q, r255 = 1.f / 255.f;
-  const float t = y * r255;
-  return __builtin_fmaf(__builtin_fmaf(-255.f, t, y), r255, t);
+  float y = x;
+  if (FAST255 || normalize) y = (float)clip_sym(((double)x - mu) / sd, clip);
+  return FAST255 ? div255_exact(y) : scale_elem(y, scale_div);
 }
-__device__ __forceinline__ float norm_elem_rcp255(float x, double mu, double sd, double r, double clip) {
+// The same value (normalize = 1) with the float64 division replaced by quot_refined on r = RN(1 / sd)
+template <bool FAST255 = false>
+__device__ __forceinline__ float norm_elem_rcp(float x, double mu, double sd, double r, double clip, float scale_div) {
 #pragma clang fp contract(off)
-  const double d = (double)x - mu;
-  double q = d * r;
-  double e = __builtin_fma(-sd, q, d);
-  q = __builtin_fma(e, r, q);
-  e = __builtin_fma(-sd, q, d);
-  q = __builtin_fma(e, r, q);
-  q = __builtin_fmax(__builtin_fmin(q, clip), -clip);
-  const float y = (float)q, r255 = 1.f / 255.f;
-  const float t = y * r255;
-  return __builtin_fmaf(__builtin_fmaf(-255.f, t, y), r255, t);
+  const float y = (float)clip_sym(quot_refined((double)x - mu, sd, r), clip);
+  return FAST255 ? div255_exact(y) : scale_elem(y, scale_div);
 }
 
-// One minibatch row (observation, next observation, action, reward, done) by the 256 threads of a workgroup: what the
-// blocks (*, b, 0..1) of gather_norm_kernel do for row b, element by element -- for launches that already own a row
-// (the prioritised sampler knows the replay index of its row and gathers it on the spot, per_kernels.h).
-__device__ __forceinline__ void gather_row_device(const GatherArgs& a, int b, int64_t src) {
-  const int t = threadIdx.x;
-  for (int which = 0; which < 2; ++which) {
-    const float* rp = which ? a.rp_next : a.rp_obs;
-    float* dst = which ? a.x_next : a.x_obs;
-    for (int e = t; e < a.img_elems; e += 256) {
-      const float y = norm_elem(rp[src * a.img_elems + e], a.normalize ? a.mean[e] : 0.0, a.normalize ? a.stdv[e] : 1.0,
-                                a.normalize, a.clip_obs, a.scale_div);
-      dst[(long)b * a.ldx + e] = y;
-      if (!which && a.x_obs2) a.x_obs2[(long)b * a.ldx + e] = y;
-    }
-    if (t < a.n_direct) {
-      const float* rd = which ? a.rp_dnext : a.rp_dobs;
-      const float y = norm_elem(rd[src * a.n_direct + t], a.normalize ? a.dmean[t] : 0.0, a.normalize ? a.dstd[t] : 1.0,
-                                a.normalize, a.clip_obs, a.scale_div);
-      if (which) a.d_next[(long)b * a.ldd + t] = y;
-      else { a.d_obs0[(long)b * a.ldd + t] = y; a.d_obs1[(long)b * a.ldd + t] = y; }
-    }
-  }
-  if (t < a.act_dim) {
-    const float av = a.rp_act[src * a.act_dim + t];
-    a.act_out[(long)b * a.ld_act + t] = av;
-    if (a.act_out2) a.act_out2[(long)b * a.ld_act2 + t] = av;
-  }
-  if (t == 64) {
-    float r = a.rp_rew[src];
-    if (a.normalize_rew) {
-      double z = (double)r / a.ret_std[0];
-      z = z < -a.clip_rew ? -a.clip_rew : (z > a.clip_rew ? a.clip_rew : z);
-      r = (float)z;
-    }
-    a.rew_out[b] = r;
-  }
-  if (t == 65) a.done_out[b] = a.rp_done[src];
+// ---- row helpers: the draws and the per-row duties, ONE copy each
+// replay index of minibatch row b at Philox counter `step`: uniform in [0, size)
+__device__ __forceinline__ int64_t replay_index_draw(uint64_t seed, uint64_t step, int b, int64_t size) {
+  uint32_t c[4] = {(uint32_t)step, (uint32_t)(step >> 32), (uint32_t)b, 0u};
+  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const uint64_t u = ((uint64_t)c[0] << 32) | c[1];
+  return size > 0 ? (int64_t)__umul64hi(u, (uint64_t)size) : 0;
 }
-// the Adam step size of the update that starts (TF ApplyAdam), and the beta powers for the next one
-__device__ __forceinline__ void adam_tick_device(DevScalars* sc) {
-  sc->adam_alpha = sc->lr * sqrtf(1.f - sc->beta2_power) / (1.f - sc->beta1_power);
-  sc->beta1_power *= 0.9f;
-  sc->beta2_power *= 0.999f;
+// standard normals j0, j0 + 1 of row b at counter `step`: one Philox draw, Box-Muller
+__device__ __forceinline__ void normal_pair_draw(uint64_t seed, uint64_t step, int b, int j0, float& n0, float& n1) {
+  uint32_t d[4] = {(uint32_t)step, (uint32_t)(step >> 32), (uint32_t)b, (uint32_t)(1 + j0)};
+  philox4x32_10(d, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const float u1 = ((float)(d[0] >> 8) + 0.5f) * (1.f / 16777216.f);
+  const float u2 = ((float)(d[1] >> 8) + 0.5f) * (1.f / 16777216.f);
+  const float rad = sqrtf(-2.f * logf(u1));
+  float sn, cs;
+  sincosf(6.283185307179586f * u2, &sn, &cs);
+  n0 = rad * cs;
+  n1 = rad * sn;
 }
-
-// block (bx, b, which) of the gather grid: elements [bx * per_block, ...) of row b of obs (which 0) / next_obs (1)
-__device__ __forceinline__ void gather_norm_body(const GatherArgs& a, const int bx, const int b, const int which) {
-  int64_t src;
-  uint64_t step = 0;
-  if (a.use_rng) {
-    step = a.img_ctr ? a.sc->rng_img : a.sc->rng_step + (uint64_t)a.rng_ahead;
-    const int64_t size = a.sc->replay_size;
-    uint32_t c[4] = {(uint32_t)step, (uint32_t)(step >> 32), (uint32_t)b, 0u};
-    philox4x32_10(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-    const uint64_t u = ((uint64_t)c[0] << 32) | c[1];
-    src = size > 0 ? (int64_t)__umul64hi(u, (uint64_t)size) : 0;
+// VecNormalize.normalize_reward at sample time
+__device__ __forceinline__ float reward_norm(const GatherArgs& a, float r) {
+  if (!a.normalize_rew) return r;
+  const double z = (double)r / a.ret_std[0];
+  return (float)(z < -a.clip_rew ? -a.clip_rew : (z > a.clip_rew ? a.clip_rew : z));
+}
+// replay index of row b: drawn at the launch's counter (left in `step`) in device-RNG mode, else the caller's
+__device__ __forceinline__ int64_t gather_row_src(const GatherArgs& a, int b, uint64_t& step) {
+  if (!a.use_rng) return a.idx[b];
+  step = a.img_ctr ? a.sc->rng_img : a.sc->rng_step + (uint64_t)a.rng_ahead;
+  return replay_index_draw(a.seed, step, b, a.sc->replay_size);
+}
+// element e of stored observation `src` of ring rp (byte-colour rings: channel e & 3 of pixel e >> 2)
+__device__ __forceinline__ float gather_load(const GatherArgs& a, const float* rp, int64_t src, int e) {
+  if (!a.rgb_u8) return rp[src * a.img_elems + e];
+  const int hwp = a.img_elems >> 2, px = e >> 2, ch = e & 3;
+  const float* ob = rp + src * (2 * hwp);
+  return ch == 3 ? ob[hwp + px] : (float)((((const uint32_t*)ob)[px] >> (8 * ch)) & 255u);
+}
+// element x of position e through norm_elem with the statistics of that position
+__device__ __forceinline__ float gather_norm_at(const GatherArgs& a, float x, const double* mean, const double* stdv, int e) {
+  return norm_elem(x, a.normalize ? mean[e] : 0.0, a.normalize ? stdv[e] : 1.0, a.normalize, a.clip_obs, a.scale_div);
+}
+// y (a float, or four of them) to offset o of the minibatch tensor of obs (which 0: both copies) / next_obs (1)
+template <class T>
+__device__ __forceinline__ void gather_store(const GatherArgs& a, int which, long o, T y) {
+  if (which) {
+    *(T*)(a.x_next + o) = y;
   } else {
-    src = a.idx[b];
-  }
-#ifndef GRL_HOSTEMU
-  if (a.parts == 2) {
-  } else if (a.vec4) {
-    typedef float gn_f4 __attribute__((ext_vector_type(4)));
-    typedef double gn_d4 __attribute__((ext_vector_type(4)));
-    const int e4 = (bx * 256 + threadIdx.x) * 4;
-    if (e4 < a.img_elems) {
-      const float* rp = which ? a.rp_next : a.rp_obs;
-      gn_f4 x;
-      if (a.rgb_u8) {            // one pixel per thread: colours from the packed dword, depth from the float plane
-        const int hwp = a.img_elems >> 2, px = e4 >> 2;
-        const float* ob = rp + src * (2 * hwp);
-        const uint32_t w = ((const uint32_t*)ob)[px];
-        x = gn_f4{(float)(w & 255u), (float)((w >> 8) & 255u), (float)((w >> 16) & 255u), ob[hwp + px]};
-      } else {
-        x = *(const gn_f4*)(rp + src * a.img_elems + e4);
-      }
-      gn_d4 mu = {0.0, 0.0, 0.0, 0.0}, sd = {1.0, 1.0, 1.0, 1.0};
-      if (a.normalize) { mu = *(const gn_d4*)(a.mean + e4); sd = *(const gn_d4*)(a.stdv + e4); }
-      gn_f4 y;
-      if (norm_fast255(a.normalize, a.clip_obs, a.scale_div)) {      // (uniform; four independent chains, no branch between them)
-        y.x = norm_elem_div255(x.x, mu.x, sd.x, a.clip_obs);
-        y.y = norm_elem_div255(x.y, mu.y, sd.y, a.clip_obs);
-        y.z = norm_elem_div255(x.z, mu.z, sd.z, a.clip_obs);
-        y.w = norm_elem_div255(x.w, mu.w, sd.w, a.clip_obs);
-      } else {
-      y.x = norm_elem(x.x, mu.x, sd.x, a.normalize, a.clip_obs, a.scale_div);
-      y.y = norm_elem(x.y, mu.y, sd.y, a.normalize, a.clip_obs, a.scale_div);
-      y.z = norm_elem(x.z, mu.z, sd.z, a.normalize, a.clip_obs, a.scale_div);
-      y.w = norm_elem(x.w, mu.w, sd.w, a.normalize, a.clip_obs, a.scale_div);
-      }
-      if (which) {
-        *(gn_f4*)(a.x_next + (long)b * a.ldx + e4) = y;
-      } else {
-        *(gn_f4*)(a.x_obs + (long)b * a.ldx + e4) = y;
-        if (a.x_obs2) *(gn_f4*)(a.x_obs2 + (long)b * a.ldx + e4) = y;
-      }
-    }
-  } else
-#endif
-  {
-  const int e = bx * 256 + threadIdx.x;
-  if (e < a.img_elems && a.parts != 2) {
-    const float* rp = which ? a.rp_next : a.rp_obs;
-    float x;
-    if (a.rgb_u8) {
-      const int hwp = a.img_elems >> 2, px = e >> 2, ch = e & 3;
-      const float* ob = rp + src * (2 * hwp);
-      x = ch == 3 ? ob[hwp + px] : (float)((((const uint32_t*)ob)[px] >> (8 * ch)) & 255u);
-    } else {
-      x = rp[src * a.img_elems + e];
-    }
-    const float y = norm_elem(x, a.normalize ? a.mean[e] : 0.0, a.normalize ? a.stdv[e] : 1.0,
-                              a.normalize, a.clip_obs, a.scale_div);
-    if (which) {
-      a.x_next[(long)b * a.ldx + e] = y;
-    } else {
-      a.x_obs[(long)b * a.ldx + e] = y;
-      if (a.x_obs2) a.x_obs2[(long)b * a.ldx + e] = y;
-    }
-  }
-  }
-  if (bx == 0 && a.parts != 1) {
-    const int t = threadIdx.x;
-    if (t < a.n_direct) {
-      const float* rp = which ? a.rp_dnext : a.rp_dobs;
-      const float x = rp[src * a.n_direct + t];
-      const float y = norm_elem(x, a.normalize ? a.dmean[t] : 0.0, a.normalize ? a.dstd[t] : 1.0,
-                                a.normalize, a.clip_obs, a.scale_div);
-      if (which) {
-        a.d_next[(long)b * a.ldd + t] = y;
-      } else {
-        a.d_obs0[(long)b * a.ldd + t] = y;
-        a.d_obs1[(long)b * a.ldd + t] = y;
-      }
-    }
-    if (which == 0) {
-      if (t < a.act_dim) {
-        const float av = a.rp_act[src * a.act_dim + t];
-        a.act_out[(long)b * a.ld_act + t] = av;
-        if (a.act_out2) a.act_out2[(long)b * a.ld_act2 + t] = av;
-      }
-      if (t == 64) {
-        float r = a.rp_rew[src];
-        if (a.normalize_rew) {
-          double z = (double)r / a.ret_std[0];
-          z = z < -a.clip_rew ? -a.clip_rew : (z > a.clip_rew ? a.clip_rew : z);
-          r = (float)z;
-        }
-        a.rew_out[b] = r;
-      }
-      if (t == 65) a.done_out[b] = a.rp_done[src];
-      if (a.use_rng) {
-        if (t == 66) a.idx_w[b] = src;
-        if (t >= 128 && 2 * (t - 128) < a.n_eps) {   // Box-Muller pairs, as rng_kernel
-          const int j0 = 2 * (t - 128);
-          uint32_t d[4] = {(uint32_t)step, (uint32_t)(step >> 32), (uint32_t)b, (uint32_t)(1 + j0)};
-          philox4x32_10(d, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-          const float u1 = ((float)(d[0] >> 8) + 0.5f) * (1.f / 16777216.f);
-          const float u2 = ((float)(d[1] >> 8) + 0.5f) * (1.f / 16777216.f);
-          const float rad = sqrtf(-2.f * logf(u1));
-          float sn, cs;
-          sincosf(6.283185307179586f * u2, &sn, &cs);
-          a.eps_w[b * a.n_eps + j0] = rad * cs;
-          if (j0 + 1 < a.n_eps) a.eps_w[b * a.n_eps + j0 + 1] = rad * sn;
-        }
-      }
-    }
-  }
-  // rng_step itself is advanced by the (single-workgroup) loss reduction later in the update: a counter
-  // bumped by the last of these 8192 workgroups would serialise 8192 same-address atomics (~100 us)
-  if (bx == 0 && b == 0 && which == 0 && threadIdx.x == 0 && !a.quiet && a.parts != 1) {
-    if (a.use_rng) a.sc->rng_used = 1u;
-    if (a.use_rng && a.set_img) a.sc->rng_img = step + 1;
-    if (a.adam_tick) adam_tick_device(a.sc);
+    *(T*)(a.x_obs + o) = y;
+    if (a.x_obs2) *(T*)(a.x_obs2 + o) = y;
   }
 }
-// the per-row duties of tile 0 (direct features, action, reward, done flag, the row's index and standard normals in device-RNG
-// mode): what gather_norm_body does under `bx == 0`, for the grouped form
-__device__ __forceinline__ void gather_row_extras(const GatherArgs& a, const int b, const int which, const int64_t src, const uint64_t step) {
+// The per-row duties, by the first 256 threads of a workgroup: direct features of obs (which 0) / next_obs (1) and, with the
+// obs half, action, reward, done flag and -- `draws`: device-RNG mode -- the row's index and standard normals.  The only
+// implementation: tile 0 of every form of the gather calls it.
+__device__ __forceinline__ void gather_row_extras(const GatherArgs& a, const int b, const int which, const int64_t src, const uint64_t step,
+                                                  const bool draws) {
   const int t = threadIdx.x;
   if (t < a.n_direct) {
-    const float* rp = which ? a.rp_dnext : a.rp_dobs;
-    const float y = norm_elem(rp[src * a.n_direct + t], a.normalize ? a.dmean[t] : 0.0, a.normalize ? a.dstd[t] : 1.0,
-                              a.normalize, a.clip_obs, a.scale_div);
+    const float y = gather_norm_at(a, (which ? a.rp_dnext : a.rp_dobs)[src * a.n_direct + t], a.dmean, a.dstd, t);
     if (which) a.d_next[(long)b * a.ldd + t] = y;
     else { a.d_obs0[(long)b * a.ldd + t] = y; a.d_obs1[(long)b * a.ldd + t] = y; }
   }
@@ -378,61 +246,129 @@ __device__ __forceinline__ void gather_row_extras(const GatherArgs& a, const int
     a.act_out[(long)b * a.ld_act + t] = av;
     if (a.act_out2) a.act_out2[(long)b * a.ld_act2 + t] = av;
   }
-  if (t == 64) {
-    float r = a.rp_rew[src];
-    if (a.normalize_rew) {
-      double z = (double)r / a.ret_std[0];
-      z = z < -a.clip_rew ? -a.clip_rew : (z > a.clip_rew ? a.clip_rew : z);
-      r = (float)z;
-    }
-    a.rew_out[b] = r;
-  }
+  if (t == 64) a.rew_out[b] = reward_norm(a, a.rp_rew[src]);
   if (t == 65) a.done_out[b] = a.rp_done[src];
-  if (a.use_rng) {
+  if (draws) {
     if (t == 66) a.idx_w[b] = src;
-    if (t >= 128 && 2 * (t - 128) < a.n_eps) {   // Box-Muller pairs, as gather_norm_body
+    if (t >= 128 && 2 * (t - 128) < a.n_eps) {
       const int j0 = 2 * (t - 128);
-      uint32_t d[4] = {(uint32_t)step, (uint32_t)(step >> 32), (uint32_t)b, (uint32_t)(1 + j0)};
-      philox4x32_10(d, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-      const float u1 = ((float)(d[0] >> 8) + 0.5f) * (1.f / 16777216.f);
-      const float u2 = ((float)(d[1] >> 8) + 0.5f) * (1.f / 16777216.f);
-      const float rad = sqrtf(-2.f * logf(u1));
-      float sn, cs;
-      sincosf(6.283185307179586f * u2, &sn, &cs);
-      a.eps_w[b * a.n_eps + j0] = rad * cs;
-      if (j0 + 1 < a.n_eps) a.eps_w[b * a.n_eps + j0 + 1] = rad * sn;
+      float n0, n1;
+      normal_pair_draw(a.seed, step, b, j0, n0, n1);
+      a.eps_w[b * a.n_eps + j0] = n0;
+      if (j0 + 1 < a.n_eps) a.eps_w[b * a.n_eps + j0 + 1] = n1;
     }
+  }
+}
+// the Adam step size of the update that starts (TF ApplyAdam), and the beta powers for the next one
+__device__ __forceinline__ void adam_tick_device(DevScalars* sc) {
+  sc->adam_alpha = sc->lr * sqrtf(1.f - sc->beta2_power) / (1.f - sc->beta1_power);
+  sc->beta1_power *= 0.9f;
+  sc->beta2_power *= 0.999f;
+}
+// what ONE thread of a gather launch that is not `quiet` leaves in the device scalars.  rng_step itself is advanced by the
+// (single-workgroup) loss reduction later in the update: a counter bumped by the last of these 8192 workgroups would
+// serialise 8192 same-address atomics (~100 us)
+__device__ __forceinline__ void gather_open_update(const GatherArgs& a, const uint64_t step) {
+  if (a.use_rng) a.sc->rng_used = 1u;
+  if (a.use_rng && a.set_img) a.sc->rng_img = step + 1;
+  if (a.adam_tick) adam_tick_device(a.sc);
+}
+
+#ifndef GRL_HOSTEMU
+// ---- the 16-byte forms: a thread moves four consecutive elements
+typedef float gn_f4 __attribute__((ext_vector_type(4)));
+typedef double gn_d4 __attribute__((ext_vector_type(4)));
+template <bool FAST255>
+__device__ __forceinline__ gn_f4 norm_elem4(gn_f4 x, gn_d4 mu, gn_d4 sd, int normalize, double clip, float scale_div) {
+  gn_f4 y;      // (four independent chains, no branch between them)
+  y.x = norm_elem<FAST255>(x.x, mu.x, sd.x, normalize, clip, scale_div);
+  y.y = norm_elem<FAST255>(x.y, mu.y, sd.y, normalize, clip, scale_div);
+  y.z = norm_elem<FAST255>(x.z, mu.z, sd.z, normalize, clip, scale_div);
+  y.w = norm_elem<FAST255>(x.w, mu.w, sd.w, normalize, clip, scale_div);
+  return y;
+}
+template <bool FAST255>
+__device__ __forceinline__ gn_f4 norm_elem_rcp4(gn_f4 x, gn_d4 mu, gn_d4 sd, gn_d4 rc, double clip, float scale_div) {
+  gn_f4 y;
+  y.x = norm_elem_rcp<FAST255>(x.x, mu.x, sd.x, rc.x, clip, scale_div);
+  y.y = norm_elem_rcp<FAST255>(x.y, mu.y, sd.y, rc.y, clip, scale_div);
+  y.z = norm_elem_rcp<FAST255>(x.z, mu.z, sd.z, rc.z, clip, scale_div);
+  y.w = norm_elem_rcp<FAST255>(x.w, mu.w, sd.w, rc.w, clip, scale_div);
+  return y;
+}
+// one pixel of a byte-colour ring: colours from its packed dword (R | G << 8 | B << 16), depth from the float plane
+__device__ __forceinline__ gn_f4 rgbd_pixel(uint32_t w, float depth) {
+  return gn_f4{(float)(w & 255u), (float)((w >> 8) & 255u), (float)((w >> 16) & 255u), depth};
+}
+#endif
+
+// One minibatch row (observation, next observation, action, reward, done) by the 256 threads of a workgroup: what the
+// blocks (*, b, 0..1) of gather_norm_kernel do for row b, element by element -- for launches that already own a row
+// (the prioritised sampler knows the replay index of its row and gathers it on the spot, per_kernels.h; the index and the
+// noise are the sampler's: nothing is drawn here, whatever use_rng says).  float32 rings only.
+__device__ __forceinline__ void gather_row_device(const GatherArgs& a, int b, int64_t src) {
+  for (int which = 0; which < 2; ++which) {
+    const float* rp = which ? a.rp_next : a.rp_obs;
+    for (int e = threadIdx.x; e < a.img_elems; e += 256)
+      gather_store(a, which, (long)b * a.ldx + e, gather_norm_at(a, rp[src * a.img_elems + e], a.mean, a.stdv, e));
+    gather_row_extras(a, b, which, src, 0, false);
+  }
+}
+
+// block (bx, b, which) of the gather grid: elements [bx * per_block, ...) of row b of obs (which 0) / next_obs (1)
+__device__ __forceinline__ void gather_norm_body(const GatherArgs& a, const int bx, const int b, const int which) {
+  uint64_t step = 0;
+  const int64_t src = gather_row_src(a, b, step);
+  const float* rp = which ? a.rp_next : a.rp_obs;
+#ifndef GRL_HOSTEMU
+  if (a.parts == 2) {
+  } else if (a.vec4) {
+    const int e4 = (bx * 256 + threadIdx.x) * 4;
+    if (e4 < a.img_elems) {
+      gn_f4 x;
+      if (a.rgb_u8) {            // one pixel per thread
+        const int hwp = a.img_elems >> 2, px = e4 >> 2;
+        const float* ob = rp + src * (2 * hwp);
+        x = rgbd_pixel(((const uint32_t*)ob)[px], ob[hwp + px]);
+      } else {
+        x = *(const gn_f4*)(rp + src * a.img_elems + e4);
+      }
+      gn_d4 mu = {0.0, 0.0, 0.0, 0.0}, sd = {1.0, 1.0, 1.0, 1.0};
+      if (a.normalize) { mu = *(const gn_d4*)(a.mean + e4); sd = *(const gn_d4*)(a.stdv + e4); }
+      gn_f4 y;
+      if (norm_fast255(a.normalize, a.clip_obs, a.scale_div)) y = norm_elem4<true>(x, mu, sd, 1, a.clip_obs, 255.f);      // (uniform)
+      else y = norm_elem4<false>(x, mu, sd, a.normalize, a.clip_obs, a.scale_div);
+      gather_store(a, which, (long)b * a.ldx + e4, y);
+    }
+  } else
+#endif
+  {
+    const int e = bx * 256 + threadIdx.x;
+    if (e < a.img_elems && a.parts != 2)
+      gather_store(a, which, (long)b * a.ldx + e, gather_norm_at(a, gather_load(a, rp, src, e), a.mean, a.stdv, e));
+  }
+  if (bx == 0 && a.parts != 1) {
+    gather_row_extras(a, b, which, src, step, a.use_rng);
+    if (b == 0 && which == 0 && threadIdx.x == 0 && !a.quiet) gather_open_update(a, step);
   }
 }
 
 #ifndef GRL_HOSTEMU
 // Grouped form (GatherArgs.rows = R > 1): workgroup (bx, grp) moves tile bx -- elements [1024 bx, 1024 bx + 1024) -- of the R
 // row instances grp R .. grp R + R - 1 of the 2 B (obs rows first, then next_obs rows; R divides B, so a group is all obs or all
-// next_obs).  Same arithmetic per element as gather_norm_body (norm_elem), hence the same bits.  What changes is the shape of
-// the latency chain: one Philox draw per lane (lane r holds row r's index, the others read it with a lane broadcast), the
-// statistics of the thread's four element positions loaded ONCE, and the R replay reads issued back to back before the first
-// is consumed -- a workgroup lives about as long as a one-row workgroup does and there are R times fewer of them.
-// BRANCH_FREE: take norm_elem_rcp255's loop when the arguments allow it.  It keeps all R results live (the point: R x 4 chains
+// next_obs).  What changes against gather_norm_body is the shape of the latency chain: one Philox draw per lane (lane r holds row
+// r's index, the others read it with a lane broadcast), the statistics of the thread's four element positions loaded ONCE -- the
+// float64 division becomes quot_refined on a per-position reciprocal -- and the R replay reads issued back to back before the
+// first is consumed: a workgroup lives about as long as a one-row workgroup does and there are R times fewer of them.
+// BRANCH_FREE: take the FAST255 loop when the arguments allow it.  It keeps all R results live (the point: R x 4 chains
 // in flight), which the kernels built for 8 waves per SIMD cannot afford (reduce_slabs_gather_kernel: 36 bytes of scratch per
 // lane and 4 660 against 4 740 updates/s on the RGB-D ring): those keep the one-element-at-a-time loop.
 template <int R, bool BRANCH_FREE = false>
 __device__ __forceinline__ void gather_norm_rows_body(const GatherArgs& a, const int bx, const int grp) {
-  typedef float gn_f4 __attribute__((ext_vector_type(4)));
-  typedef double gn_d4 __attribute__((ext_vector_type(4)));
   const int i0 = grp * R, which = i0 >= a.B ? 1 : 0, b0 = i0 - which * a.B;
   const int lane = (int)(threadIdx.x & 63u);
   uint64_t step = 0;
-  int64_t mine;
-  if (a.use_rng) {
-    step = a.img_ctr ? a.sc->rng_img : a.sc->rng_step + (uint64_t)a.rng_ahead;
-    const int64_t size = a.sc->replay_size;
-    uint32_t c[4] = {(uint32_t)step, (uint32_t)(step >> 32), (uint32_t)(b0 + (lane % R)), 0u};
-    philox4x32_10(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-    const uint64_t u = ((uint64_t)c[0] << 32) | c[1];
-    mine = size > 0 ? (int64_t)__umul64hi(u, (uint64_t)size) : 0;
-  } else {
-    mine = a.idx[b0 + (lane % R)];
-  }
+  const int64_t mine = gather_row_src(a, b0 + (lane % R), step);
   int64_t src[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -444,7 +380,7 @@ __device__ __forceinline__ void gather_norm_rows_body(const GatherArgs& a, const
   if (e4 < a.img_elems && a.parts != 2) {
     const float* rp = which ? a.rp_next : a.rp_obs;
     gn_f4 x[R];
-    if (a.rgb_u8) {            // one pixel per thread: colours from the packed dword, depth from the float plane
+    if (a.rgb_u8) {            // one pixel per thread
       const int hwp = a.img_elems >> 2, px = e4 >> 2;
       uint32_t w[R];
       float d[R];
@@ -455,7 +391,7 @@ __device__ __forceinline__ void gather_norm_rows_body(const GatherArgs& a, const
         d[r] = ob[hwp + px];
       }
 #pragma unroll
-      for (int r = 0; r < R; ++r) x[r] = gn_f4{(float)(w[r] & 255u), (float)((w[r] >> 8) & 255u), (float)((w[r] >> 16) & 255u), d[r]};
+      for (int r = 0; r < R; ++r) x[r] = rgbd_pixel(w[r], d[r]);
     } else {
 #pragma unroll
       for (int r = 0; r < R; ++r) x[r] = *(const gn_f4*)(rp + src[r] * a.img_elems + e4);
@@ -469,54 +405,22 @@ __device__ __forceinline__ void gather_norm_rows_body(const GatherArgs& a, const
     if (fast) {
       gn_f4 y[R];
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
-        y[r].x = norm_elem_rcp255(x[r].x, mu.x, sd.x, rc.x, a.clip_obs);
-        y[r].y = norm_elem_rcp255(x[r].y, mu.y, sd.y, rc.y, a.clip_obs);
-        y[r].z = norm_elem_rcp255(x[r].z, mu.z, sd.z, rc.z, a.clip_obs);
-        y[r].w = norm_elem_rcp255(x[r].w, mu.w, sd.w, rc.w, a.clip_obs);
-      }
+      for (int r = 0; r < R; ++r) y[r] = norm_elem_rcp4<true>(x[r], mu, sd, rc, a.clip_obs, 255.f);
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const long o = (long)(b0 + r) * a.ldx + e4;
-        if (which) {
-          *(gn_f4*)(a.x_next + o) = y[r];
-        } else {
-          *(gn_f4*)(a.x_obs + o) = y[r];
-          if (a.x_obs2) *(gn_f4*)(a.x_obs2 + o) = y[r];
-        }
-      }
+      for (int r = 0; r < R; ++r) gather_store(a, which, (long)(b0 + r) * a.ldx + e4, y[r]);
     } else
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       gn_f4 y;
-      if (a.normalize) {
-        y.x = norm_elem_rcp(x[r].x, mu.x, sd.x, rc.x, a.clip_obs, a.scale_div);
-        y.y = norm_elem_rcp(x[r].y, mu.y, sd.y, rc.y, a.clip_obs, a.scale_div);
-        y.z = norm_elem_rcp(x[r].z, mu.z, sd.z, rc.z, a.clip_obs, a.scale_div);
-        y.w = norm_elem_rcp(x[r].w, mu.w, sd.w, rc.w, a.clip_obs, a.scale_div);
-      } else {
-        y.x = norm_elem(x[r].x, 0.0, 1.0, 0, a.clip_obs, a.scale_div);
-        y.y = norm_elem(x[r].y, 0.0, 1.0, 0, a.clip_obs, a.scale_div);
-        y.z = norm_elem(x[r].z, 0.0, 1.0, 0, a.clip_obs, a.scale_div);
-        y.w = norm_elem(x[r].w, 0.0, 1.0, 0, a.clip_obs, a.scale_div);
-      }
-      const long o = (long)(b0 + r) * a.ldx + e4;
-      if (which) {
-        *(gn_f4*)(a.x_next + o) = y;
-      } else {
-        *(gn_f4*)(a.x_obs + o) = y;
-        if (a.x_obs2) *(gn_f4*)(a.x_obs2 + o) = y;
-      }
+      if (a.normalize) y = norm_elem_rcp4<false>(x[r], mu, sd, rc, a.clip_obs, a.scale_div);
+      else y = norm_elem4<false>(x[r], mu, sd, 0, a.clip_obs, a.scale_div);
+      gather_store(a, which, (long)(b0 + r) * a.ldx + e4, y);
     }
   }
   if (bx == 0 && a.parts != 1) {
 #pragma unroll 1
-    for (int r = 0; r < R; ++r) gather_row_extras(a, b0 + r, which, src[r], step);
-    if (grp == 0 && threadIdx.x == 0 && !a.quiet) {
-      if (a.use_rng) a.sc->rng_used = 1u;
-      if (a.use_rng && a.set_img) a.sc->rng_img = step + 1;
-      if (a.adam_tick) adam_tick_device(a.sc);
-    }
+    for (int r = 0; r < R; ++r) gather_row_extras(a, b0 + r, which, src[r], step, a.use_rng);
+    if (grp == 0 && threadIdx.x == 0 && !a.quiet) gather_open_update(a, step);
   }
 }
 #endif
@@ -524,7 +428,7 @@ __device__ __forceinline__ void gather_norm_rows_body(const GatherArgs& a, const
 // Workgroup r of the image gather that rides on the head launch (heads_mfma.h; GatherArgs.parts == 1, vec4, B a multiple of
 // GATHER_RIDE_ROWS): tile r % gx of the GATHER_RIDE_ROWS row instances of group r / gx -- the head kernel is compiled for one
 // wave per SIMD (245 registers), so a rider workgroup is alone on its CU and keeps 16 replay reads in flight per lane instead of
-// relying on neighbours to hide its latency.  Same arithmetic per element as every other form of the gather.
+// relying on neighbours to hide its latency.  rows is 4, 8 or 16 (gather_ride_rows_built, checked where the plan sets it).
 static inline int gather_rider_blocks(const GatherArgs& a, int gx) { return gx * (2 * a.B / a.rows); }
 __device__ __forceinline__ void gather_images_rider(const GatherArgs& a, const int gx, const int r) {
 #ifndef GRL_HOSTEMU
@@ -540,15 +444,15 @@ __device__ __forceinline__ void gather_images_rider(const GatherArgs& a, const i
 }
 
 // workgroup r of a linearised gather grid (gather_blocks) with gx tiles per row.  GROUPED is a compile-time choice of the
-// LAUNCH (the plan picks the kernel by GatherArgs.rows): a kernel that could take either form is allocated the registers of
-// the larger one -- 69 instead of 64 for the reduction + gather launch, one wave per SIMD less for the one-row form
+// LAUNCH (launch_gather and its kin pick the kernel by GatherArgs.rows): a kernel that could take either form is allocated the
+// registers of the larger one -- 69 instead of 64 for the reduction + gather launch, one wave per SIMD less for the one-row form
 template <bool GROUPED>
 __device__ __forceinline__ void gather_norm_dispatch(const GatherArgs& a, const int gx, const int r) {
 #ifndef GRL_HOSTEMU
   if (GROUPED) {
     const int bx = r % gx, grp = r / gx;
-    // (two instantiations only: the launch that carries this body is compiled for the largest of them -- with R = 16 in the
-    // list reduce_slabs_gather_kernel went from 64 to 95 registers and spilled)
+    // (two instantiations only -- rows is 2 or 4 here, gather_rows_built: the launch that carries this body is compiled for the
+    // largest of them -- with R = 16 in the list reduce_slabs_gather_kernel went from 64 to 95 registers and spilled)
     if (a.rows == 2) gather_norm_rows_body<2>(a, bx, grp);
     else gather_norm_rows_body<4>(a, bx, grp);
     return;
@@ -1590,21 +1494,12 @@ __global__ __launch_bounds__(256) void rng_kernel(RngArgs a) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   const uint64_t step = a.sc->rng_step;
   if (b < a.B) {
-    const int64_t size = a.sc->replay_size;
-    uint32_t c[4] = {(uint32_t)step, (uint32_t)(step >> 32), (uint32_t)b, 0u};
-    philox4x32_10(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-    const uint64_t u = ((uint64_t)c[0] << 32) | c[1];
-    a.idx[b] = size > 0 ? (int64_t)__umul64hi(u, (uint64_t)size) : 0;
+    a.idx[b] = replay_index_draw(a.seed, step, b, a.sc->replay_size);
     for (int j0 = 0; j0 < a.A; j0 += 2) {
-      uint32_t d[4] = {(uint32_t)step, (uint32_t)(step >> 32), (uint32_t)b, (uint32_t)(1 + j0)};
-      philox4x32_10(d, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-      const float u1 = ((float)(d[0] >> 8) + 0.5f) * (1.f / 16777216.f);
-      const float u2 = ((float)(d[1] >> 8) + 0.5f) * (1.f / 16777216.f);
-      const float rad = sqrtf(-2.f * logf(u1));
-      float sn, cs;
-      sincosf(6.283185307179586f * u2, &sn, &cs);
-      a.eps[b * a.A + j0] = rad * cs;
-      if (j0 + 1 < a.A) a.eps[b * a.A + j0 + 1] = rad * sn;
+      float n0, n1;
+      normal_pair_draw(a.seed, step, b, j0, n0, n1);
+      a.eps[b * a.A + j0] = n0;
+      if (j0 + 1 < a.A) a.eps[b * a.A + j0 + 1] = n1;
     }
     if (a.ones) a.ones[b] = 1.f;
   }
@@ -1731,6 +1626,22 @@ static inline void launch_q_loss(const QLossArgs& a, hipStream_t s) {
   if (a.n <= 64) hipLaunchKernelGGL(q_loss_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(q_loss_rows_kernel, dim3(1), dim3(256), 0, s, a);
 #endif
+}
+// The replay gather: GatherArgs.rows picks the grouped or the one-row kernel, here and nowhere else.  The row counts the
+// kernels instantiate -- a plan that sets any other fails with GRL_ERR_INVALID where it builds the GatherArgs, so the last
+// branch of gather_norm_dispatch / gather_images_rider is taken by the count it names and by no other.
+static inline bool gather_rows_built(int rows) { return rows == 1 || rows == 2 || rows == 4; }
+static inline bool gather_ride_rows_built(int rows) { return rows == 4 || rows == 8 || rows == 16; }
+static inline void launch_gather(const GatherArgs& ga, int gx, hipStream_t s) {
+  if (ga.rows > 1) hipLaunchKernelGGL(gather_norm_lin_kernel, dim3(gather_blocks(ga, gx)), dim3(256), 0, s, ga, gx);
+  else hipLaunchKernelGGL(gather_norm_kernel, dim3(gx, ga.B, 2), dim3(256), 0, s, ga);
+}
+// the reduction + Adam launch that ends an update, carrying the gather (or its parts) of the next one
+static inline void launch_reduce_slabs_gather(const ReduceDesc* descs, const int2* tiles, int n_tiles, const LossArgs& la, int has_loss,
+                                              const AdamArgs& aa, const GatherArgs& ga, int gx, hipStream_t s) {
+  const dim3 grid(n_tiles + has_loss + gather_blocks(ga, gx));
+  if (ga.rows > 1) hipLaunchKernelGGL(reduce_slabs_gather_kernel<true>, grid, dim3(256), 0, s, descs, tiles, n_tiles, la, has_loss, aa, 1, ga, gx);
+  else hipLaunchKernelGGL(reduce_slabs_gather_kernel<false>, grid, dim3(256), 0, s, descs, tiles, n_tiles, la, has_loss, aa, 1, ga, gx);
 }
 // 16-byte forms of the element-wise kernels (gather_norm's vec4 rows, the reduction's quads): device build only
 static inline bool elem_vec4_built() {

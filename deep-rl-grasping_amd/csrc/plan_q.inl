@@ -234,7 +234,7 @@ int grl_ctx::plan_q() {
     op.run = [ga, q_defer](hipStream_t s) {
       GatherArgs g2 = ga;
       g2.adam_tick = *q_defer;        // deferred loss sums: the Adam step size of the update is fixed here, as in the SAC plan
-      hipLaunchKernelGGL(gather_norm_kernel, dim3((g2.img_elems + 255) / 256, g2.B, 2), dim3(256), 0, s, g2);
+      launch_gather(g2, (g2.img_elems + 255) / 256, s);      // (scalar form, one row per workgroup)
     };
     ops_grads.push_back(op);
   }

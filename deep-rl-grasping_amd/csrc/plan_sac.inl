@@ -174,8 +174,9 @@ int grl_ctx::plan_sac() {
     // rows per workgroup of the grouped form (elem_kernels.h: gather_norm_rows_body); GRL_TUNE gather_rows=1 keeps one row each
     {
       int rows = tune_int("gather_rows", c.replay_rgb_u8 ? GATHER_ROWS_U8 : GATHER_ROWS_F32);
-      if (!ga.vec4 || (rows != 2 && rows != 4) || B % rows) rows = 1;
+      if (!ga.vec4 || !gather_rows_built(rows) || B % rows) rows = 1;
       ga.rows = rows;
+      if (!gather_rows_built(ga.rows)) return fail(GRL_ERR_INVALID, "gather: no kernel for this many rows per workgroup");
     }
     pf_ga = ga;
     pf_gx = (ga.img_elems + per_block - 1) / per_block;
@@ -184,10 +185,7 @@ int grl_ctx::plan_sac() {
       Op op; op.tag = "gather_norm";
       op.bytes = 2.0 * B * ((double)img_elems * 4 + (double)obs_store * 4 + 4.0 * nd) + B * (4.0 * A + 8) * 2;
       const int gx0 = pf_gx;
-      op.run = [ga, gx0](hipStream_t s) {
-        if (ga.rows > 1) hipLaunchKernelGGL(gather_norm_lin_kernel, dim3(gather_blocks(ga, gx0)), dim3(256), 0, s, ga, gx0);
-        else hipLaunchKernelGGL(gather_norm_kernel, dim3(gx0, ga.B, 2), dim3(256), 0, s, ga);
-      };
+      op.run = [ga, gx0](hipStream_t s) { launch_gather(ga, gx0, s); };
       (mode ? ops_rng : ops_gather).push_back(op);
     }
   }
@@ -811,10 +809,7 @@ int grl_ctx::plan_sac() {
         {
           Op op; op.tag = "gather_norm";
           op.bytes = ops_rng[0].bytes;
-          op.run = [g1, gx](hipStream_t s) {
-            if (g1.rows > 1) hipLaunchKernelGGL(gather_norm_lin_kernel, dim3(gather_blocks(g1, gx)), dim3(256), 0, s, g1, gx);
-            else hipLaunchKernelGGL(gather_norm_kernel, dim3(gx, g1.B, 2), dim3(256), 0, s, g1);
-          };
+          op.run = [g1, gx](hipStream_t s) { launch_gather(g1, gx, s); };
           ops_pf_first.push_back(op);
         }
         GatherArgs g2 = g1;
@@ -827,11 +822,7 @@ int grl_ctx::plan_sac() {
         AdamArgs aq = aa;
         aq.skip_bucket = 1;                 // (the call's last update -- `fo` -- leaves its gradients in the bucket)
         ro.bytes -= (double)n_train * 4;
-        ro.run = [dr, d_rt, ntiles, lk, has_loss, aq, g2, gx](hipStream_t s) {
-          const dim3 grid(ntiles + has_loss + gather_blocks(g2, gx));
-          if (g2.rows > 1) hipLaunchKernelGGL(reduce_slabs_gather_kernel<true>, grid, dim3(256), 0, s, dr, d_rt, ntiles, lk, has_loss, aq, 1, g2, gx);
-          else hipLaunchKernelGGL(reduce_slabs_gather_kernel<false>, grid, dim3(256), 0, s, dr, d_rt, ntiles, lk, has_loss, aq, 1, g2, gx);
-        };
+        ro.run = [dr, d_rt, ntiles, lk, has_loss, aq, g2, gx](hipStream_t s) { launch_reduce_slabs_gather(dr, d_rt, ntiles, lk, has_loss, aq, g2, gx, s); };
         for (int v = 0; v < 3; ++v) {     // 0 first, 1 middle, 2 last
           std::vector<Op>& dst = v == 0 ? ops_pf_first : (v == 1 ? ops_pf_mid : ops_pf_last);
           for (size_t k = 0; k + 1 < ops_grads_apply.size(); ++k) {
@@ -867,7 +858,7 @@ int grl_ctx::plan_sac() {
               have_conv_alt = true;
             }
           int ride_rows = tune_int("ride_rows", GATHER_RIDE_ROWS);
-          if (ride_rows != 4 && ride_rows != 8 && ride_rows != 16) ride_rows = GATHER_RIDE_ROWS;
+          if (!gather_ride_rows_built(ride_rows)) ride_rows = GATHER_RIDE_ROWS;
           if (have_conv_alt) {
             GatherArgs gx2 = g2;                         // extras of update t+1, carried by update t's reduction launch
             gx2.parts = 2;
@@ -876,20 +867,13 @@ int grl_ctx::plan_sac() {
             Op rx; rx.tag = "reduce_adam";
             rx.join = true;
             rx.bytes = ro.bytes - ops_rng[0].bytes;
-            rx.run = [dr, d_rt, ntiles, lr3, has_loss, aq, gx2](hipStream_t s) {
-              const dim3 grid(ntiles + has_loss + gather_blocks(gx2, 1));
-              if (gx2.rows > 1) hipLaunchKernelGGL(reduce_slabs_gather_kernel<true>, grid, dim3(256), 0, s, dr, d_rt, ntiles, lr3, has_loss, aq, 1, gx2, 1);
-              else hipLaunchKernelGGL(reduce_slabs_gather_kernel<false>, grid, dim3(256), 0, s, dr, d_rt, ntiles, lr3, has_loss, aq, 1, gx2, 1);
-            };
+            rx.run = [dr, d_rt, ntiles, lr3, has_loss, aq, gx2](hipStream_t s) { launch_reduce_slabs_gather(dr, d_rt, ntiles, lr3, has_loss, aq, gx2, 1, s); };
             ride_lk = lr3; ride_g2 = gx2;
             Op first_g = ops_pf_first[0];                // the call's own gather, leaving rng_img behind
             {
               GatherArgs g0 = g1;
               g0.set_img = 1;
-              first_g.run = [g0, gx](hipStream_t s) {
-                if (g0.rows > 1) hipLaunchKernelGGL(gather_norm_lin_kernel, dim3(gather_blocks(g0, gx)), dim3(256), 0, s, g0, gx);
-                else hipLaunchKernelGGL(gather_norm_kernel, dim3(gx, g0.B, 2), dim3(256), 0, s, g0);
-              };
+              first_g.run = [g0, gx](hipStream_t s) { launch_gather(g0, gx, s); };
             }
             const HeadsFusedArgs* d_ha = ride_heads_args;
             const int hshape = ride_heads_shape, hnblk = ride_heads_nblk;
@@ -897,6 +881,7 @@ int grl_ctx::plan_sac() {
               GatherArgs gi = g2;                        // images of update t+1 into the buffer flavour f does NOT read
               gi.parts = 1; gi.img_ctr = 1; gi.rng_ahead = 0; gi.quiet = 1;
               gi.rows = ride_rows;
+              if (!gather_ride_rows_built(gi.rows)) return fail(GRL_ERR_INVALID, "gather_ride: no kernel for this many rows per rider workgroup");
               gi.x_obs = f ? x_obs : x_obs_b;
               Op heads_ride[2];                          // [0] the call's first update, [1] later ones (see pf_heads)
               for (int v = 0; v < 2; ++v) {

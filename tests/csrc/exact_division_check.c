@@ -1,5 +1,5 @@
-/* Host check of the two division-free forms the gather kernels use (csrc/elem_kernels.h: scale_elem, norm_elem_rcp /
- * norm_elem_rcp255).  Test infrastructure only: built and run by tests/test_exact_division.py.
+/* Host check of the two division-free forms the gather kernels use (csrc/elem_kernels.h: div255_exact, quot_refined --
+ * restated here on purpose).  Test infrastructure only: built and run by tests/test_exact_division.py.
  *   mode 0: y / 255 in float32 == q + fma(-255, q, y) * r with q = y * r, r = RN(1 / 255), for EVERY float 0 <= y <= 2^22
  *           (the form is odd in y, so the negative half follows)
  *   mode 1: ((double)x - mu) / sd == two FMA refinement steps on d * r, r = RN(1 / sd) (an IEEE division), over n random and

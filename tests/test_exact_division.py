@@ -1,5 +1,5 @@
 """The gather kernels replace two divisions by FMA forms and claim the bits of the IEEE quotient (csrc/elem_kernels.h:
-scale_elem -- y / 255 in float32, one refinement step; norm_elem_rcp / norm_elem_rcp255 -- (x - mu) / sd in float64, two steps on
+div255_exact -- y / 255 in float32, one refinement step; quot_refined (norm_elem_rcp) -- (x - mu) / sd in float64, two steps on
 the correctly rounded reciprocal).  The device keeps float32 subnormals and has correctly rounded fma / float64 division, so the
 identities are properties of IEEE arithmetic: checked here on the host, the float32 one for EVERY float up to 2^22."""
 import os

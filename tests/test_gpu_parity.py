@@ -331,7 +331,7 @@ def test_image_gather_riding_on_the_head_launch_is_bit_identical_b256(monkeypatc
             monkeypatch.delenv("GRL_TUNE")
         return out
     ref = run([1] * 7)
-    for got in (run([3, 4], tune="gather_ride=1"), run([7], tune="gather_ride=0")):     # (the byte-colour ring's default is off)
+    for got in (run([3, 4], tune="gather_ride=1"), run([7], tune="gather_ride=0")):     # (the riding gather is the default on both rings)
         assert all(np.array_equal(ref[0][n], got[0][n]) for n in ref[0])
         assert all(np.array_equal(a, b) for a, b in zip(ref[1:4], got[1:4]))
         assert ref[5] == got[5]
