@@ -687,9 +687,52 @@ int grl_get_metrics(grl_handle h, grl_metrics* out) {
   return GRL_OK;
 }
 
+// the completion of the act path's last launch: poll its counter in coherent host memory (bounded -- after 2 ms, or on any
+// doubt, the stream is synchronised) or, without a counter / under grl_profile_enable, synchronise the stream
+static int act_wait(grl_handle h, unsigned wgs) {
+  const bool poll = wgs && !h->prof;
+  bool seen = false;
+  if (wgs) h->act_done_seen += wgs;
+  if (poll) {
+    const unsigned want = h->act_done_seen;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spin = 0;; ++spin) {
+      if ((int)(__atomic_load_n(h->act_done_host, __ATOMIC_ACQUIRE) - want) >= 0) { seen = true; break; }
+      if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+    }
+  }
+  if (!seen) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->act_done_host) h->act_done_seen = __atomic_load_n(h->act_done_host, __ATOMIC_ACQUIRE);
+  }
+  HIPCHK(hipGetLastError());
+  return GRL_OK;
+}
+
+// grl_act(GRL_ACT_GREEDY) on a DQN / BDQ handle: bins [n, D] (plan_q.inl; q_act.h).  Observations, overrides and bins live
+// in coherent host memory the launch reads and writes: the previous call has waited for its launch, so they are free
+static int act_greedy(grl_handle h, const float* obs, int n, const float* explore, float* out) {
+  if (!h->q_io_host) return fail(GRL_ERR_STATE, "this handle has no act path");
+  const int D = h->qD, od = h->cfg.obs_dim;
+  float* io_obs = h->q_io_host; float* io_explore = io_obs + (size_t)h->NA * od; float* io_bins = io_explore + (size_t)h->NA * D;
+  if (h->q_act_fused) memcpy(io_obs, obs, (size_t)n * od * 4);
+  else {
+    if (int e = pin_reserve(h, (size_t)n * od, 0)) return e;
+    memcpy(h->pin_in, obs, (size_t)n * od * 4);
+    HIPCHK(hipMemcpyAsync(h->stg_obs, h->pin_in, (size_t)n * od * 4, hipMemcpyHostToDevice, h->stream));
+  }
+  if (explore) memcpy(io_explore, explore, (size_t)n * D * 4);
+  else for (int i = 0; i < n * D; ++i) io_explore[i] = -1.f;
+  __atomic_thread_fence(__ATOMIC_RELEASE);
+  if (int e = h->run_seq("act_greedy", {&h->ops_act_greedy})) return e;
+  if (int e = act_wait(h, h->q_greedy_wgs)) return e;
+  memcpy(out, io_bins, (size_t)n * D * 4);
+  return GRL_OK;
+}
+
 int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps, float* out) {
   if (!h || !out || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
-  if (flags & ~(GRL_ACT_DETERMINISTIC | GRL_ACT_RAW_OBS | GRL_ACT_OBSERVED)) return fail(GRL_ERR_INVALID, "unknown flag bits");
+  if (flags & ~(GRL_ACT_DETERMINISTIC | GRL_ACT_RAW_OBS | GRL_ACT_OBSERVED | GRL_ACT_GREEDY)) return fail(GRL_ERR_INVALID, "unknown flag bits");
   const int deterministic = flags & GRL_ACT_DETERMINISTIC;
   const bool raw = (flags & GRL_ACT_RAW_OBS) != 0;        // raw observations: VecNormalize applied on the device (grl_norm_update statistics)
   const bool observed = (flags & GRL_ACT_OBSERVED) != 0;  // act on what grl_observe uploaded: no second upload
@@ -699,6 +742,10 @@ int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps, 
   if (raw && !h->n_mean) return fail(GRL_ERR_STATE, "this handle has no normalising act path");
   if (observed && h->ob_n != n) return fail(GRL_ERR_STATE, "n differs from the number of observations grl_observe holds");
   if (n > h->NA) return fail(GRL_ERR_INVALID, "n exceeds act_batch");
+  if (flags & GRL_ACT_GREEDY) {
+    if (!q) return fail(GRL_ERR_STATE, "GRL_ACT_GREEDY is defined for DQN / BDQ handles");
+    return act_greedy(h, obs, n, eps, out);
+  }
   if (!q && !deterministic && !eps) return fail(GRL_ERR_INVALID, "stochastic action needs eps");
   const int64_t oe = (!q && h->cnn) ? (int64_t)h->hw * h->hw * h->cfg.obs_channels : h->cfg.obs_dim;
   const size_t n_in = observed ? 0 : (size_t)n * oe, n_eps = (!q && !deterministic) ? (size_t)n * h->A : 0;
@@ -718,26 +765,9 @@ int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps, 
   }
   const bool poll = h->act_done_wgs && !h->prof;
   if (q && !poll) HIPCHK(hipMemcpyAsync(h->pin_out, h->q_aout, n_out * 4, hipMemcpyDeviceToHost, h->stream));
-  bool seen = false;
   // the last launch counts its workgroups into coherent host memory once their actions are out (act_mfma.h) -- on EVERY call,
   // polled or not (a call under grl_profile_enable synchronises the stream instead): the expectation advances with it
-  if (h->act_done_wgs) h->act_done_seen += h->act_done_wgs;
-  if (poll) {
-    // poll the counter instead of the stream's completion signal; bounded -- after 2 ms (or on any doubt) the stream is
-    // synchronised as before.  Wrap-safe and tolerant of a counter that is ahead: (int)(cur - want) >= 0
-    const unsigned want = h->act_done_seen;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spin = 0;; ++spin) {
-      if ((int)(__atomic_load_n(h->act_done_host, __ATOMIC_ACQUIRE) - want) >= 0) { seen = true; break; }
-      if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-    }
-  }
-  if (!seen) {
-    HIPCHK(hipStreamSynchronize(h->stream));
-    // the stream is idle: whatever the counter says now is what the next call starts from
-    if (h->act_done_wgs) h->act_done_seen = __atomic_load_n(h->act_done_host, __ATOMIC_ACQUIRE);
-  }
-  HIPCHK(hipGetLastError());
+  if (int e = act_wait(h, h->act_done_wgs)) return e;
   memcpy(out, q ? (poll ? h->q_act_host : h->pin_out) : h->a_out, n_out * 4);
   return GRL_OK;
 }

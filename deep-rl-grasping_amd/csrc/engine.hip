@@ -262,6 +262,12 @@ struct grl_ctx {
   float *ax, *aa1, *aa2, *aa3, *afeat, *a_eps, *a_out;
   float* act_io_host = nullptr;   // SAC: a_eps | a_out live in page-locked host memory (plan_sac.inl)
   float* q_act_host = nullptr;         // DQN / BDQ: the Q-values of the act path in coherent host memory (plan_q.inl)
+  // DQN / BDQ, grl_act(GRL_ACT_GREEDY): observations [NA, obs_dim] | overrides [NA, D] | bins [NA, D] in coherent host memory
+  // (q_act.h); increments the greedy sequence leaves in the completion counter; whether the observations are read from there
+  float* q_io_host = nullptr;
+  unsigned q_greedy_wgs = 0;
+  bool q_act_fused = false;
+  std::vector<Op> ops_act_greedy;
   unsigned* act_done_host = nullptr;   // SAC: completion counter of the act path's last launch (coherent host memory), polled by grl_act
   unsigned act_done_wgs = 0, act_done_seen = 0;    // increments per call (0: no counter, synchronise the stream); expected value
   HeadAct ahPI;
@@ -366,6 +372,7 @@ struct grl_ctx {
     if (act_io_host) hipHostFree(act_io_host);
     if (act_done_host) hipHostFree(act_done_host);
     if (q_act_host) hipHostFree(q_act_host);
+    if (q_io_host) hipHostFree(q_io_host);
     for (int k = 0; k < 2; ++k) {
       if (pin_ob[k]) hipHostFree(pin_ob[k]);
       if (pin_ob_ev[k]) hipEventDestroy(pin_ob_ev[k]);

@@ -1,6 +1,6 @@
 // heads.hip -- the row-local chains: every MLP head of the SAC update forward + backward on the 16x16x4 matrix cores
 // (heads_mfma.h), the two-launch VALU chains other widths fall back to (heads_kernels.h), and the DQN / BDQ towers
-// (q_kernels.h).  Launchers declared in launch.h.
+// (q_kernels.h) with their one-launch epsilon-greedy act (q_act.h).  Launchers declared in launch.h.
 #ifdef GRL_HOSTEMU
 #include "hostemu.h"
 #else
@@ -92,6 +92,13 @@ void launch_q_bwd(const QFusedArgs& a, hipStream_t s) {
 #endif
   hipLaunchKernelGGL(q_bwd_towers_kernel, towers, dim3(256), 0, s, a);
   if (a.bwd_tr) hipLaunchKernelGGL(q_bwd_trunk_kernel, trunk, dim3(256), 0, s, a);
+}
+unsigned q_act_workgroups(const QActArgs& a) { return (unsigned)((a.rows + HT_RB - 1) / HT_RB) * (unsigned)a.D; }
+void launch_q_act(const QActArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(q_act_kernel, dim3((a.rows + HT_RB - 1) / HT_RB, a.D), dim3(256), 0, s, a);
+}
+void launch_q_select(const float* q, int rows, int D, int n, const float* explore, float* bins, unsigned* done, hipStream_t s) {
+  hipLaunchKernelGGL(q_select_kernel, dim3((rows * D + 255) / 256), dim3(256), 0, s, q, rows, D, n, explore, bins, done);
 }
 void launch_q_bwd_chain(const QChainArgs& a, hipStream_t s) {
   const dim3 towers((a.f.B + HT_RB - 1) / HT_RB, a.f.D + 1), trunk((a.f.B + HT_RB - 1) / HT_RB, qc_trunk_rows(a));

@@ -4,7 +4,8 @@
 //   gemm_fwd.hip    igemm2_kernel with P along the reduction, Q along the output columns (forward products), igemm_sk_kernel
 //   gemm_bwd.hip    igemm2_kernel with both operands along the reduction (backward-data), igemm2_pair_kernel
 //   gemm_wgrad.hip  igemm2_kernel with P along the output rows (weight gradients), the scalar-gather igemm_kernel
-//   heads.hip       heads_fused_kernel (MFMA), the VALU head chains, the DQN / BDQ tower chains (q_mfma.h on the matrix cores, q_kernels.h VALU)
+//   heads.hip       heads_fused_kernel (MFMA), the VALU head chains, the DQN / BDQ tower chains (q_mfma.h on the matrix cores, q_kernels.h VALU),
+//                   the one-launch epsilon-greedy act of the Q networks (q_act.h)
 // so that the four compile side by side (the single translation unit of round 3 took 62 s).
 #pragma once
 #include "igemm.h"
@@ -15,6 +16,7 @@
 #include "q_mfma.h"
 #include "q_chain.h"
 #include "act_mfma.h"
+#include "q_act.h"
 #include "conv_stack.h"
 
 namespace grl {
@@ -51,5 +53,9 @@ void launch_act_heads_mfma(const ActHeadsArgs& a, hipStream_t s);     // one wor
 void launch_q_fwd(const QFusedArgs& a, hipStream_t s);
 void launch_q_bwd(const QFusedArgs& a, hipStream_t s);     // towers, then the trunk (when there is one)
 void launch_q_bwd_chain(const QChainArgs& a, hipStream_t s);     // the same with loss + weight gradients inside (q_chain.h)
+void launch_q_act(const QActArgs& a, hipStream_t s);     // grl_act(GRL_ACT_GREEDY): forward + dueling + arg-max + override, grid (rows / 16, D) (q_act.h)
+unsigned q_act_workgroups(const QActArgs& a);            // ... and the increments it leaves in the completion counter
+// the same result behind the launch list of the Q-value path: arg-max + override over q [rows, D, n]; ceil(rows * D / 256) workgroups
+void launch_q_select(const float* q, int rows, int D, int n, const float* explore, float* bins, unsigned* done, hipStream_t s);
 
 }  // namespace grl

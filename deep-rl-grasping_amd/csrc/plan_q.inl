@@ -792,6 +792,49 @@ int grl_ctx::plan_q() {
       hipLaunchKernelGGL(dueling_kernel, dim3((rows * Dq + 255) / 256), dim3(256), 0, s, adv, vv, rows, Dq, nq, qo, qh, dn);
     };
     ops_act.push_back(op2);
+    // ---- GRL_ACT_GREEDY: the chosen bins instead of the Q-values.  One launch (q_act.h) for the shapes its 64-wide stages
+    // cover; every other shape keeps the launch list above and gets the select kernel behind it (GRL_TUNE q_act=0: always)
+    if (!dry) {
+      const size_t io_floats = (size_t)NA * c.obs_dim + 2 * (size_t)NA * D;
+      if (hipHostMalloc((void**)&q_io_host, io_floats * 4, hipHostMallocCoherent) != hipSuccess) {
+        q_io_host = nullptr;
+        return fail(GRL_ERR_HIP, "no page-locked memory for the act path of the Q handle");
+      }
+      memset(q_io_host, 0, io_floats * 4);
+      float* io_obs = q_io_host; float* io_explore = io_obs + (size_t)NA * c.obs_dim; float* io_bins = io_explore + (size_t)NA * D;
+      for (int i = 0; i < NA * D; ++i) io_explore[i] = -1.f;
+      q_act_fused = tune_int("q_act", 1) != 0 &&
+                    qa_shape_ok(c.obs_dim, D, nb, Lc, c.q_common, Lb, c.q_branch, Lv, c.q_value);
+      if (getenv("GRL_PLAN_DUMP"))
+        fprintf(stderr, "grl plan: q_act         epsilon-greedy act: %s\n",
+                q_act_fused ? "one launch (q_act.h)" : "launch list of the Q-value path + select kernel");
+      if (q_act_fused) {
+        QActArgs qa;
+        memset(&qa, 0, sizeof(qa));
+        qa.obs = io_obs; qa.ld_obs = c.obs_dim; qa.obs_dim = c.obs_dim; qa.rows = NA;
+        qa.Lc = Lc; qa.D = D; qa.nb = nb;
+        for (int k = 0; k < Lc; ++k) qa.trunk[k] = QActLayer{P + Pon.cw[k], P + Pon.cb[k], c.q_common[k]};
+        for (int tw = 0; tw <= D; ++tw) {
+          QActTower& T = qa.tw[tw];
+          const std::vector<int64_t>& W = tw < D ? Pon.bw[tw] : Pon.vw;
+          const std::vector<int64_t>& Bv = tw < D ? Pon.bb[tw] : Pon.vb;
+          T.L = tw < D ? Lb : Lv;
+          for (int l = 0; l < T.L; ++l) T.lay[l] = QActLayer{P + W[l], P + Bv[l], tw < D ? c.q_branch[l] : c.q_value[l]};
+          T.ow = P + W[T.L]; T.ob = P + Bv[T.L];
+        }
+        qa.explore = io_explore; qa.bins = io_bins; qa.done = dn;
+        q_greedy_wgs = dn ? q_act_workgroups(qa) : 0u;
+        Op og; og.tag = "q_act";
+        og.run = [qa](hipStream_t s) { launch_q_act(qa, s); };
+        ops_act_greedy.push_back(og);
+      } else {
+        ops_act_greedy = ops_act;       // (dueling_kernel counts its workgroups too: both counts are expected)
+        q_greedy_wgs = dn ? act_done_wgs + (unsigned)((rows * Dq + 255) / 256) : 0u;
+        Op og; og.tag = "q_select";
+        og.run = [qo, rows, Dq, nq, io_explore, io_bins, dn](hipStream_t s) { launch_q_select(qo, rows, Dq, nq, io_explore, io_bins, dn, s); };
+        ops_act_greedy.push_back(og);
+      }
+    }
   }
   for (int k = 0; k < 8; ++k) enc_w[k] = nullptr;
   dbg["feat_pi"] = {feat[0], (int64_t)B * ldf};

@@ -4,6 +4,7 @@ import os
 
 GRL_MAX_LAYERS = 4
 EXTRACTOR_MLP, EXTRACTOR_AUGMENTED, EXTRACTOR_NATURE = 0, 1, 2
+ACT_DETERMINISTIC, ACT_RAW_OBS, ACT_OBSERVED, ACT_GREEDY = 1, 2, 4, 8      # grl_act flags (include/grl.h: GRL_ACT_*)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, "libgrl.so")

@@ -430,6 +430,21 @@ class QEngine(SacEngine):
     def act(self, obs, deterministic=True, eps=None):
         return self.q_values(obs).argmax(axis=2)
 
+    def act_bins(self, obs, explore=None):
+        """Epsilon-greedy bins [n, branches] (int64) of n <= act_batch observations: the arg-max of the dueling Q-values per
+        branch, formed on the device (grl_act with GRL_ACT_GREEDY; one launch, csrc/q_act.h).  explore [n, branches]: an
+        entry >= 0 replaces the greedy bin of that (row, branch), a negative one keeps it; None = all greedy.  The caller
+        draws the randomness."""
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        n = obs.shape[0]
+        out = np.empty((n, self.D), np.float32)
+        pe = None
+        if explore is not None:
+            explore = np.ascontiguousarray(explore, dtype=np.float32).reshape(n, self.D)
+            pe = explore.ctypes.data
+        check(self.lib, self.lib.grl_act(self.h, obs.ctypes.data, n, _capi.ACT_GREEDY, pe, out.ctypes.data))
+        return out.astype(np.int64)
+
     def update_target(self):
         check(self.lib, self.lib.grl_q_update_target(self.h))
 

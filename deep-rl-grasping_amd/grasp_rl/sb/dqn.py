@@ -12,6 +12,12 @@ proportional prioritised sampler (sum-tree on the host, as stable-baselines does
 is SURVEY.md 8f row 4).  DQN follows stock stable-baselines 2.10.1; BDQ follows the decisions
 documented in SURVEY.md A.6 / oracle/dqn.py (the fork's source is unavailable: parity unpinned).
 
+N environments: a VecEnv of N environments -- or GRL_NUM_ENVS around the script's one-factory DummyVecEnv, as for SAC -- is
+stepped as one vectorised step: exploration drawn row by row in env order, the greedy rows' bins chosen on the device in one
+launch (``QEngine.act_bins``, csrc/q_act.h), one ``replay_add`` of N rows, the counter advanced by N and as many updates /
+target copies as multiples of ``train_freq`` / ``target_network_update_freq`` it crossed.  One environment: the loop of
+stable-baselines, same random stream.
+
 Data parallelism (BASELINE north_star: "SAC / BDQ / DQN update ... optionally sharded"):
 ``data_parallel="auto"`` (or GRL_DATA_PARALLEL=auto) under a torchrun launch trains one replica per rank, as ``sb.SAC``
 does -- every rank steps its OWN environment and fills its own replay ring, the global minibatch is split evenly over
@@ -33,7 +39,7 @@ from . import policies as pol
 from . import save_util
 from . import spaces as sp
 from .callbacks import as_callback
-from .vec_env import DummyVecEnv, VecEnv, unwrap_vec_normalize
+from .vec_env import DummyVecEnv, VecEnv, expand_training_env, unwrap_vec_normalize
 
 
 class LinearSchedule:
@@ -92,13 +98,16 @@ class _QModel:
         if env is not None and not isinstance(env, VecEnv) and not hasattr(env, "num_envs"):
             env = DummyVecEnv([lambda: env])
         if env is not None:
-            if env.num_envs != 1:
-                raise ValueError("%s trains on a single environment (as stable-baselines does)" % type(self).__name__)
-            import os
-            if os.environ.get("GRL_NUM_ENVS", "1").strip() not in ("", "1"):
-                logger.warn("GRL_NUM_ENVS is ignored by %s: it trains on the single environment it is given, like "
-                            "stable-baselines' (the fan-out is SAC's)" % type(self).__name__)
+            # GRL_NUM_ENVS: the single-factory DummyVecEnv of the reference's script (train_stable_baselines.py:52-54) fans out
+            # to worker processes, as for SAC -- this process's share of the job's environments under data parallelism
+            rt = self._dp_runtime()
+            env = expand_training_env(env, rank=0 if rt is None else rt.rank, world=1 if rt is None else rt.world)
+            if self.observation_space is not None and tuple(env.observation_space.shape) != tuple(self.observation_space.shape):
+                raise ValueError("observation space of the new env does not match the model")
+            if self.engine is not None and env.num_envs > self.engine.cfg.act_batch:
+                raise ValueError("env has more sub-environments than the model was built for")
             self.observation_space, self.action_space = env.observation_space, env.action_space
+            self.n_envs = env.num_envs
             self._vec_normalize_env = unwrap_vec_normalize(env)
         self.env = env
 
@@ -144,7 +153,7 @@ class _QModel:
             engine_seed += 7919 * rt.rank             # every replica draws its own replay indices
             self.device = rt.device
         cfg = _capi.make_q_config(self.algo, obs_shape[0], D, bins, common, branch, value, batch_size=self._local_batch,
-                                  act_batch=1, replay_capacity=self.buffer_size, normalize=0 if vn is None else _capi.norm_mode(vn), gamma=self.gamma,
+                                  act_batch=max(1, self.n_envs), replay_capacity=self.buffer_size, normalize=0 if vn is None else _capi.norm_mode(vn), gamma=self.gamma,
                                   lr=lr, double_q=self.double_q, seed=engine_seed,
                                   prioritized=bool(self.prioritized_replay), per_alpha=self.prioritized_replay_alpha,
                                   per_eps=self.prioritized_replay_eps, **kw)
@@ -184,8 +193,21 @@ class _QModel:
         return ("deepq" if self.algo == "dqn" else "bdq") + "/eps:0"
 
     # ------------------------------------------------------------------ acting
-    def _greedy_bins(self, obs):
-        return self.engine.q_values(np.asarray(obs, np.float32).reshape(1, -1)).argmax(axis=2)[0]     # [D]
+    def _act_bins(self, obs, eps, always_draw=False):
+        """Epsilon-greedy bins [n, D] of n observations.  The randomness is drawn here, row by row in env order -- one uniform
+        per row (always_draw: also when eps is 0, as the learn loop does) and, only for a row that explores, its D bins: the
+        stream the single-env loop consumes -- and the greedy rows are chosen on the device, one call per act_batch rows
+        (engine.act_bins; skipped when every row explores)."""
+        obs = np.asarray(obs, np.float32).reshape(-1, self.observation_space.shape[0])
+        explore = np.full((obs.shape[0], self.D), -1, np.int64)
+        if always_draw or eps > 0:
+            for i in range(obs.shape[0]):
+                if self._rng.random() < eps:
+                    explore[i] = self._rng.integers(0, self.bins, self.D)
+        if np.all(explore >= 0):
+            return explore
+        cap = self.engine.cfg.act_batch
+        return np.concatenate([self.engine.act_bins(obs[k:k + cap], explore[k:k + cap]) for k in range(0, obs.shape[0], cap)])
 
     def _bins_to_env_action(self, bins):
         raise NotImplementedError
@@ -195,13 +217,7 @@ class _QModel:
         single = observation.shape == tuple(self.observation_space.shape)
         obs = observation.reshape((-1,) + tuple(self.observation_space.shape))
         eps = 0.0 if deterministic else float(self.engine.get_parameters()[self._eps_name()])
-        acts = []
-        for o in obs:
-            b = self._greedy_bins(o)
-            if eps > 0 and self._rng.random() < eps:
-                b = self._rng.integers(0, self.bins, self.D)
-            acts.append(self._bins_to_env_action(b))
-        acts = np.asarray(acts)
+        acts = np.asarray([self._bins_to_env_action(b) for b in self._act_bins(obs, eps)])
         return (acts[0] if single else acts), None
 
     # ------------------------------------------------------------------ learn
@@ -226,6 +242,7 @@ class _QModel:
         beta_iters = self.prioritized_replay_beta_iters or total_timesteps
         beta_schedule = LinearSchedule(beta_iters, 1.0, self.prioritized_replay_beta0)
         episode_rewards, episode_successes = [0.0], []
+        self.episode_reward = np.zeros((self.n_envs,))
         writer = logger.SummaryWriter(self.tensorboard_log, tb_log_name or type(self).__name__) \
             if getattr(self, "tensorboard_log", None) else None
         obs = self.env.reset()
@@ -258,16 +275,14 @@ class _QModel:
         # stable-baselines: `for _ in range(total_timesteps)` -- a continued run (reset_num_timesteps=False) takes total_timesteps
         # MORE steps from where the counter stands; the schedules keep reading the counter itself
         end = self.num_timesteps + total_timesteps
+        N = self.n_envs
         while self.num_timesteps < end:
             eps = self.exploration.value(self.num_timesteps)
-            if self._rng.random() < eps:
-                bins = self._rng.integers(0, self.bins, self.D)
-            else:
-                bins = self._greedy_bins(obs[0])
-            env_action = self._bins_to_env_action(bins)
-            new_obs, rew, done, info = self.env.step(np.asarray([env_action]))
+            bins = self._act_bins(obs, eps, always_draw=True)         # [N, D]: one device call for all rows
+            env_action = np.asarray([self._bins_to_env_action(b) for b in bins])
+            new_obs, rew, done, info = self.env.step(env_action)
             before = self.num_timesteps
-            self.num_timesteps += W                 # environment steps of the job
+            self.num_timesteps += N * W             # environment steps of the job
             callback.update_locals(locals())
             stop = callback.on_step() is False
             if rt is not None:
@@ -275,13 +290,17 @@ class _QModel:
             if stop:
                 break
             new_obs_, rew_ = (vn.get_original_obs(), vn.get_original_reward()) if vn is not None else (new_obs, rew)
-            eng.replay_add(np.asarray(obs_, np.float32), bins.astype(np.float32).reshape(1, -1),
+            # N rows in env order.  A finished row carries done = 1, which masks the bootstrap term: the auto-reset observation
+            # it holds as its next observation is never used
+            eng.replay_add(np.asarray(obs_, np.float32), bins.astype(np.float32).reshape(N, -1),
                            np.asarray(rew_, np.float32), np.asarray(new_obs_, np.float32), np.asarray(done, np.float32))
             obs, obs_ = new_obs, new_obs_
+            self.episode_reward += np.asarray(rew_, np.float64).reshape(N)
+            for i in range(N):
+                if done[i] and isinstance(info[i], dict) and info[i].get("is_success") is not None:
+                    episode_successes.append(float(info[i]["is_success"]))
             episode_rewards[-1] += float(np.asarray(rew_).reshape(-1)[0])
             if done[0]:
-                if isinstance(info[0], dict) and info[0].get("is_success") is not None:
-                    episode_successes.append(float(info[0]["is_success"]))
                 episode_rewards.append(0.0)
             can_sample = eng.replay_size() >= self._local_batch
             # one update per train_freq environment steps of the job: W of them happened in this iteration
@@ -338,7 +357,7 @@ class _QModel:
         d = {k: getattr(self, k) for k in self._SAVED}
         d["learning_rate"] = float(self.learning_rate(1.0)) if callable(self.learning_rate) else float(self.learning_rate)
         d.update(observation_space=self.observation_space, action_space=self.action_space, policy=self.policy,
-                 n_envs=1, _vectorize_action=True)
+                 n_envs=self.n_envs, _vectorize_action=True)
         return d
 
     def save(self, save_path, cloudpickle=False):

@@ -294,7 +294,7 @@ def evaluate_success(model, kind="depth", action="box", episodes=200, seed=10_00
 
 
 def learn_reach(algo="sac", kind="depth", total_timesteps=30_000, n_envs=16, device="cuda:0", seed=0, engine_factory=None,
-                eval_episodes=200, **model_kwargs):
+                eval_episodes=200, q_envs=1, **model_kwargs):
     """Train `algo` ('sac' | 'dqn' | 'bdq') on ReachGraspEnv through the stable-baselines surface the reference drives
     (sb_helper.py:104-128 / 159-165 / 210-224: VecNormalize(norm_obs, norm_reward, clip_obs 10) + model.learn), then run the
     reference's evaluation.  Returns dict(train_success = mean is_success of the last 200 TRAINING episodes (the
@@ -318,7 +318,7 @@ def learn_reach(algo="sac", kind="depth", total_timesteps=30_000, n_envs=16, dev
             return True
 
     action = "discrete" if algo == "dqn" else "box"
-    N = n_envs if algo == "sac" else 1
+    N = n_envs if algo == "sac" else q_envs       # (DQN / BDQ: one environment unless q_envs asks for more)
     venv = DummyVecEnv([(lambda s=s: ReachGraspEnv(kind, seed=seed * 1000 + s, action=action)) for s in range(N)])
     env = VecNormalize(venv, norm_obs=True, norm_reward=True, clip_obs=10.0)
     if algo == "sac":

@@ -283,10 +283,21 @@ int grl_get_metrics(grl_handle h, grl_metrics* out);
      GRL_ACT_OBSERVED       (SAC handles) act on the n observations the last grl_observe uploaded; `obs` is ignored
                             (may be NULL) and nothing but eps and the actions crosses the bus.
    eps_or_null: [n,act_dim] noise for stochastic actions (host).  Synchronises the stream.
-   DQN / BDQ handles: out receives the dueling Q-values [n, q_branches*q_bins]. */
+   DQN / BDQ handles: out receives the dueling Q-values [n, q_branches*q_bins] (normalised observations only:
+   GRL_ACT_RAW_OBS / GRL_ACT_OBSERVED are GRL_ERR_STATE on them), or with
+     GRL_ACT_GREEDY         (DQN / BDQ handles; GRL_ERR_STATE on the others) the epsilon-greedy ACTION of every row: out
+                            receives the bins [n, q_branches] as float32 -- the arg-max of the Q-values over the bins of each
+                            branch (lowest index among equal values, as np.argmax), formed on the device -- and eps_or_null
+                            is the exploration table explore[n, q_branches] (host) or NULL (all greedy): an entry >= 0
+                            replaces the greedy bin of that (row, branch) and comes back verbatim, a negative entry keeps
+                            it.  The caller draws the randomness.  One launch for networks whose widths and bins fit 64,
+                            observations up to 128 values and up to 7 branches (csrc/q_act.h); other shapes run the launches
+                            of the Q-value path plus a select launch.  Stands behind stable-baselines DQN.learn's
+                            `self.act(...)` as entered from sb_helper.py:159-177 and `model.predict` in utils.py:71. */
 #define GRL_ACT_DETERMINISTIC 1
 #define GRL_ACT_RAW_OBS 2
 #define GRL_ACT_OBSERVED 4
+#define GRL_ACT_GREEDY 8
 int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps_or_null,
             float* out_actions);
 
