@@ -11,12 +11,11 @@ import q_parity_util as qu
 from grasp_rl import _capi, synthetic
 from grasp_rl.engine import QEngine
 from oracle import dqn as od
+from q_parity_util import TIE_CAP, TIE_REL, compared_pairs      # noqa: F401  (shared with tests/test_gpu_q_shapes.py)
 
 gpu = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-TIE_REL = 1e-4          # the project's forward tolerance (tests/q_parity_util.py): closer top-two Q-values are not compared
-TIE_CAP = 0.05          # ... for at most this share of the (row, branch) pairs of a case
 
 
 def shipped_case(name, n):
@@ -43,17 +42,16 @@ def shipped_case(name, n):
     return spec, params, cfg, obs
 
 
-def compared_pairs(q):
-    """[n, D] mask of the (row, branch) pairs whose two largest oracle Q-values differ by more than the forward tolerance."""
-    top = np.sort(q, axis=2)[:, :, -2:]
-    return (top[:, :, 1] - top[:, :, 0]) > TIE_REL * np.maximum(np.abs(top[:, :, 1]), np.abs(top[:, :, 0]))
-
-
 def test_tie_cap_holds_for_the_oracle_alone():
     """CPU part of the cases below: with these seeds the oracle itself leaves at most 5 % of the pairs of every case out."""
     for name in ("dqn_reference_shape", "bdq_baseline_config3", "golden"):
         for n in (1, 16, 64):
             spec, params, _, obs = shipped_case(name, n)
+            keep = compared_pairs(od.QOracle(spec, params).q_values(obs))
+            assert keep.any() and (~keep).mean() <= TIE_CAP, (name, n, (~keep).mean())
+    for name in qu.SHAPE_CASES:          # ... and of the boundary shapes (tests/test_gpu_q_shapes.py)
+        for n in qu.ACT_NS:
+            spec, params, _, obs = qu.act_case(name, n)
             keep = compared_pairs(od.QOracle(spec, params).q_values(obs))
             assert keep.any() and (~keep).mean() <= TIE_CAP, (name, n, (~keep).mean())
 

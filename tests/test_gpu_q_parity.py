@@ -20,8 +20,10 @@ def test_q_update_per_layer_gemm_fallback(name, monkeypatch):
 
 @pytest.mark.parametrize("name", ["dqn_reference_shape", "bdq_reference_shape", "bdq_baseline_config3"])
 def test_q_update_valu_chains(name, monkeypatch, capfd):
-    """GRL_TUNE q_mfma=0: the VALU stage chains of q_kernels.h (what networks wider than 64 units run on) stay correct next
-    to the matrix-core stages of q_mfma.h -- and the default plan does take the matrix-core kernels for these shapes."""
+    """GRL_TUNE q_mfma=0: the VALU stage chains of q_kernels.h stay correct next to the matrix-core stages of q_mfma.h at
+    widths up to 64 -- and the default plan does take the matrix-core kernels for these shapes.  (Networks wider than 64 units,
+    which run on the VALU chains by shape: tests/test_gpu_q_shapes.py::test_update_matches_oracle_at_shape_boundaries, cases
+    valu_w65, valu_w128, qapply_edge and qapply_over.)"""
     monkeypatch.setenv("GRL_PLAN_DUMP", "1")
     qu.run_and_compare(qu.make_q_case(**qu.CASES[name]))
     assert "matrix-core stages" in capfd.readouterr().err
