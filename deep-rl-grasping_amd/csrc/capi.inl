@@ -530,60 +530,18 @@ int grl_train_step(grl_handle h, int n_steps, const int64_t* idx, const float* e
   if ((idx == nullptr) != (eps == nullptr)) return fail(GRL_ERR_INVALID, "idx and eps must both be given or both be NULL");
   if (h->rp_size < 1) return fail(GRL_ERR_STATE, "replay buffer is empty");
   h->grad_scale = 1.f;
-  if (!idx && n_steps >= 2 && h->ride_ok && !h->prof) {     // device RNG, several updates, double-buffered images (plan_sac "gather_ride")
-    if (int e = h->run_ride("ride", &h->ops_ride_first, h->ops_ride_mid, h->ops_ride_last, n_steps)) return e;
-    HIPCHK(hipGetLastError());
-    return GRL_OK;
-  }
-  if (!idx && n_steps >= 2 && h->prefetch_ok && !h->prof) {   // device RNG, several updates: prefetching sequences (plan_sac)
-    // short calls (what SAC.learn issues: n = number of environments) are ONE graph, cached per n
-    if (n_steps <= 32 && tune_int("graph_updates", 16) != 1) {
-      std::vector<std::vector<Op>*> seq;
-      seq.push_back(&h->ops_pf_first);
-      for (int s = 0; s < n_steps - 2; ++s) seq.push_back(&h->ops_pf_mid);
-      seq.push_back(&h->ops_pf_last);
-      if (int e = h->run_seq("pf_call_" + std::to_string(n_steps), seq)) return e;
-      HIPCHK(hipGetLastError());
-      return GRL_OK;
-    }
-    // first | middle updates, grouped several to a graph (run_repeated) | last
-    if (int e = h->run_seq("pf_first", {&h->ops_pf_first})) return e;
-    if (n_steps > 2)
-      if (int e = h->run_repeated("pf_mid", {&h->ops_pf_mid}, n_steps - 2)) return e;
-    if (int e = h->run_seq("pf_last", {&h->ops_pf_last})) return e;
-    HIPCHK(hipGetLastError());
-    return GRL_OK;
-  }
-  if (!idx && n_steps >= 2 && h->q_pf_ok && !h->prof) {      // DQN / BDQ, uniform replay: prefetching sequences (plan_q "q_pf")
-    if (n_steps <= 32 && tune_int("graph_updates", 16) != 1) {
-      std::vector<std::vector<Op>*> seq;
-      seq.push_back(&h->ops_q_pf_first);
-      for (int s = 0; s < n_steps - 2; ++s) seq.push_back(&h->ops_q_pf_mid);
-      seq.push_back(&h->ops_q_pf_last);
-      if (int e = h->run_seq("q_pf_call_" + std::to_string(n_steps), seq)) return e;
-      HIPCHK(hipGetLastError());
-      return GRL_OK;
-    }
-    if (int e = h->run_seq("q_pf_first", {&h->ops_q_pf_first})) return e;
-    if (n_steps > 2)
-      if (int e = h->run_repeated("q_pf_mid", {&h->ops_q_pf_mid}, n_steps - 2)) return e;
-    if (int e = h->run_seq("q_pf_last", {&h->ops_q_pf_last})) return e;
-    HIPCHK(hipGetLastError());
-    return GRL_OK;
-  }
-  if (!idx) {      // device RNG: identical updates, several to a graph
-    if (!h->ops_grads_apply.empty()) {
-      if (int e = h->run_repeated("full_rng", {&h->ops_rng, &h->ops_grads_apply}, n_steps)) return e;
-    } else if (int e = h->run_repeated("full_rng", {&h->ops_rng, &h->ops_grads, &h->ops_apply}, n_steps)) return e;
-    HIPCHK(hipGetLastError());
-    return GRL_OK;
-  }
-  for (int s = 0; s < n_steps; ++s) {
-    if (int e = stage_noise(h, idx, eps, s)) return e;
-    if (!h->ops_grads_apply.empty()) {
-      if (int e = h->run_seq("full_explicit", {&h->ops_gather, &h->ops_grads_apply})) return e;
-    } else if (int e = h->run_seq("full_explicit", {&h->ops_gather, &h->ops_grads, &h->ops_apply})) return e;
-  }
+  // device RNG, several updates: work of update t + 1 rides on a launch of update t where the plan has such sequences (plan_sac
+  // "gather_ride" with double-buffered images, else "prefetch"; plan_q "q_pf" for uniform replay)
+  const bool call = !idx && n_steps >= 2 && !h->prof;
+  int e = GRL_OK;
+  if (call && h->ride.ok()) e = h->run_call("ride", h->ride, n_steps);
+  else if (call && h->pf.ok()) e = h->run_call("pf", h->pf, n_steps);
+  else if (call && h->q_pf.ok()) e = h->run_call("q_pf", h->q_pf, n_steps);
+  else if (!idx) e = h->run_repeated("full_rng", h->update_seq(&h->ops_rng), n_steps);      // identical updates, several to a graph
+  else
+    for (int s = 0; s < n_steps && !e; ++s)
+      if (!(e = stage_noise(h, idx, eps, s))) e = h->run_seq("full_explicit", h->update_seq(&h->ops_gather));
+  if (e) return e;
   HIPCHK(hipGetLastError());
   return GRL_OK;
 }
@@ -614,40 +572,21 @@ int grl_train_step_per(grl_handle h, int n_steps, double beta, const double* u) 
     return GRL_OK;
   }
   if (!u) {        // device Philox: identical updates, several to a graph
-    if (n_steps >= 2 && h->per_pf_ok && !h->prof) {
+    if (n_steps >= 2 && h->per_pf.ok() && !h->prof) {
       // four launches per update (plan_q "per_pf"): the sampler of update t + 1 rides on the launch that ends update t
-      if (int e = h->run_seq("per_pf_first", {&h->ops_per_pf_first})) return e;
-      if (n_steps > 2)
-        if (int e = h->run_repeated("per_pf_mid", {&h->ops_per_pf_mid}, n_steps - 2)) return e;
-      if (int e = h->run_seq("per_pf_last", {&h->ops_per_pf_last})) return e;
+      if (int e = h->run_call("per_pf", h->per_pf, n_steps)) return e;
     } else if (n_steps >= 2 && !h->ops_grads_apply_per_r.empty() && !h->prof) {
       // nothing but the updates themselves touches the leaves inside one call: the first update sums every block of the
       // ring, each apply launch refreshes the blocks its write-back touched, the later samplers start from those
       if (int e = h->run_seq("per_rng_first", {&h->ops_per_rng_g, &h->ops_grads_apply_per_r})) return e;
       if (int e = h->run_repeated("per_rng_inc", {&h->ops_per_rng_g_inc, &h->ops_grads_apply_per_r}, n_steps - 1)) return e;
-    } else if (!h->ops_grads_apply_per.empty()) {
-      if (int e = h->run_repeated("per_rng", {&h->ops_per_rng_g, &h->ops_grads_apply_per}, n_steps)) return e;
-    } else if (!h->ops_grads_apply.empty()) {
-      if (int e = h->run_repeated("per_rng", {&h->ops_per_rng, &h->ops_gather, &h->ops_grads_apply, &h->ops_per_update}, n_steps)) return e;
-    } else if (int e = h->run_repeated("per_rng", {&h->ops_per_rng, &h->ops_gather, &h->ops_grads, &h->ops_apply, &h->ops_per_update}, n_steps)) return e;
+    } else if (int e = h->run_repeated("per_rng", h->per_update_seq(true), n_steps)) return e;
     HIPCHK(hipGetLastError());
     return GRL_OK;
   }
   for (int s = 0; s < n_steps; ++s) {
-    if (u) {
-      HIPCHK(hipMemcpyAsync(h->per_u, u + (int64_t)s * h->B, (size_t)h->B * 8, hipMemcpyDeviceToDevice, h->stream));
-      if (!h->ops_grads_apply_per.empty()) {
-        if (int e = h->run_seq("per_u", {&h->ops_per_u_g, &h->ops_grads_apply_per})) return e;
-      } else if (!h->ops_grads_apply.empty()) {
-        if (int e = h->run_seq("per_u", {&h->ops_per_u, &h->ops_gather, &h->ops_grads_apply, &h->ops_per_update})) return e;
-      } else if (int e = h->run_seq("per_u", {&h->ops_per_u, &h->ops_gather, &h->ops_grads, &h->ops_apply, &h->ops_per_update})) return e;
-    } else {
-      if (!h->ops_grads_apply_per.empty()) {
-        if (int e = h->run_seq("per_rng", {&h->ops_per_rng_g, &h->ops_grads_apply_per})) return e;
-      } else if (!h->ops_grads_apply.empty()) {
-        if (int e = h->run_seq("per_rng", {&h->ops_per_rng, &h->ops_gather, &h->ops_grads_apply, &h->ops_per_update})) return e;
-      } else if (int e = h->run_seq("per_rng", {&h->ops_per_rng, &h->ops_gather, &h->ops_grads, &h->ops_apply, &h->ops_per_update})) return e;
-    }
+    HIPCHK(hipMemcpyAsync(h->per_u, u + (int64_t)s * h->B, (size_t)h->B * 8, hipMemcpyDeviceToDevice, h->stream));
+    if (int e = h->run_seq("per_u", h->per_update_seq(false))) return e;
   }
   HIPCHK(hipGetLastError());
   return GRL_OK;
@@ -885,11 +824,8 @@ static Op dp_gather_op(const DpArgs& da) {
   return op;
 }
 static AdamArgs dp_adam_args(grl_ctx* self, int world) {
-  AdamArgs aa;
-  memset(&aa, 0, sizeof(aa));
-  aa.params = self->params; aa.grads = nullptr; aa.m = self->adam_m; aa.v = self->adam_v;
-  aa.n_train = self->n_train; aa.sc = self->sc; aa.grad_scale = 1.f / (float)world; aa.tau = self->cfg.tau; aa.eps = 1e-8f;
-  aa.src_ofs = self->vf_off; aa.n_polyak = self->n_polyak; aa.target = self->params + self->tgt_off;
+  AdamArgs aa = self->adam_args(1.f / (float)world, true);
+  aa.grads = nullptr;      // (the exchange kernels read the sums from the exchange buffers)
   return aa;
 }
 static Op dp_apply_op(grl_ctx* self, const DpArgs& da, const DpArgs& db) {
@@ -907,6 +843,25 @@ static Op dp_apply_oneshot_op(grl_ctx* self, const DpArgs& da) {
   const int blocks = dp_blocks(2, da.n / 4);
   op.run = [aa, da, blocks](hipStream_t s) { hipLaunchKernelGGL(dp_apply_oneshot_kernel, dim3(blocks), dim3(256), 0, s, aa, da); };
   return op;
+}
+
+// The sequences of a multi-update call ending in the exchange: every part of `src` with its last launch (reduction + Adam)
+// replaced by the publishing reduction K1 -- carrying the riders of the next update (`lk`, `g2`, `gx`) except in the call's last
+// update -- and the rest of the exchange `tail` appended.  short_call_graph is the caller's choice, not copied from `src`
+static void close_with_exchange(grl_ctx* h, const DpArgs& d, const CallPlan& src, CallPlan& dst, const LossArgs& lk,
+                                const GatherArgs* g2, int gx, const std::vector<Op>& tail, bool short_call_graph) {
+  dst.clear();
+  dst.alternate = src.alternate;
+  dst.short_call_graph = short_call_graph;
+  for (int v = 0; v < 3; ++v)
+    for (int f = 0; f < (v > 0 && src.alternate ? 2 : 1); ++f) {
+      const std::vector<Op>& from = src.part(v, f);
+      std::vector<Op>& to = dst.part(v, f);
+      to.assign(from.begin(), from.end() - 1);
+      to.push_back(v == 2 ? dp_k1_op(h, h->red_all, d, h->loss_args, nullptr, 0, "reduce_publish")
+                          : dp_k1_op(h, h->red_all, d, lk, g2, gx, "reduce_publish"));
+      to.insert(to.end(), tail.begin() + 1, tail.end());
+    }
 }
 
 int grl_allreduce_connect(grl_handle h, const void* handles) {
@@ -963,7 +918,7 @@ int grl_allreduce_connect(grl_handle h, const void* handles) {
     for (auto& o : h->dp_body)
       if (o.tag != "gather_norm") h->dp_body_per.push_back(o);
     h->ops_dp1.clear();
-    for (auto* v : {&h->ops_pfdp_first, &h->ops_pfdp_mid, &h->ops_pfdp_last, &h->ops_pfdp1_first, &h->ops_pfdp1_mid, &h->ops_pfdp1_last}) v->clear();
+    for (int one = 0; one < 2; ++one) { h->pf_dp[one].clear(); h->ride_dp[one].clear(); }
   }
   for (int one = 0; one < 2 && !qh; ++one) {
     const DpArgs& d = one ? d1s : h->dp;
@@ -973,35 +928,13 @@ int grl_allreduce_connect(grl_handle h, const void* handles) {
     tail.push_back(dp_wait_op(d, 0));
     if (one) tail.push_back(dp_apply_oneshot_op(h, d));
     else { tail.push_back(dp_reduce_op(d)); tail.push_back(dp_wait_op(d, 1)); tail.push_back(dp_apply_op(h, d, none)); }
-    // multi-update calls on the device RNG: the same with the gather of the next update riding on K1 (plan_sac "prefetch")
-    std::vector<Op>* pf[3] = {one ? &h->ops_pfdp1_first : &h->ops_pfdp_first, one ? &h->ops_pfdp1_mid : &h->ops_pfdp_mid,
-                              one ? &h->ops_pfdp1_last : &h->ops_pfdp_last};
-    for (auto* v : pf) v->clear();
-    if (h->prefetch_ok) {
-      const std::vector<Op>* src[3] = {&h->ops_pf_first, &h->ops_pf_mid, &h->ops_pf_last};
-      for (int v = 0; v < 3; ++v) {
-        pf[v]->assign(src[v]->begin(), src[v]->end() - 1);
-        if (v == 2) pf[v]->push_back(dp_k1_op(h, h->red_all, d, h->loss_args, nullptr, 0, "reduce_publish"));
-        else pf[v]->push_back(dp_k1_op(h, h->red_all, d, h->pf_lk, &h->pf_g2, h->pf_gx, "reduce_publish"));
-        for (size_t k = 1; k < tail.size(); ++k) pf[v]->push_back(tail[k]);
-      }
-    }
-    // ... or, with double-buffered images, the image gather riding on the head launch and the extras on K1 (plan_sac "gather_ride")
-    for (int f = 0; f < 2; ++f) { h->ops_ridedp_mid[one][f].clear(); h->ops_ridedp_last[one][f].clear(); }
-    h->ops_ridedp_first[one].clear();
-    if (h->ride_ok) {
-      auto close = [&](const std::vector<Op>& src, std::vector<Op>& dst, bool last) {
-        dst.assign(src.begin(), src.end() - 1);
-        if (last) dst.push_back(dp_k1_op(h, h->red_all, d, h->loss_args, nullptr, 0, "reduce_publish"));
-        else dst.push_back(dp_k1_op(h, h->red_all, d, h->ride_lk, &h->ride_g2, 1, "reduce_publish"));
-        for (size_t k = 1; k < tail.size(); ++k) dst.push_back(tail[k]);
-      };
-      close(h->ops_ride_first, h->ops_ridedp_first[one], false);
-      for (int f = 0; f < 2; ++f) {
-        close(h->ops_ride_mid[f], h->ops_ridedp_mid[one][f], false);
-        close(h->ops_ride_last[f], h->ops_ridedp_last[one][f], true);
-      }
-    }
+    // multi-update calls on the device RNG: the same with the gather of the next update riding on K1 (plan_sac "prefetch") or,
+    // with double-buffered images, the image gather riding on the head launch and the extras on K1 (plan_sac "gather_ride").
+    // (pf_dp keeps short_call_graph off: see plan_q "per_pf")
+    h->pf_dp[one].clear();
+    h->ride_dp[one].clear();
+    if (h->pf.ok()) close_with_exchange(h, d, h->pf, h->pf_dp[one], h->pf_lk, &h->pf_g2, h->pf_gx, tail, false);
+    if (h->ride.ok()) close_with_exchange(h, d, h->ride, h->ride_dp[one], h->ride_lk, &h->ride_g2, 1, tail, true);
   }
   // ---- the overlapped update (grl_allreduce_set_overlap): the staged plan (grl_compute_grads_staged) with both exchanges in
   // the graph.  After heads_dfeat a SIDE LANE forms the dense layers' weight gradients, reduces them (publishing) and
@@ -1063,13 +996,8 @@ int grl_allreduce_disconnect(grl_handle h) {
   h->dp_on = false;
   h->dp_overlap = false;
   h->dp_mode = 0;
-  for (auto* v : {&h->ops_dp, &h->ops_dp1, &h->ops_pfdp_first, &h->ops_pfdp_mid, &h->ops_pfdp_last, &h->ops_pfdp1_first,
-                  &h->ops_pfdp1_mid, &h->ops_pfdp1_last, &h->dp_body, &h->dp_body_per, &h->ops_dp_overlap})
-    v->clear();
-  for (int one = 0; one < 2; ++one) {
-    h->ops_ridedp_first[one].clear();
-    for (int f = 0; f < 2; ++f) { h->ops_ridedp_mid[one][f].clear(); h->ops_ridedp_last[one][f].clear(); }
-  }
+  for (auto* v : {&h->ops_dp, &h->ops_dp1, &h->dp_body, &h->dp_body_per, &h->ops_dp_overlap}) v->clear();
+  for (int one = 0; one < 2; ++one) { h->pf_dp[one].clear(); h->ride_dp[one].clear(); }
   for (int p = 0; p < 2 * DP_MAX_WORLD; ++p)
     if (h->dp_peer[p]) { (void)hipIpcCloseMemHandle(h->dp_peer[p]); h->dp_peer[p] = nullptr; }
   if (h->dp_buf) (void)hipFree(h->dp_buf);
@@ -1121,18 +1049,13 @@ int grl_train_step_allreduce(grl_handle h, int n_steps, const int64_t* idx, cons
   std::vector<Op>* body = h->dp_overlap ? &h->ops_dp_overlap : &h->dp_body;
   std::vector<Op>* tail = h->dp_overlap ? &none : (one ? &h->ops_dp1 : &h->ops_dp);
   const std::string sfx = one ? "1" : "";
-  std::vector<Op>* pf[3] = {one ? &h->ops_pfdp1_first : &h->ops_pfdp_first, one ? &h->ops_pfdp1_mid : &h->ops_pfdp_mid,
-                            one ? &h->ops_pfdp1_last : &h->ops_pfdp_last};
-  if (!idx && n_steps >= 2 && !h->dp_overlap && h->ride_ok && !h->prof && !h->ops_ridedp_first[one ? 1 : 0].empty()) {
+  const bool call = !idx && n_steps >= 2 && !h->dp_overlap && !h->prof;
+  if (call && h->ride_dp[one].ok()) {
     // plain exchange on the device RNG, double-buffered images: the image gather of update t+1 rides on update t's head launch
-    const int o = one ? 1 : 0;
-    if (int e = h->run_ride("dpr" + sfx, &h->ops_ridedp_first[o], h->ops_ridedp_mid[o], h->ops_ridedp_last[o], n_steps)) return e;
-  } else if (!idx && n_steps >= 2 && !h->dp_overlap && h->prefetch_ok && !h->prof && !pf[1]->empty() && tune_int("gather_prefetch", 1)) {
+    if (int e = h->run_call("dpr" + sfx, h->ride_dp[one], n_steps)) return e;
+  } else if (call && h->pf_dp[one].ok()) {
     // plain exchange on the device RNG: the prefetching sequences (the gather of update t+1 rides on the reduction of update t)
-    if (int e = h->run_seq("dpp_first" + sfx, {pf[0]})) return e;
-    if (n_steps > 2)
-      if (int e = h->run_repeated("dpp_mid" + sfx, {pf[1]}, n_steps - 2)) return e;
-    if (int e = h->run_seq("dpp_last" + sfx, {pf[2]})) return e;
+    if (int e = h->run_call("dpp" + sfx, h->pf_dp[one], n_steps)) return e;
   } else if (!idx) {      // device RNG: identical updates, several to a graph
     if (int e = h->run_repeated((h->dp_overlap ? "dpo_rng" : "dp_rng") + sfx, {&h->ops_rng, body, tail}, n_steps)) return e;
   } else {

@@ -60,6 +60,7 @@ static inline int64_t rup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 // `dp_timeout_ms`, `heads_stamps`) and the switches that select a tested alternative launch list (`fused_adam=0`,
 // `gather_prefetch=0`, `fused_q=0`, `fused_qapply=0`, `q_mfma=0`, `q_l0_chain=0`, `per_inc=0`).  None of them changes what is
 // computed; `q_mfma` / `fused_q` pick stage kernels with a different summation order (each checked against the oracle).
+// The switches that select a launch list are read when the handle is created (plan()); `graph_updates` at every call.
 static bool tune_str(const char* key, std::string* out) {
   const char* e = getenv("GRL_TUNE");
   if (!e) return false;
@@ -163,6 +164,23 @@ struct Op {
   double flops = 0;   // algorithmic FLOPs of one launch (2 * M * N * K over the taps / rows that exist)
   double flops_exec = 0;   // FLOPs the launch's MFMAs execute (>= flops: masked taps of the parity-class backward-data form)
   double bytes = 0;   // algorithmic HBM bytes of one launch
+};
+
+// A call of n >= 2 updates on the device RNG in which work of update t + 1 rides on a launch of update t:
+// first | mid ... mid | last.  alternate: update j of the call uses flavour j & 1 (double-buffered images); otherwise only
+// flavour 0 exists.  grl_ctx::run_call strings the parts into graphs.
+struct CallPlan {
+  std::vector<Op> first, mid[2], last[2];
+  bool alternate = false;
+  bool short_call_graph = false;   // calls of <= 32 updates go out as ONE graph, cached per n
+  // (a plan is built in one go inside plan() / grl_allreduce_connect, which fail as a whole: it is never observed half built)
+  bool ok() const { return !first.empty(); }
+  // part v (0 first, 1 middle, 2 last) of flavour f
+  std::vector<Op>& part(int v, int f = 0) { return v == 0 ? first : (v == 1 ? mid[f] : last[f]); }
+  const std::vector<Op>& part(int v, int f = 0) const { return const_cast<CallPlan*>(this)->part(v, f); }
+  // the part update j of a call of n updates runs
+  std::vector<Op>* at(int j, int n) { return &part(j == 0 ? 0 : (j + 1 < n ? 1 : 2), alternate ? j & 1 : 0); }
+  void clear() { *this = CallPlan(); }
 };
 
 struct ProfAcc {
@@ -285,13 +303,17 @@ struct grl_ctx {
   std::vector<Op> ops_rng, ops_gather, ops_grads, ops_apply, ops_act, ops_act_det, ops_act_sto, ops_enc, wgrad_ops;   // ops_rng: gather with device RNG; ops_gather: gather of explicit indices
   LossArgs loss_args;              // SAC: batch reductions appended to the reduce_slabs launch (fused heads)
   std::vector<Op> ops_grads_apply; // SAC: ops_grads with Adam + Polyak fused into the slab-reduction launch (full updates)
-  // SAC, calls of several updates on the device RNG: the next minibatch is gathered inside the last launch of an update
-  std::vector<Op> ops_pf_first, ops_pf_mid, ops_pf_last;
-  // "gather_ride": the same three kinds of update with the minibatch IMAGES double buffered (x_obs / x_obs_b).  Flavour f reads
-  // buffer f; its head launch carries the image gather of update t+1 into the other buffer as extra workgroups (heads_mfma.h),
-  // its reduction launch the per-row extras of update t+1 (GatherArgs.parts)
-  std::vector<Op> ops_ride_first, ops_ride_mid[2], ops_ride_last[2];
-  bool ride_ok = false;
+  // Calls of several updates on the device RNG (CallPlan).  SAC "prefetch": the next minibatch is gathered inside the last launch
+  // of an update.  "gather_ride": the same with the minibatch IMAGES double buffered (x_obs / x_obs_b).  Flavour f reads buffer f;
+  // its head launch carries the image gather of update t+1 into the other buffer as extra workgroups (heads_mfma.h), its
+  // reduction launch the per-row extras of update t+1 (GatherArgs.parts)
+  CallPlan pf, ride;
+  // DQN / BDQ, FOUR launches per update.  "q_pf" (uniform replay): the next update's index draw + gather ride on the apply launch.
+  // "per_pf" (prioritised): write-back + block-sum refresh ride on the trunk launch, the sampler of the next update on the apply
+  // launch; the forward launch opens the update
+  CallPlan q_pf, per_pf;
+  // data parallel: pf / ride ending in the exchange (built at connect): [0] two-shot, [1] one-shot
+  CallPlan pf_dp[2], ride_dp[2];
   float* x_obs_b = nullptr;
   Op wgrad_conv_alt;                    // the merged weight-gradient launch with conv1's operand in x_obs_b
   bool have_wgrad_conv_alt = false;
@@ -304,15 +326,7 @@ struct grl_ctx {
   float* ae_gp4 = nullptr;               // auto-encoder step: the output gradient's four sub-position planes (plan_ae, MseArgs.gp4)
   GatherArgs pf_ga;
   int pf_gx = 0;
-  bool prefetch_ok = false;
   std::vector<Op> ops_grads_apply_per;   // DQN / BDQ with prioritised replay: ... and the priority write-back
-  // ... multi-update calls on the device RNG, FOUR launches per update: write-back + block-sum refresh ride on the trunk launch,
-  // the sampler of the next update on the apply launch (plan_q.inl "per_pf"); the forward launch opens the update
-  std::vector<Op> ops_per_pf_first, ops_per_pf_mid, ops_per_pf_last;
-  // ... and uniform replay: the next update's index draw + gather ride on the apply launch (plan_q.inl "q_pf"), four launches per update
-  std::vector<Op> ops_q_pf_first, ops_q_pf_mid, ops_q_pf_last;
-  bool q_pf_ok = false;
-  bool per_pf_ok = false;
   Op q_fwd_tick_op, q_bwd_wb_op;
   bool have_q_fwd_tick = false, have_q_bwd_wb = false;
   // data parallel, staged (grl_compute_grads_staged): stage 0 ends with the dense (fc + head) gradients final in the
@@ -337,10 +351,6 @@ struct grl_ctx {
   AdamArgs adam_base;
   std::vector<Op> ops_dp;                // two-shot: reduce + publish | reduce-scatter | pull + Adam + Polyak (replaces the last op of ops_grads)
   std::vector<Op> ops_dp1;               // one-shot: reduce + publish | sum of all ranks + Adam + Polyak
-  std::vector<Op> ops_pfdp_first, ops_pfdp_mid, ops_pfdp_last;      // prefetching sequences ending in the two-shot exchange (built at connect)
-  std::vector<Op> ops_pfdp1_first, ops_pfdp1_mid, ops_pfdp1_last;   // ... in the one-shot exchange
-  // ... and the "gather_ride" sequences ending in the exchange: [0] two-shot, [1] one-shot; flavour = image buffer the update reads
-  std::vector<Op> ops_ridedp_first[2], ops_ridedp_mid[2][2], ops_ridedp_last[2][2];
   LossArgs pf_lk;                        // loss arguments / gather of the NEXT update as the prefetching reductions carry them (plan_sac)
   GatherArgs pf_g2;
   std::vector<Op> dp_body;               // ops_grads without its final reduction (the exchange's first kernel forms the sums)
@@ -416,55 +426,71 @@ struct grl_ctx {
     return GRL_OK;
   }
 
-  // `count` identical updates (device RNG: nothing changes on the host between them): groups of up to `graph_updates`
-  // (GRL_TUNE; default 16, powers of two) go out as ONE graph -- no graph boundary between the updates of a group (measured on
-  // MI355X, SAC depth B = 256: 5 090 -> 5 194 / 5 227 / 5 232 updates/s at 4 / 8 / 16 per graph)
-  int run_repeated(const std::string& key, const std::vector<std::vector<Op>*>& one, int count) {
-    const int max_group = std::max(1, std::min(64, tune_int("graph_updates", 16)));
+  // Updates j .. j + count - 1 of a call on the device RNG (nothing changes on the host between them): groups of up to
+  // `graph_updates` (GRL_TUNE; default 16, powers of two) go out as ONE graph -- no graph boundary between the updates of a group
+  // (measured on MI355X, SAC depth B = 256: 5 090 -> 5 194 / 5 227 / 5 232 updates/s at 4 / 8 / 16 per graph).  add(j, seq)
+  // appends the op lists of update j.  by_parity: the updates alternate between two flavours, so a graph is also keyed by the
+  // parity of its first update (groups are powers of two: every group of two or more ends on the other parity).
+  static int max_group() { return std::max(1, std::min(64, tune_int("graph_updates", 16))); }
+  int run_grouped(const std::string& key, int j, int count, bool by_parity,
+                  const std::function<void(int, std::vector<std::vector<Op>*>&)>& add) {
+    const int limit = graphs_on() ? max_group() : 1;
     while (count > 0) {
       int group = 1;
-      while (2 * group <= max_group && 2 * group <= count) group *= 2;
-      if (group == 1 || !graphs_on()) {
-        if (int e = run_seq(key, one)) return e;
-        count -= 1;
-        continue;
-      }
+      while (2 * group <= limit && 2 * group <= count) group *= 2;
       std::vector<std::vector<Op>*> seq;
-      for (int g = 0; g < group; ++g) seq.insert(seq.end(), one.begin(), one.end());
-      if (int e = run_seq(key + "_x" + std::to_string(group), seq)) return e;
+      for (int g = 0; g < group; ++g) add(j + g, seq);
+      const std::string k = key + (by_parity ? "_p" + std::to_string(j & 1) : "") + (group > 1 ? "_x" + std::to_string(group) : "");
+      if (int e = run_seq(k, seq)) return e;
+      j += group;
       count -= group;
     }
     return GRL_OK;
   }
-
-  // A call of n >= 2 updates with double-buffered minibatch images (plan_sac "gather_ride"): update j reads image buffer j % 2
-  // and its head launch gathers the images of update j + 1 into the other one.  first: the call's first update (flavour 0);
-  // mid[f] / last[f]: later updates reading buffer f.
-  int run_ride(const std::string& key, std::vector<Op>* first, std::vector<Op>* mid, std::vector<Op>* last, int n_steps) {
-    const int max_group = std::max(1, std::min(64, tune_int("graph_updates", 16)));
-    if (n_steps <= 32 && max_group != 1) {        // short calls (SAC.learn: n = number of environments): ONE graph, cached per n
+  // `count` identical updates
+  int run_repeated(const std::string& key, const std::vector<std::vector<Op>*>& one, int count) {
+    return run_grouped(key, 0, count, false, [&](int, std::vector<std::vector<Op>*>& seq) { seq.insert(seq.end(), one.begin(), one.end()); });
+  }
+  // A call of n >= 2 updates on the device RNG through a CallPlan.  Short calls (SAC.learn: n = number of environments) of a plan
+  // with short_call_graph are ONE graph, cached per n; every other call is first | grouped middles | last.  The keys of a plan
+  // that does not alternate carry no parity: one sequence, one graph.  (`graph_updates` <= 0 counts as 1 here as in the grouping.)
+  int run_call(const std::string& key, CallPlan& p, int n_steps) {
+    if (p.short_call_graph && n_steps <= 32 && max_group() != 1) {
       std::vector<std::vector<Op>*> seq;
-      seq.push_back(first);
-      for (int j = 1; j + 1 < n_steps; ++j) seq.push_back(&mid[j & 1]);
-      seq.push_back(&last[(n_steps - 1) & 1]);
+      for (int j = 0; j < n_steps; ++j) seq.push_back(p.at(j, n_steps));
       return run_seq(key + "_call_" + std::to_string(n_steps), seq);
     }
-    if (int e = run_seq(key + "_first", {first})) return e;
-    int j = 1;                                     // index of the next update within the call
-    while (j + 1 < n_steps) {
-      const int left = n_steps - 1 - j;
-      int group = 1;
-      while (2 * group <= max_group && 2 * group <= left) group *= 2;
-      std::vector<std::vector<Op>*> seq;
-      for (int g = 0; g < group; ++g) seq.push_back(&mid[(j + g) & 1]);
-      // (groups are powers of two: every group of two or more starts at the parity of its first update and ends on the other)
-      if (int e = run_seq(key + "_mid_p" + std::to_string(j & 1) + "_x" + std::to_string(group), seq)) return e;
-      j += group;
-    }
-    return run_seq(key + "_last_p" + std::to_string((n_steps - 1) & 1), {&last[(n_steps - 1) & 1]});
+    if (int e = run_seq(key + "_first", {&p.first})) return e;
+    if (int e = run_grouped(key + "_mid", 1, n_steps - 2, p.alternate,
+                            [&](int j, std::vector<std::vector<Op>*>& seq) { seq.push_back(p.at(j, n_steps)); })) return e;
+    const int last = n_steps - 1;
+    return run_seq(key + "_last" + (p.alternate ? "_p" + std::to_string(last & 1) : ""), {p.at(last, n_steps)});
   }
 
   // ---------------------------------------------------------------- helpers
+  // arguments of an Adam launch on the whole trainable range; polyak: followed by the target update of SAC (cfg.tau)
+  AdamArgs adam_args(float scale, bool polyak, float eps = 1e-8f) const {
+    AdamArgs aa;
+    memset(&aa, 0, sizeof(aa));
+    aa.params = params; aa.grads = grads; aa.m = adam_m; aa.v = adam_v; aa.n_train = n_train; aa.sc = sc;
+    aa.grad_scale = scale; aa.tau = polyak ? cfg.tau : 0.f; aa.eps = eps;
+    aa.src_ofs = polyak ? vf_off : 0; aa.n_polyak = polyak ? n_polyak : 0; aa.target = params + tgt_off;
+    return aa;
+  }
+  // the op lists of one full update behind its minibatch gather: Adam fused into the reduction where the plan has that form
+  std::vector<std::vector<Op>*> update_seq(std::vector<Op>* gather) {
+    if (!ops_grads_apply.empty()) return {gather, &ops_grads_apply};
+    return {gather, &ops_grads, &ops_apply};
+  }
+  // ... of one prioritised update, drawn on the device RNG or from the caller's uniforms: the sampler that gathers its rows +
+  // the fully fused update, else sampler | update_seq | priority write-back
+  std::vector<std::vector<Op>*> per_update_seq(bool rng) {
+    if (!ops_grads_apply_per.empty()) return {rng ? &ops_per_rng_g : &ops_per_u_g, &ops_grads_apply_per};
+    std::vector<std::vector<Op>*> seq = update_seq(&ops_gather);
+    seq.insert(seq.begin(), rng ? &ops_per_rng : &ops_per_u);
+    seq.push_back(&ops_per_update);
+    return seq;
+  }
   template <class T>
   T* upload_vec(Arena& a, const std::vector<T>& v) {
     T* d = (T*)a.take(std::max<size_t>(v.size(), 1) * sizeof(T));

@@ -380,10 +380,7 @@ int grl_ctx::plan_ae() {
   {
     grl_ctx* self = this;
     elem("adam", [self](hipStream_t s) {
-      AdamArgs aa;
-      aa.params = self->params; aa.grads = self->grads; aa.m = self->adam_m; aa.v = self->adam_v;
-      aa.n_train = self->n_train; aa.sc = self->sc; aa.grad_scale = 1.f; aa.tau = 0.f; aa.eps = 1e-7f;   // Keras epsilon
-      aa.src_ofs = 0; aa.n_polyak = 0; aa.target = self->params;
+      const AdamArgs aa = self->adam_args(1.f, false, 1e-7f);   // Keras epsilon
       const int blocks = (int)std::min<int64_t>(2048, (self->n_train + 255) / 256);
       hipLaunchKernelGGL(adam_polyak_kernel, dim3(blocks), dim3(256), 0, s, aa);
     });

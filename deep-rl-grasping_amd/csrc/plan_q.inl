@@ -601,10 +601,7 @@ int grl_ctx::plan_q() {
     Op op; op.tag = "adam";
     grl_ctx* self = this;
     op.run = [self](hipStream_t s) {
-      AdamArgs aa;
-      aa.params = self->params; aa.grads = self->grads; aa.m = self->adam_m; aa.v = self->adam_v;
-      aa.n_train = self->n_train; aa.sc = self->sc; aa.grad_scale = self->grad_scale; aa.tau = 0.f; aa.eps = 1e-8f;
-      aa.src_ofs = 0; aa.n_polyak = 0; aa.target = self->params + self->tgt_off;
+      const AdamArgs aa = self->adam_args(self->grad_scale, false);
       const int blocks = (int)std::min<int64_t>(2048, (self->n_train + 255) / 256);
       hipLaunchKernelGGL(adam_polyak_kernel, dim3(blocks), dim3(256), 0, s, aa);
     };
@@ -639,10 +636,7 @@ int grl_ctx::plan_q() {
       const int q_gx = (img_elems + 255) / 256;      // tiles per row of gather_norm_kernel on this plan (scalar form)
       auto apply_op = [self, dr, nd, clip, rp, rows, fin, qga, q_gx](bool with_per, bool refresh = false, bool next_sampler = false, bool next_uniform = false) {
         return [self, dr, nd, clip, rp, rows, fin, with_per, refresh, next_sampler, next_uniform, qga, q_gx](hipStream_t s) {
-          AdamArgs aa;
-          aa.params = self->params; aa.grads = self->grads; aa.m = self->adam_m; aa.v = self->adam_v;
-          aa.n_train = self->n_train; aa.sc = self->sc; aa.grad_scale = self->grad_scale; aa.tau = 0.f; aa.eps = 1e-8f;
-          aa.src_ofs = 0; aa.n_polyak = 0; aa.target = self->params + self->tgt_off;
+          const AdamArgs aa = self->adam_args(self->grad_scale, false);
           PerArgs q = self->per;
           q.prio_in = self->q_prio;
           // prioritised replay: one more workgroup writes the new priorities back (per_update_kernel's work)
@@ -692,9 +686,9 @@ int grl_ctx::plan_q() {
         //   middle:                            forward[tick] | towers | trunk + write-back + refresh | apply + sampler(t + 1)
         //   last  :                            forward[tick] | towers | trunk + write-back + refresh | apply
         if (tune_int("per_pf", 1) && q_chain && have_q_fwd_tick && have_q_bwd_wb && !ops_per_rng_g.empty()) {
-          ops_per_pf_first = ops_per_rng_g;
+          per_pf.first = ops_per_rng_g;
           for (int v = 0; v < 3; ++v) {
-            std::vector<Op>& dst = v == 0 ? ops_per_pf_first : (v == 1 ? ops_per_pf_mid : ops_per_pf_last);
+            std::vector<Op>& dst = per_pf.part(v);
             for (size_t k = 0; k + 1 < ops_grads_apply_per.size(); ++k) {
               const Op& o = ops_grads_apply_per[k];
               if (o.tag == "q_fwd") dst.push_back(v == 0 ? o : q_fwd_tick_op);
@@ -705,10 +699,11 @@ int grl_ctx::plan_q() {
             ao.run = v == 2 ? apply_op(false) : apply_op(false, false, true);
             dst.push_back(ao);
           }
-          per_pf_ok = true;
+          // (short_call_graph stays off here and on the SAC sequences that end in the exchange (pf_dp, built at connect): calls of
+          //  <= 32 updates go out as first | grouped middles | last.  Turning it on is a speed change that needs a measurement.)
         }
         if (getenv("GRL_PLAN_DUMP"))
-          fprintf(stderr, "grl plan: per_pf        multi-update prioritised calls, four launches per update (sampler on the apply launch): %s\n", per_pf_ok ? "yes" : "no");
+          fprintf(stderr, "grl plan: per_pf        multi-update prioritised calls, four launches per update (sampler on the apply launch): %s\n", per_pf.ok() ? "yes" : "no");
       }
       // "q_pf": uniform replay, calls of several updates on the device RNG -- FOUR launches per update instead of six: the index draw
       // and the gather of update t + 1 (rng_kernel + gather_norm_kernel) ride on the launch that ends update t, whose forward launch
@@ -723,9 +718,9 @@ int grl_ctx::plan_q() {
           ft.tick_sc = sc; ft.tick_rng = 1;
           fwd_adv.run = [ft](hipStream_t s) { launch_q_fwd(ft, s); };
         }
-        ops_q_pf_first = ops_rng;
+        q_pf.first = ops_rng;
         for (int v = 0; v < 3; ++v) {
-          std::vector<Op>& dst = v == 0 ? ops_q_pf_first : (v == 1 ? ops_q_pf_mid : ops_q_pf_last);
+          std::vector<Op>& dst = q_pf.part(v);
           for (size_t k = 0; k + 1 < ops_grads_apply.size(); ++k) {
             const Op& o = ops_grads_apply[k];
             if (o.tag == "gather_norm") { if (v == 0) dst.push_back(o); }
@@ -736,7 +731,7 @@ int grl_ctx::plan_q() {
           ao.run = v == 2 ? apply_op(false) : apply_op(false, false, false, true);
           dst.push_back(ao);
         }
-        q_pf_ok = true;
+        q_pf.short_call_graph = true;
         if (getenv("GRL_PLAN_DUMP"))
           fprintf(stderr, "grl plan: q_pf          multi-update uniform calls, four launches per update (draw + gather on the apply launch)\n");
       }

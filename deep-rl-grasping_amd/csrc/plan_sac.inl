@@ -746,11 +746,7 @@ int grl_ctx::plan_sac() {
     op.join = true;
     const LossArgs la = loss_args;
     const int has_loss = fused_heads ? 1 : 0;
-    AdamArgs aa;
-    memset(&aa, 0, sizeof(aa));
-    aa.params = params; aa.grads = grads; aa.m = adam_m; aa.v = adam_v; aa.n_train = n_train; aa.sc = sc;
-    aa.grad_scale = 1.f; aa.tau = c.tau; aa.eps = 1e-8f;
-    aa.src_ofs = vf_off; aa.n_polyak = n_polyak; aa.target = params + tgt_off;
+    const AdamArgs aa = adam_args(1.f, true);
     op.run = [dr, d_rt, ntiles, la, has_loss, aa](hipStream_t s) {
       hipLaunchKernelGGL(reduce_slabs_kernel, dim3(ntiles + has_loss), dim3(256), 0, s, dr, d_rt, ntiles, la, has_loss, aa, 0);
     };
@@ -810,7 +806,7 @@ int grl_ctx::plan_sac() {
           Op op; op.tag = "gather_norm";
           op.bytes = ops_rng[0].bytes;
           op.run = [g1, gx](hipStream_t s) { launch_gather(g1, gx, s); };
-          ops_pf_first.push_back(op);
+          pf.first.push_back(op);
         }
         GatherArgs g2 = g1;
         g2.quiet = 1; g2.rng_ahead = 1;
@@ -824,7 +820,7 @@ int grl_ctx::plan_sac() {
         ro.bytes -= (double)n_train * 4;
         ro.run = [dr, d_rt, ntiles, lk, has_loss, aq, g2, gx](hipStream_t s) { launch_reduce_slabs_gather(dr, d_rt, ntiles, lk, has_loss, aq, g2, gx, s); };
         for (int v = 0; v < 3; ++v) {     // 0 first, 1 middle, 2 last
-          std::vector<Op>& dst = v == 0 ? ops_pf_first : (v == 1 ? ops_pf_mid : ops_pf_last);
+          std::vector<Op>& dst = pf.part(v);
           for (size_t k = 0; k + 1 < ops_grads_apply.size(); ++k) {
             if (ops_grads_apply[k].tag == "heads") dst.push_back(pf_heads[v == 0 ? 0 : 1]);
             else dst.push_back(ops_grads_apply[k]);
@@ -832,7 +828,7 @@ int grl_ctx::plan_sac() {
           dst.push_back(v == 2 ? fo : ro);
         }
         pf_lk = lk; pf_g2 = g2;     // (the data-parallel update builds its own final launches from these at connect)
-        prefetch_ok = true;
+        pf.short_call_graph = true;
         // ---- "gather_ride": the IMAGES of update t+1 gathered by extra workgroups of update t's HEAD launch -- 64 workgroups of
         // row-local chains on 256 CUs for 16 us -- instead of the reduction launch, which is memory bound itself.  What the
         // gather writes and update t still reads after its head launch: x_obs (conv1's weight gradient, in the last GEMM launch)
@@ -869,7 +865,7 @@ int grl_ctx::plan_sac() {
             rx.bytes = ro.bytes - ops_rng[0].bytes;
             rx.run = [dr, d_rt, ntiles, lr3, has_loss, aq, gx2](hipStream_t s) { launch_reduce_slabs_gather(dr, d_rt, ntiles, lr3, has_loss, aq, gx2, 1, s); };
             ride_lk = lr3; ride_g2 = gx2;
-            Op first_g = ops_pf_first[0];                // the call's own gather, leaving rng_img behind
+            Op first_g = pf.first[0];                // the call's own gather, leaving rng_img behind
             {
               GatherArgs g0 = g1;
               g0.set_img = 1;
@@ -891,8 +887,8 @@ int grl_ctx::plan_sac() {
                 heads_ride[v].run = [dv, hnblk, hshape, gi, gx](hipStream_t s) { launch_heads_fused(hshape, hnblk, s, dv, &gi, gx); };
               }
               for (int v = (f ? 1 : 0); v < 3; ++v) {    // (the call's first update is always flavour 0)
-                const std::vector<Op>& src = v == 0 ? ops_pf_first : (v == 1 ? ops_pf_mid : ops_pf_last);
-                std::vector<Op>& dst = v == 0 ? ops_ride_first : (v == 1 ? ops_ride_mid[f] : ops_ride_last[f]);
+                const std::vector<Op>& src = pf.part(v);
+                std::vector<Op>& dst = ride.part(v, f);
                 for (size_t k = 0; k < src.size(); ++k) {
                   const bool last_op = k + 1 == src.size();
                   if (v == 0 && k == 0) dst.push_back(first_g);
@@ -904,7 +900,7 @@ int grl_ctx::plan_sac() {
                 }
               }
             }
-            ride_ok = true;
+            ride.alternate = ride.short_call_graph = true;
             if (getenv("GRL_PLAN_DUMP"))
               fprintf(stderr, "grl plan: gather_ride  %d image-gather workgroups of the next update ride on the head launch (%d tiles per row, %d rows each); extras on the reduction launch\n",
                       gx * (2 * B / ride_rows), gx, ride_rows);
@@ -920,10 +916,7 @@ int grl_ctx::plan_sac() {
     op.bytes = (double)n_train * 4 * 7 + (double)n_polyak * 4 * 2;
     grl_ctx* self = this;
     op.run = [self](hipStream_t s) {
-      AdamArgs aa;
-      aa.params = self->params; aa.grads = self->grads; aa.m = self->adam_m; aa.v = self->adam_v;
-      aa.n_train = self->n_train; aa.sc = self->sc; aa.grad_scale = self->grad_scale; aa.tau = self->cfg.tau; aa.eps = 1e-8f;
-      aa.src_ofs = self->vf_off; aa.n_polyak = self->n_polyak; aa.target = self->params + self->tgt_off;
+      const AdamArgs aa = self->adam_args(self->grad_scale, true);
       const int blocks = (int)std::min<int64_t>(2048, (self->n_train + 255) / 256);
       hipLaunchKernelGGL(adam_polyak_kernel, dim3(blocks), dim3(256), 0, s, aa);
     };
