@@ -69,6 +69,19 @@ int grl_query_sizes(const grl_config* cfg, grl_sizes* out) {
   return GRL_OK;
 }
 
+// Prioritised replay with an empty ring: all leaves 0, PerState at its starting values.  The block sums / minima (per.bsum,
+// per.bmin) need no reset: the first update of every prioritised call rebuilds ALL of them from the leaves below the ring's fill
+// (per_blocksum_kernel in front of the first sampler, plan_q.inl), on a used handle as on a new one.  Used by grl_create and
+// by grl_state_import for a checkpoint saved without its ring.
+static hipError_t per_start(grl_ctx* h) {
+  hipError_t e = hipMemset(h->per.p, 0, (size_t)h->cfg.replay_capacity * 8);
+  if (e != hipSuccess) return e;
+  PerState ps;
+  memset(&ps, 0, sizeof(ps));
+  ps.max_priority = 1.f; ps.p_min = 1.0; ps.beta = 1.0;
+  return hipMemcpy(h->per.st, &ps, sizeof(ps), hipMemcpyHostToDevice);
+}
+
 int grl_create(const grl_config* cfg, const grl_buffers* bufs, grl_handle* out) {
   if (int e = check_cfg(cfg)) return e;
   if (!bufs || !out || !bufs->state || !bufs->grads || !bufs->work || !bufs->replay)
@@ -104,11 +117,7 @@ int grl_create(const grl_config* cfg, const grl_buffers* bufs, grl_handle* out) 
     hipMemcpy(h->n_count, c2, 16, hipMemcpyHostToDevice);
   }
   if (h->per_on) {
-    hipMemset(h->per.p, 0, (size_t)cfg->replay_capacity * 8);
-    PerState ps;
-    memset(&ps, 0, sizeof(ps));
-    ps.max_priority = 1.f; ps.p_min = 1.0; ps.beta = 1.0;
-    e = hipMemcpy(h->per.st, &ps, sizeof(ps), hipMemcpyHostToDevice);
+    e = per_start(h);
     if (e != hipSuccess) { delete h; return fail(GRL_ERR_HIP, std::string("per init: ") + hipGetErrorString(e)); }
   }
   *out = h;
@@ -1179,5 +1188,7 @@ int grl_profile_dump(grl_handle h, char* buf, int cap) {
   buf[cap - 1] = 0;
   return GRL_OK;
 }
+
+#include "checkpoint.inl"
 
 }  // extern "C"

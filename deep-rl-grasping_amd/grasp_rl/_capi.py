@@ -56,7 +56,22 @@ EXPORTS = [
     "grl_norm_update", "grl_set_running_stats", "grl_set_ret_var", "grl_get_obs_stats",
     "grl_allreduce_init", "grl_allreduce_connect", "grl_train_step_allreduce", "grl_allreduce_status", "grl_allreduce_set_overlap", "grl_allreduce_set_mode", "grl_allreduce_set_timeout",
     "grl_allreduce_disconnect",
+    "grl_state_size", "grl_state_export", "grl_state_import", "grl_replay_segments",
 ]
+
+
+class GrlStateHeader(C.Structure):
+    """Head of the blob grl_state_export writes (include/grl.h: grl_state_header)."""
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_int32), ("layout", C.c_int32), ("config_bytes", C.c_int32),
+                ("config_hash", C.c_uint64), ("replay_pos", C.c_int64), ("replay_size", C.c_int64),
+                ("total_bytes", C.c_uint64)]
+
+
+class GrlSegment(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("row_bytes", C.c_uint64), ("rows", C.c_int64)]
+
+
+STATE_MAGIC = 0x534C5247
 
 
 class GrlError(RuntimeError):
@@ -125,6 +140,11 @@ def load_library(path=None):
     lib.grl_profile_enable.argtypes = [vp, i32]
     lib.grl_profile_query.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(i64)]
     lib.grl_profile_dump.argtypes = [vp, C.c_char_p, i32]
+    lib.grl_state_size.argtypes = [vp, C.POINTER(C.c_size_t)]
+    lib.grl_state_export.argtypes = [vp, vp, C.c_size_t]
+    lib.grl_state_export.restype = i64
+    lib.grl_state_import.argtypes = [vp, vp, C.c_size_t]
+    lib.grl_replay_segments.argtypes = [vp, i32, C.POINTER(GrlSegment)]
     return lib
 
 

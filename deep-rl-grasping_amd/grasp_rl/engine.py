@@ -10,12 +10,69 @@ Reference call sites this object stands behind: sb.SAC(...) construction and .le
 update at /root/reference/manipulation_main/training/sb_helper.py:104-128,175-177.
 """
 import ctypes as C
+import json
+import os
+import shutil
 from collections import OrderedDict
 
 import numpy as np
 
 from . import _capi
 from ._capi import GrlError, check
+
+
+CHECKPOINT_FORMAT = 1
+STAGE_BYTES = 256 << 20         # page-locked staging of save_state / load_state: two halves used in turn, never more than this
+
+
+def _flush(f):
+    f.flush()
+    os.fsync(f.fileno())
+
+
+def _sync_dir(path):
+    """The directory entries themselves on the disk (a rename is durable only then)."""
+    try:
+        fd = os.open(path, os.O_RDONLY)
+    except OSError:
+        return
+    try:
+        os.fsync(fd)
+    except OSError:
+        pass
+    finally:
+        os.close(fd)
+
+
+def _release_staging(be):
+    if hasattr(be, "release_staging"):
+        be.release_staging()
+
+
+def _read_chunks(be, t, lo, hi):
+    """float32 elements [lo, hi) of arena `t` as successive host arrays (each valid until the next one is asked for)."""
+    fn = getattr(be, "read_chunks", None)
+    if fn is not None:
+        yield from fn(t, lo, hi)
+        return
+    step = STAGE_BYTES // 8
+    for a in range(lo, hi, step):
+        yield be.to_host(t[a:min(hi, a + step)])
+
+
+def _write_chunks(be, t, lo, hi, fill):
+    """fill(array) loads the next float32 elements of [lo, hi) into a host array, which then goes to arena `t`."""
+    fn = getattr(be, "write_chunks", None)
+    if fn is not None:
+        fn(t, lo, hi, fill)
+        return
+    step = STAGE_BYTES // 8
+    for a in range(lo, hi, step):
+        b = min(hi, a + step)
+        buf = np.empty(b - a, np.float32)
+        fill(buf)
+        be.write(t[a:b], buf)
+    be.synchronize()
 
 
 class TorchCudaBackend:
@@ -88,6 +145,71 @@ class TorchCudaBackend:
 
     def as_torch(self, t):
         return t
+
+    # ---- checkpoint I/O: arena <-> host through ONE page-locked buffer of at most STAGE_BYTES, its two halves used in
+    # turn, so that the device copy of chunk k + 1 runs while the caller writes (reads) chunk k to (from) the file
+    def _staging(self, n):
+        want = min(STAGE_BYTES // 4, 2 * max(int(n), 1))
+        want += want & 1
+        st = getattr(self, "_stage", None)
+        if st is None or st.numel() < want:
+            self._stage = st = self.torch.empty(want, dtype=self.torch.float32).pin_memory()
+        half = st.numel() // 2
+        return [st[:half], st[half:2 * half]], half
+
+    def release_staging(self):
+        """Frees the page-locked buffer (up to STAGE_BYTES): one save / load allocates it once and gives it back."""
+        self.stream.synchronize()
+        self._stage = None
+
+    def staging_bytes(self):
+        st = getattr(self, "_stage", None)
+        return 0 if st is None else int(st.numel()) * 4
+
+    def read_chunks(self, t, lo, hi):
+        torch = self.torch
+        if hi <= lo:
+            return
+        halves, half = self._staging(hi - lo)
+        evs = [torch.cuda.Event(), torch.cuda.Event()]
+
+        def issue(k, a):
+            b = min(hi, a + half)
+            with torch.cuda.stream(self.stream):
+                halves[k][:b - a].copy_(t[a:b], non_blocking=True)
+                evs[k].record(self.stream)
+            return b - a
+
+        a, k = lo, 0
+        m = issue(k, a)
+        while True:
+            nxt = a + m
+            m_next = issue(k ^ 1, nxt) if nxt < hi else 0
+            evs[k].synchronize()
+            yield halves[k][:m].numpy()
+            if not m_next:
+                break
+            a, m, k = nxt, m_next, k ^ 1
+
+    def write_chunks(self, t, lo, hi, fill):
+        torch = self.torch
+        if hi <= lo:
+            return
+        halves, half = self._staging(hi - lo)
+        evs = [torch.cuda.Event(), torch.cuda.Event()]
+        used = [False, False]
+        a, k = lo, 0
+        while a < hi:
+            b = min(hi, a + half)
+            if used[k]:
+                evs[k].synchronize()
+            fill(halves[k][:b - a].numpy())
+            with torch.cuda.stream(self.stream):
+                t[a:b].copy_(halves[k][:b - a], non_blocking=True)
+                evs[k].record(self.stream)
+            used[k] = True
+            a, k = b, k ^ 1
+        self.stream.synchronize()
 
 
 class SacEngine:
@@ -285,6 +407,163 @@ class SacEngine:
 
     def replay_size(self):
         return int(self.lib.grl_replay_size(self.h))
+
+    # ------------------------------------------------------------------ checkpoint / resume (DESIGN.md "Checkpoints")
+    def replay_segments(self):
+        """[(byte offset, bytes per row, rows)] of the replay arena's arrays; rows == 0: an array that is saved whole
+        (grl_replay_segments)."""
+        segs = (_capi.GrlSegment * 32)()
+        n = check(self.lib, self.lib.grl_replay_segments(self.h, 32, segs))
+        return [(int(segs[k].offset), int(segs[k].row_bytes), int(segs[k].rows)) for k in range(n)]
+
+    def export_state(self):
+        """The handle's host-side state as bytes (grl_state_export; synchronises the stream)."""
+        size = C.c_size_t()
+        check(self.lib, self.lib.grl_state_size(self.h, C.byref(size)))
+        buf = C.create_string_buffer(max(1, size.value))
+        n = check(self.lib, self.lib.grl_state_export(self.h, buf, size.value))
+        return buf.raw[:n]
+
+    def import_state(self, blob):
+        check(self.lib, self.lib.grl_state_import(self.h, C.c_char_p(bytes(blob)), len(blob)))
+
+    def _arena_sizes(self):
+        return {k: int(getattr(self.sizes, k)) for k in ("state_bytes", "grads_bytes", "work_bytes", "replay_bytes")}
+
+    @staticmethod
+    def _segment_span(seg, filled):
+        off, row_bytes, rows = seg
+        nbytes = row_bytes * filled if rows else row_bytes
+        if off % 4 or nbytes % 4:
+            raise GrlError("replay segment is not a whole number of 4-byte words")
+        return off // 4, (off + nbytes) // 4
+
+    def save_state(self, dirpath, include_replay=True, extra=None):
+        """Writes the full training state of this engine to the directory `dirpath`: meta.json, state.bin (the state arena),
+        handle.bin (grl_state_export) and -- unless include_replay is False -- one replay_<k>.bin per array of the replay
+        arena, stored rows only.  `extra`: {file name: bytes} written next to them (the model layer's host state), part of
+        the same atomic step.  Built as `<dirpath>.tmp`, every file and the directory flushed to the disk, and renamed at
+        the end: a save that dies -- or a machine that is reset -- leaves the previous checkpoint as it was, at `dirpath`
+        or, between the two renames, at `<dirpath>.old`, where `load_state` finds it.  The page-locked staging buffer is
+        released when the save ends."""
+        dirpath = os.fspath(dirpath).rstrip("/")
+        tmp, old = dirpath + ".tmp", dirpath + ".old"
+        if os.path.isdir(tmp):
+            shutil.rmtree(tmp)
+        os.makedirs(tmp)
+        blob = self.export_state()
+        hdr = _capi.GrlStateHeader.from_buffer_copy(blob[:C.sizeof(_capi.GrlStateHeader)])
+        try:
+            return self._save_state(dirpath, tmp, old, blob, hdr, include_replay, extra or {})
+        finally:
+            _release_staging(self.be)
+
+    def _save_state(self, dirpath, tmp, old, blob, hdr, include_replay, extra):
+        for name, raw in [("handle.bin", blob)] + sorted(extra.items()):
+            with open(os.path.join(tmp, name), "wb") as f:
+                f.write(raw)
+                _flush(f)
+        with open(os.path.join(tmp, "state.bin"), "wb") as f:
+            for chunk in _read_chunks(self.be, self.state, 0, int(self.state.shape[0])):
+                f.write(memoryview(chunk).cast("B"))
+            _flush(f)
+        segs = self.replay_segments()
+        if include_replay:
+            for k, seg in enumerate(segs):
+                lo, hi = self._segment_span(seg, int(hdr.replay_size))
+                with open(os.path.join(tmp, "replay_%d.bin" % k), "wb") as f:
+                    for chunk in _read_chunks(self.be, self.replay, lo, hi):
+                        f.write(memoryview(chunk).cast("B"))
+                    _flush(f)
+        meta = {"format": CHECKPOINT_FORMAT, "grl_version": int(self.lib.grl_version()),
+                "config_hash": "%016x" % hdr.config_hash, "sizes": self._arena_sizes(),
+                "state_floats": int(self.state.shape[0]), "handle_bytes": len(blob),
+                "segments": [list(sg) for sg in segs], "include_replay": bool(include_replay),
+                "replay_size": int(hdr.replay_size), "replay_pos": int(hdr.replay_pos)}
+        with open(os.path.join(tmp, "meta.json"), "w") as f:
+            json.dump(meta, f, indent=1, sort_keys=True)
+            _flush(f)
+        _sync_dir(tmp)
+        # at every point one complete checkpoint stands at `dirpath` or at `<dirpath>.old`: an `.old` left by a save that
+        # died between its renames goes only once `dirpath` exists again
+        if os.path.isdir(dirpath):
+            if os.path.isdir(old):
+                shutil.rmtree(old)
+            os.rename(dirpath, old)
+        os.rename(tmp, dirpath)
+        _sync_dir(os.path.dirname(os.path.abspath(dirpath)))
+        if os.path.isdir(old):
+            shutil.rmtree(old)
+        return meta
+
+    def load_state(self, dirpath):
+        """Restores what `save_state` wrote.  Everything is checked before anything changes: format, grl_version(),
+        configuration hash, arena sizes, segment table, file sizes and -- by grl_state_import -- the handle blob; a
+        mismatch raises GrlError and leaves this engine as it was.  Once those checks have passed the arenas are
+        overwritten file by file: an I/O error from then on (a file that changes or becomes unreadable underneath) raises and
+        leaves the engine half loaded -- load again or discard it.  A checkpoint saved without its ring restores everything
+        else; `replay_size()` is then 0.  The page-locked staging buffer is released when the load ends."""
+        try:
+            return self._load_state(dirpath)
+        finally:
+            _release_staging(self.be)
+
+    def _load_state(self, dirpath):
+        dirpath = os.fspath(dirpath).rstrip("/")
+        if not os.path.isdir(dirpath) and os.path.isdir(dirpath + ".old"):
+            dirpath = dirpath + ".old"          # a save died between its two renames: the previous checkpoint
+        try:
+            with open(os.path.join(dirpath, "meta.json")) as f:
+                meta = json.load(f)
+        except (OSError, ValueError) as e:
+            raise GrlError("no readable checkpoint at %s: %s" % (dirpath, e))
+        if meta.get("format") != CHECKPOINT_FORMAT:
+            raise GrlError("checkpoint format %r, this build reads %d" % (meta.get("format"), CHECKPOINT_FORMAT))
+        if meta.get("grl_version") != int(self.lib.grl_version()):
+            raise GrlError("checkpoint written by library version %r, this is %d" % (meta.get("grl_version"), self.lib.grl_version()))
+        with open(os.path.join(dirpath, "handle.bin"), "rb") as f:
+            blob = f.read()
+        hsz = C.sizeof(_capi.GrlStateHeader)
+        mine = _capi.GrlStateHeader.from_buffer_copy(self.export_state()[:hsz])
+        hdr = _capi.GrlStateHeader.from_buffer_copy(blob[:hsz]) if len(blob) >= hsz else None
+        if hdr is None or hdr.magic != _capi.STATE_MAGIC or hdr.config_hash != mine.config_hash:
+            # a short or foreign blob, or one of another configuration: grl_state_import refuses it before it changes
+            # anything and says why (it names the first grl_config field that differs)
+            self.import_state(blob)
+            raise GrlError("checkpoint was written for another configuration (config hash)")
+        if meta.get("config_hash") != "%016x" % hdr.config_hash:       # the blob is this configuration's: nothing imported
+            raise GrlError("meta.json names configuration hash %r, handle.bin %016x" % (meta.get("config_hash"), hdr.config_hash))
+        with_ring = bool(meta.get("include_replay"))
+        if meta.get("sizes") != self._arena_sizes() or meta.get("state_floats") != int(self.state.shape[0]):
+            raise GrlError("checkpoint arena sizes %r differ from this engine's %r" % (meta.get("sizes"), self._arena_sizes()))
+        segs = self.replay_segments()
+        if [tuple(sg) for sg in meta.get("segments", [])] != segs:
+            raise GrlError("checkpoint replay layout differs from this engine's")
+        files = [("state.bin", self.state, 0, int(self.state.shape[0]))]
+        if with_ring:
+            if meta.get("replay_size") != hdr.replay_size or meta.get("replay_pos") != hdr.replay_pos:
+                raise GrlError("meta.json and handle.bin disagree about the ring")
+            for k, seg in enumerate(segs):
+                lo, hi = self._segment_span(seg, int(hdr.replay_size))
+                files.append(("replay_%d.bin" % k, self.replay, lo, hi))
+        else:                                   # the ring stays out: cursor and size come back as 0
+            hdr.replay_pos = hdr.replay_size = 0
+            blob = bytes(hdr) + blob[hsz:]
+        for name, _, lo, hi in files:
+            path = os.path.join(dirpath, name)
+            if not os.path.isfile(path) or os.path.getsize(path) != 4 * (hi - lo):
+                raise GrlError("checkpoint file %s is missing or has the wrong size" % name)
+        self.import_state(blob)                 # the last check (length, layout, host fields); nothing has changed before it
+        for name, arena, lo, hi in files:
+            with open(os.path.join(dirpath, name), "rb") as f:
+                def fill(buf, f=f, name=name):
+                    if f.readinto(memoryview(buf).cast("B")) != buf.nbytes:
+                        raise GrlError("checkpoint file %s is truncated" % name)
+                _write_chunks(self.be, arena, lo, hi, fill)
+        # the state arena carries the ring size of the SAVED run (DevScalars.replay_size): importing again lets the blob
+        # decide (0 when the ring was left out)
+        self.import_state(blob)
+        return meta
 
     # ------------------------------------------------------------------ update
     def _noise(self, idx, eps, n_steps):

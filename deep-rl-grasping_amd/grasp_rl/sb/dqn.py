@@ -39,6 +39,7 @@ from . import policies as pol
 from . import save_util
 from . import spaces as sp
 from .callbacks import as_callback
+from .checkpoint import CheckpointMixin
 from .vec_env import DummyVecEnv, VecEnv, expand_training_env, unwrap_vec_normalize
 
 
@@ -51,7 +52,7 @@ class LinearSchedule:
         return self.initial_p + frac * (self.final_p - self.initial_p)
 
 
-class _QModel:
+class _QModel(CheckpointMixin):
     """Shared host loop of DQN and BDQ."""
     _engine_factory = staticmethod(lambda cfg, device: QEngine(cfg, device=device))
     algo = "dqn"
@@ -228,6 +229,10 @@ class _QModel:
         total_timesteps = int(total_timesteps)
         if reset_num_timesteps:
             self.num_timesteps = 0
+        # a model restored from a checkpoint continues in place (sb/checkpoint.py): the exploration, beta and learning-rate
+        # schedules keep the length they had in the saved run and read on from the restored counter
+        resume = self._take_resume(reset_num_timesteps)
+        self._schedule_total = sched_total = total_timesteps if resume is None else (resume["schedule_total"] or total_timesteps)
         rt, dp = self._dp_rt, self._dp
         W = 1 if rt is None else rt.world
         lead = rt is None or rt.rank == 0
@@ -237,15 +242,18 @@ class _QModel:
         if rt is not None and vn is not None:       # running statistics merged over the ranks
             from ..parallel import share_running_stats
             share_running_stats(vn, rt.ctrl)
-        self.exploration = LinearSchedule(self.exploration_fraction * total_timesteps, self.exploration_final_eps,
+        self.exploration = LinearSchedule(self.exploration_fraction * sched_total, self.exploration_final_eps,
                                           self.exploration_initial_eps)
-        beta_iters = self.prioritized_replay_beta_iters or total_timesteps
+        beta_iters = self.prioritized_replay_beta_iters or sched_total
         beta_schedule = LinearSchedule(beta_iters, 1.0, self.prioritized_replay_beta0)
         episode_rewards, episode_successes = [0.0], []
         self.episode_reward = np.zeros((self.n_envs,))
         writer = logger.SummaryWriter(self.tensorboard_log, tb_log_name or type(self).__name__) \
             if getattr(self, "tensorboard_log", None) else None
-        obs = self.env.reset()
+        if resume is not None and vn is not None:
+            obs = vn.reset_restored(resume["ret"])      # this first observation is in the restored statistics already
+        else:
+            obs = self.env.reset()
         obs_ = vn.get_original_obs() if vn is not None else obs
         start = time.time()
         callback.on_training_start(locals(), globals())
@@ -311,7 +319,7 @@ class _QModel:
                 if vn is not None and eng.cfg.normalize:
                     eng.set_obs_stats(vn.obs_rms.mean, vn.obs_rms.var, float(vn.ret_rms.var))
                 if callable(self.learning_rate):    # stable-baselines evaluates the schedule per update: lr(1 - step / total)
-                    eng.set_learning_rate(self.learning_rate(1.0 - (self.num_timesteps - 1) / max(1, total_timesteps)))
+                    eng.set_learning_rate(self.learning_rate(1.0 - (self.num_timesteps - 1) / max(1, self._schedule_total)))
                 if self.prioritized_replay:
                     (eng if dp is None else dp).train_per(n_upd, beta_schedule.value(self.num_timesteps))
                 elif dp is not None:
@@ -360,11 +368,11 @@ class _QModel:
                  n_envs=self.n_envs, _vectorize_action=True)
         return d
 
-    def save(self, save_path, cloudpickle=False):
+    def _save_zip(self, save_path):
         return save_util.save_to_zip(save_path, self._data(), self.get_parameters())
 
     @classmethod
-    def load(cls, load_path, env=None, custom_objects=None, **kwargs):
+    def _load_zip(cls, load_path, env=None, custom_objects=None, **kwargs):
         data, params = save_util.load_from_zip(load_path)
         model = cls(policy=data.get("policy") if isinstance(data.get("policy"), type) else None, env=None,
                     _init_setup_model=False)

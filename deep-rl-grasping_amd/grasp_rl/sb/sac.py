@@ -42,6 +42,7 @@ from . import policies as pol
 from . import save_util
 from . import spaces as sp
 from .callbacks import as_callback, may_read_observations
+from .checkpoint import CheckpointMixin
 from .vec_env import DummyVecEnv, VecEnv, expand_training_env, unwrap_vec_normalize
 
 _POLICY_NAMES = {"MlpPolicy": pol.SacMlpPolicy, "CnnPolicy": pol.SacCnnPolicy, "LnMlpPolicy": pol.SacLnMlpPolicy,
@@ -68,7 +69,7 @@ def resolve_device_norm(setting, user_callback, rt, dp):
     return setting
 
 
-class SAC:
+class SAC(CheckpointMixin):
     # tests substitute the g++ emulation build here; the product default needs a HIP device
     _engine_factory = staticmethod(lambda cfg, device: SacEngine(cfg, device=device))
 
@@ -293,6 +294,10 @@ class SAC:
         total_timesteps = int(total_timesteps)
         if reset_num_timesteps:
             self.num_timesteps = 0
+        # a model restored from a checkpoint continues in place (sb/checkpoint.py): the loop counter, the learning-rate
+        # schedule's reference and the statistics stand where the saved run left them
+        resume = self._take_resume(reset_num_timesteps)
+        self._schedule_total = total_timesteps if resume is None else (resume["schedule_total"] or total_timesteps)
         rt, dp = self._dp_rt, self._dp
         W = 1 if rt is None else rt.world
         lead = rt is None or rt.rank == 0
@@ -313,12 +318,13 @@ class SAC:
         # stable-baselines hands callbacks a FileWriter when tensorboard_log is set, None otherwise
         writer = logger.SummaryWriter(self.tensorboard_log, tb_log_name) if self.tensorboard_log else None
         if device_norm and vn is not None and vn.norm_obs and eng.cfg.normalize in (1, 2):
-            vn.attach_device(eng)
+            # restored: the device holds the statistics of the saved run already, in both halves of their double buffer
+            vn.attach_device(eng, upload=resume is None)
             self._norm_stamp = None
         finished = False
         try:
             self._learn_loop(total_timesteps, callback, log_interval, writer, rt, dp, W, lead, eng, vn, N, episode_rewards,
-                             episode_successes, ep_info_buf, start)
+                             episode_successes, ep_info_buf, start, resume)
             finished = True
         finally:
             if vn is not None and vn._dev is not None:     # whatever ended the loop: the wrapper carries the statistics again
@@ -338,15 +344,18 @@ class SAC:
         return self
 
     def _learn_loop(self, total_timesteps, callback, log_interval, writer, rt, dp, W, lead, eng, vn, N, episode_rewards,
-                    episode_successes, ep_info_buf, start):
+                    episode_successes, ep_info_buf, start, resume=None):
         n_episodes = 0
         infos_values = {}
-        obs = self.env.reset()
+        if resume is not None and vn is not None:
+            obs = vn.reset_restored(resume["ret"])      # this first observation is in the restored statistics already
+        else:
+            obs = self.env.reset()
         obs_ = vn.get_original_obs() if vn is not None else obs
         serial = vn.observed_serial if vn is not None else None     # engine.observe ticket of `obs` (device-side statistics)
         callback.on_training_start(locals(), globals())
         callback.on_rollout_start()
-        step = 0
+        step = 0 if resume is None else self.num_timesteps // (N * W)      # vectorised steps taken so far
         # stable-baselines: `for step in range(total_timesteps)` -- a continued run (reset_num_timesteps=False) takes
         # total_timesteps MORE environment steps from where the counter stands
         end = self.num_timesteps + total_timesteps
@@ -372,7 +381,7 @@ class SAC:
                     self.n_updates += k
                     self._sync_norm_stats()
                     if callable(self.learning_rate):    # SB: frac = 1 - step / total (step = index of this env step)
-                        eng.set_learning_rate(self.learning_rate(1.0 - done_steps / max(1, total_timesteps)))
+                        eng.set_learning_rate(self.learning_rate(1.0 - done_steps / max(1, self._schedule_total)))
                     if dp is not None:
                         dp.train(k)      # k updates on the GLOBAL minibatch: gradients exchanged inside each update's graph
                     else:
@@ -478,11 +487,19 @@ class SAC:
             "_vectorize_action": self._vectorize_action, "policy_kwargs": self.policy_kwargs,
         }
 
-    def save(self, save_path, cloudpickle=False):
+    def _save_zip(self, save_path):
         return save_util.save_to_zip(save_path, self._data(), self.get_parameters())
 
+    def _restored_norm_stamp(self):
+        """The host wrapper and the device hold the same restored statistics: `_sync_norm_stats` pushes again only once
+        they have moved (a push rewrites the device's copy, and a frozen wrapper would never have pushed)."""
+        vn = self._vec_normalize_env
+        if vn is not None:
+            self._norm_stamp = (id(vn.obs_rms), float(vn.obs_rms.count), id(vn.ret_rms), float(vn.ret_rms.count),
+                                float(np.sum(vn.obs_rms.mean)), float(np.sum(vn.obs_rms.var)), float(np.sum(vn.ret_rms.var)))
+
     @classmethod
-    def load(cls, load_path, env=None, custom_objects=None, **kwargs):
+    def _load_zip(cls, load_path, env=None, custom_objects=None, **kwargs):
         data, params = save_util.load_from_zip(load_path)
         if "policy_kwargs" in kwargs and kwargs["policy_kwargs"] != data.get("policy_kwargs"):
             raise ValueError("the specified policy kwargs do not equal the stored policy kwargs")

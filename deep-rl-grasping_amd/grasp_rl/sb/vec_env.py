@@ -665,14 +665,16 @@ class VecNormalize(VecEnvWrapper):
         self.observed_serial = None      # engine.observe serial of the observations last handed out (None: not on the device)
 
     # -- observation statistics on the device (opt-in, grasp_rl.sb.SAC(device_norm=True)) -------------------------
-    def attach_device(self, engine):
+    def attach_device(self, engine, upload=True):
         """From now on `obs_rms` is maintained by the engine (grl_norm_update: the same float32 batch moments and
         float64 Chan merge, on the GPU) and, while training, `step_wait` / `reset` hand out RAW observations for the
         engine to normalise where it consumes them (grl_act flag 2, sample-time gather).  The host copy is refreshed by
-        `pull_device_stats` -- automatically before pickling / `save` and in `sync_envs_normalization`."""
+        `pull_device_stats` -- automatically before pickling / `save` and in `sync_envs_normalization`.  upload=False: the
+        engine holds the statistics already (restored from a checkpoint) and keeps them as they are."""
         self._dev = engine
-        engine.set_obs_stats(self.obs_rms.mean, self.obs_rms.var, float(self.ret_rms.var))
-        engine.set_running_stats(self.obs_rms.mean, self.obs_rms.var, self.obs_rms.count)
+        if upload:
+            engine.set_obs_stats(self.obs_rms.mean, self.obs_rms.var, float(self.ret_rms.var))
+            engine.set_running_stats(self.obs_rms.mean, self.obs_rms.var, self.obs_rms.count)
 
     def _observe(self, obs):
         """One upload per env step: the statistics are updated from the device copy, and `observed_serial` tells the learn
@@ -749,6 +751,22 @@ class VecNormalize(VecEnvWrapper):
             self.pull_device_stats()
         if self.training:
             self.obs_rms.update(obs)
+        return self.normalize_obs(obs)
+
+    def reset_restored(self, ret=None):
+        """`reset` for a run that continues from a checkpoint taken where its environments start an episode: the saved run
+        has folded this first observation into the statistics when its last step returned it, so it is only handed out
+        (device-side: uploaded without a statistics update), and the discounted returns stand where they stood."""
+        obs = self.venv.reset()
+        self.old_obs = obs
+        self.ret = np.zeros(self.num_envs) if ret is None else np.array(ret, np.float64)
+        self.observed_serial = None
+        if self.hands_out_raw_observations:
+            if hasattr(self._dev, "observe") and obs.shape[0] <= getattr(self._dev, "observe_rows", 0):
+                self.observed_serial = self._dev.observe(obs, update_stats=False)
+            return obs
+        if self._dev is not None:
+            self.pull_device_stats()
         return self.normalize_obs(obs)
 
     def normalize_obs(self, obs):

@@ -344,6 +344,55 @@ int64_t grl_debug_fetch(grl_handle h, const char* name, float* out, int64_t cap)
    reference call stands behind it).  Synchronises the stream.  Returns n or <0. */
 int64_t grl_debug_store(grl_handle h, const char* name, const float* in, int64_t n);
 
+/* Checkpoint and resume (DESIGN.md "Checkpoints").  The training state lives in three places: the STATE arena
+   (parameters, Adam moments, DevScalars with the beta powers / learning rate / Philox counters / replay size, the
+   sample-time and running VecNormalize statistics with their double-buffered count) and the REPLAY arena (ring, priority
+   leaves, block sums, PerState) -- both caller-owned, the caller copies them -- and a few host-side fields of the handle,
+   which the three calls below move as one opaque blob:
+     grl_state_size    bytes grl_state_export will write now (it depends on how many observations grl_observe holds);
+     grl_state_export  host; synchronises the handle's stream.  Writes a grl_state_header, the grl_config the handle was
+                       created with, the host fields (ring cursor and size, parity of the running-statistics double
+                       buffer, rows held by grl_observe) and -- the only training state in the WORK arena -- the
+                       observations of the last two grl_observe calls.  Returns the bytes written, GRL_ERR_INVALID when
+                       cap is too small;
+     grl_state_import  host; synchronises.  Checks everything before it changes anything: GRL_ERR_INVALID for a short or
+                       foreign blob (magic, grl_version(), layout version) and for a blob of another configuration -- the
+                       message names the first grl_config field that differs -- GRL_ERR_STATE on a handle connected for
+                       data parallelism while an exchange is in flight (some rank has begun an exchange another has not
+                       finished).  Then restores the host fields and observed rows and re-derives the device mirror of
+                       the ring size (DevScalars.replay_size) from the blob, so the caller restores the state arena
+                       BEFORE importing.  A blob whose header says replay_size 0 (a caller that leaves the ring out sets
+                       replay_pos = replay_size = 0 in the header) also returns the priority tree to its initial state.
+                       Captured graphs stay valid: they hold arena addresses and configuration constants only, every
+                       counter they read lives in device memory.
+   grl_replay_segments lists the arrays of the replay arena: per-transition arrays (observations, next observations,
+   direct features, actions, rewards, dones -- packed RGB rows included -- and the priority leaves) as
+   {byte offset, bytes per row, rows = capacity}: rows [0, grl_replay_size) are the stored ones; arrays to be saved whole
+   (block sums and minima of the priority tree, PerState) as {offset, bytes, 0}.  Returns their number, < 0 when cap is
+   too small.  No reference call stands behind these four: stable-baselines checkpoints hold parameters only
+   (CheckpointCallback, sb_helper.py:81). */
+#define GRL_STATE_MAGIC 0x534c5247u   /* "GRLS" */
+#define GRL_STATE_LAYOUT 1
+typedef struct grl_state_header {
+  uint32_t magic;
+  int32_t version;        /* grl_version() of the writer                         */
+  int32_t layout;         /* GRL_STATE_LAYOUT                                    */
+  int32_t config_bytes;   /* sizeof(grl_config)                                  */
+  uint64_t config_hash;   /* FNV-1a over every grl_config field, in field order  */
+  int64_t replay_pos;     /* ring cursor                                         */
+  int64_t replay_size;    /* stored transitions                                  */
+  uint64_t total_bytes;   /* of the whole blob                                   */
+} grl_state_header;
+typedef struct grl_segment {
+  uint64_t offset;        /* bytes from the start of the replay arena            */
+  uint64_t row_bytes;     /* bytes per transition; the whole array when rows = 0 */
+  int64_t rows;           /* replay_capacity, or 0: save whole                   */
+} grl_segment;
+int grl_state_size(grl_handle h, size_t* bytes);
+int64_t grl_state_export(grl_handle h, void* host_buf, size_t cap);
+int grl_state_import(grl_handle h, const void* host_buf, size_t n);
+int grl_replay_segments(grl_handle h, int cap, grl_segment* out);
+
 /* wall-clock free kernel timing: enables hipEvent timing of tagged kernels in later steps */
 int grl_profile_enable(grl_handle h, int on);
 /* host: average ms per launch of the kernel tagged `name` since enable; "" lists tags into name_out */
