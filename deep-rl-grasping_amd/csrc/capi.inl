@@ -91,8 +91,7 @@ int grl_create(const grl_config* cfg, const grl_buffers* bufs, grl_handle* out) 
   h->st.base = (char*)bufs->state; h->gr.base = (char*)bufs->grads;
   h->wk.base = (char*)bufs->work; h->rp.base = (char*)bufs->replay;
   if (int e = h->plan()) { delete h; return e; }
-  const char* ng = getenv("GRL_NO_GRAPH");
-  h->use_graph = !(ng && ng[0] == '1');
+  h->use_graph = !h->sw.get(Sw::GRL_NO_GRAPH);
   for (auto& u : h->uploads) {
     hipError_t e = hipMemcpy(u.dst, u.bytes.data(), u.bytes.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) { delete h; return fail(GRL_ERR_HIP, std::string("table upload: ") + hipGetErrorString(e)); }
@@ -228,7 +227,7 @@ int grl_set_obs_stats(grl_handle h, const double* mean, const double* var, doubl
 // the source right after each of these calls.
 static int copy_from_caller(grl_handle h, void* dst, const void* src, size_t bytes) {
   HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
-  static const int always = tune_int("host_copy_wait", 0);
+  static const int always = Switches(SwRead::FIRST_COPY).get(Sw::host_copy_wait);
   bool wait = always != 0;
   if (!wait) {
     hipPointerAttribute_t at;
@@ -740,7 +739,7 @@ int grl_allreduce_init(grl_handle h, int rank, int world, void* handle_out) {
   if (e != hipSuccess) { h->dp_flags = nullptr; return fail(GRL_ERR_HIP, std::string("exchange flags: ") + hipGetErrorString(e)); }
   // the data as well unless GRL_TUNE dp_coarse=1: the exchange kernels store it write-through and load it at system scope,
   // so its caching policy costs nothing measurable on one GPU and fine-grained is the conservative choice between GPUs
-  e = tune_int("dp_coarse", 0) ? hipMalloc(&h->dp_buf, dbytes) : hipExtMallocWithFlags(&h->dp_buf, dbytes, hipDeviceMallocFinegrained);
+  e = Switches(SwRead::DP_INIT).get(Sw::dp_coarse) ? hipMalloc(&h->dp_buf, dbytes) : hipExtMallocWithFlags(&h->dp_buf, dbytes, hipDeviceMallocFinegrained);
   if (e != hipSuccess) {
     (void)hipFree(h->dp_flags); h->dp_flags = nullptr; h->dp_buf = nullptr;
     return fail(GRL_ERR_HIP, std::string("exchange buffer: ") + hipGetErrorString(e));
@@ -781,7 +780,7 @@ static DpArgs dp_channel(grl_ctx* h, int channel, const std::vector<std::pair<in
   for (size_t k = pieces.size(); k <= DP_MAX_RANGES; ++k) d.vstart[k] = v;
   d.n = v;
   d.chunk = rup((v + d.world - 1) / d.world, 4);      // (the last ranks' chunks may be short or empty)
-  d.timeout_ticks = (uint64_t)std::max(1, tune_int("dp_timeout_ms", 120000)) * 100000ull;     // 100 MHz wall clock
+  d.timeout_ticks = (uint64_t)std::max(1, Switches(SwRead::DP_CONNECT).get(Sw::dp_timeout_ms)) * 100000ull;     // 100 MHz wall clock
   d.host_err = h->dp_err_host;
   for (int p = 0; p < d.world; ++p) {
     d.ctl[p] = (DpCtl*)(flags[p] + (size_t)channel * dp_ctl_stride());
@@ -795,7 +794,7 @@ static DpArgs dp_channel(grl_ctx* h, int channel, const std::vector<std::pair<in
 // 19 us for the 5.4 MB bucket where the slab reduction with fused Adam, one quad per thread, takes 12)
 static int dp_blocks(int which, int64_t quads) {
   int v[3] = {0, 0, 0};
-  tune_int3("dp_blocks", v);
+  Switches(SwRead::DP_CONNECT).get3(Sw::dp_blocks, v);
   const int64_t all = std::max<int64_t>(1, (quads + 255) / 256);
   return (int)(v[which] > 0 ? std::min<int64_t>(v[which], all) : std::min<int64_t>(all, 4096));
 }
@@ -1084,14 +1083,13 @@ int grl_allreduce_status(grl_handle h, int64_t* exchanges, int* error) {
   for (int k = 0; k < DP_CHANNELS; ++k)
     HIPCHK(hipMemcpy(&c[k], (char*)h->dp_flags + k * dp_ctl_stride(), sizeof(DpCtl), hipMemcpyDeviceToHost));
   if (exchanges) *exchanges = c[0].epoch;          // (channel 0 takes part in every update, plain or overlapped)
-  if (getenv("GRL_PLAN_DUMP"))
-    for (int k = 0; k < DP_CHANNELS; ++k) {
-      fprintf(stderr, "grl dp: rank %d channel %d epoch %u error %u next_buf %u ready", h->dp.rank, k, c[k].epoch, c[k].error, c[k].next_buf);
-      for (int p = 0; p < h->dp.world; ++p) fprintf(stderr, " %u", c[k].ready[p]);
-      fprintf(stderr, " done");
-      for (int p = 0; p < h->dp.world; ++p) fprintf(stderr, " %u", c[k].done[p]);
-      fprintf(stderr, " mailbox %u\n", h->dp_err_host ? *h->dp_err_host : 0u);
-    }
+  for (int k = 0; k < DP_CHANNELS; ++k) {
+    plan_note("grl dp: rank %d channel %d epoch %u error %u next_buf %u ready", h->dp.rank, k, c[k].epoch, c[k].error, c[k].next_buf);
+    for (int p = 0; p < h->dp.world; ++p) plan_note(" %u", c[k].ready[p]);
+    plan_note(" done");
+    for (int p = 0; p < h->dp.world; ++p) plan_note(" %u", c[k].done[p]);
+    plan_note(" mailbox %u\n", h->dp_err_host ? *h->dp_err_host : 0u);
+  }
   int err = h->dp_err_host ? (int)*h->dp_err_host : 0;
   for (int k = 0; k < DP_CHANNELS; ++k) err |= (int)c[k].error;
   if (error) *error = err;

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cstdarg>
 #include <cmath>
 #include <chrono>
 #include <cstdio>
@@ -55,35 +56,126 @@ static int fail(int code, const std::string& msg) {
 
 static inline int64_t rup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
-// GRL_TUNE="key=value,key=value,...": the measurement / tuning knobs of scripts/ behind ONE variable (workgroup shape per
-// launch tag `i2cfg_<tag>`, `sk_wgs`, `wg_split` "a/b/c", `l0_split`, `graph_updates`, `dp_blocks` "a/b/c", `dp_coarse`,
-// `dp_timeout_ms`, `heads_stamps`) and the switches that select a tested alternative launch list (`fused_adam=0`,
-// `gather_prefetch=0`, `fused_q=0`, `fused_qapply=0`, `q_mfma=0`, `q_l0_chain=0`, `per_inc=0`).  None of them changes what is
-// computed; `q_mfma` / `fused_q` pick stage kernels with a different summation order (each checked against the oracle).
-// The switches that select a launch list are read when the handle is created (plan()); `graph_updates` at every call.
-static bool tune_str(const char* key, std::string* out) {
-  const char* e = getenv("GRL_TUNE");
-  if (!e) return false;
-  const std::string s(e), k(key);
-  size_t pos = 0;
-  while (pos < s.size()) {
-    size_t end = s.find(',', pos);
-    if (end == std::string::npos) end = s.size();
-    const std::string item = s.substr(pos, end - pos);
-    const size_t eq = item.find('=');
-    if (eq != std::string::npos && item.substr(0, eq) == k) { *out = item.substr(eq + 1); return true; }
-    pos = end + 1;
+// ------------------------------------------------------------------------------------------------
+// The switches: everything the library takes from the environment is a row of this table -- the keys of
+// GRL_TUNE="key=value,key=value,..." (tuning knobs of scripts/ and the switches that select a tested alternative launch list)
+// and the variables of their own.  README.md ("Switches of the library") says what each row selects and which test runs it.
+// None changes what is computed; `q_mfma` / `fused_q` pick stage kernels with a different summation order (each checked
+// against the oracle).  X(key, default, kind, read):
+//   kind  INT key=value | TRIPLE key=a/b/c, as many as given (default: the plan's own choice) | PER_TAG <key><launch tag>=value |
+//         VAR a variable of its own, on when its value starts with '1' | VAR_SET ... on when set at all
+//   read  CREATE where grl_create and the dry run of grl_query_sizes begin (GRL_NO_GRAPH: grl_create only) | CALL at every
+//         training call (max_group) | DP_INIT / DP_CONNECT at grl_allreduce_init / _connect | FIRST_COPY once per process, at the
+//         first copy of a caller's buffer (copy_from_caller) | NOTE at every plan note
+// A Switches object holds what ONE moment read and hands out only the rows of that moment, so a script that changes GRL_TUNE
+// between calls meets each key where the table says.
+#define GRL_SWITCHES(X)                       \
+  X(fused_adam, 1, INT, CREATE)               \
+  X(gather_prefetch, 1, INT, CREATE)          \
+  X(gather_ride, 1, INT, CREATE)              \
+  X(ride_rows, GATHER_RIDE_ROWS, INT, CREATE) \
+  X(gather_rows, 0, INT, CREATE)              \
+  X(conv_stack, 1, INT, CREATE)               \
+  X(conv_stack_bwd, 0, INT, CREATE)           \
+  X(l0_split, 3, INT, CREATE)                 \
+  X(wg_split, 0, TRIPLE, CREATE)              \
+  X(sk_wgs, 512, INT, CREATE)                 \
+  X(i2cfg_, -1, PER_TAG, CREATE)              \
+  X(heads_stamps, 0, INT, CREATE)             \
+  X(act_mfma, 1, INT, CREATE)                 \
+  X(act_poll, 1, INT, CREATE)                 \
+  X(fused_q, 1, INT, CREATE)                  \
+  X(q_mfma, 1, INT, CREATE)                   \
+  X(q_l0_chain, 1, INT, CREATE)               \
+  X(fused_qapply, 1, INT, CREATE)             \
+  X(q_chain, 1, INT, CREATE)                  \
+  X(q_chain_late, 1, INT, CREATE)             \
+  X(per_inc, 1, INT, CREATE)                  \
+  X(per_pf, 1, INT, CREATE)                   \
+  X(q_pf, 1, INT, CREATE)                     \
+  X(q_act, 1, INT, CREATE)                    \
+  X(graph_updates, 16, INT, CALL)             \
+  X(dp_coarse, 0, INT, DP_INIT)               \
+  X(dp_timeout_ms, 120000, INT, DP_CONNECT)   \
+  X(dp_blocks, 0, TRIPLE, DP_CONNECT)         \
+  X(host_copy_wait, 0, INT, FIRST_COPY)       \
+  X(GRL_NO_V2, 0, VAR, CREATE)                \
+  X(GRL_NO_FUSED_HEADS, 0, VAR, CREATE)       \
+  X(GRL_NO_HEADS_MFMA, 0, VAR, CREATE)        \
+  X(GRL_NO_GRAPH, 0, VAR, CREATE)             \
+  X(GRL_PLAN_DUMP, 0, VAR_SET, NOTE)
+enum class SwKind { INT, TRIPLE, PER_TAG, VAR, VAR_SET };
+enum class SwRead { CREATE, CALL, DP_INIT, DP_CONNECT, FIRST_COPY, NOTE };
+enum class Sw {
+#define X(id, dflt, kind, read) id,
+  GRL_SWITCHES(X)
+#undef X
+  COUNT
+};
+static const struct SwRow { const char* name; int dflt; SwKind kind; SwRead read; } SW_TABLE[] = {
+#define X(id, dflt, kind, read) {#id, dflt, SwKind::kind, SwRead::read},
+  GRL_SWITCHES(X)
+#undef X
+};
+
+// A line of the plan description a handle writes to stderr while GRL_PLAN_DUMP is set (tested live: scripts and tests set and
+// unset it around single calls)
+__attribute__((format(printf, 1, 2))) static void plan_note(const char* fmt, ...) {
+  if (!getenv(SW_TABLE[(int)Sw::GRL_PLAN_DUMP].name)) return;
+  va_list ap;
+  va_start(ap, fmt);
+  vfprintf(stderr, fmt, ap);
+  va_end(ap);
+}
+
+// What ONE moment read of the table's rows
+struct Switches {
+  SwRead moment;
+  std::map<std::string, std::string> set;     // the rows the environment mentions: key (PER_TAG: with its tag) -> value text
+  std::vector<std::string> unknown;           // GRL_TUNE keys that are no row of the table
+
+  explicit Switches(SwRead when) : moment(when) {
+    for (const SwRow& r : SW_TABLE)
+      if (const char* e = r.kind >= SwKind::VAR && r.read == when ? getenv(r.name) : nullptr)
+        if (r.kind == SwKind::VAR_SET || e[0] == '1') set[r.name] = "1";
+    const char* e = getenv("GRL_TUNE");
+    const std::string s(e ? e : "");
+    for (size_t pos = 0, end; pos < s.size(); pos = end + 1) {
+      end = std::min(s.find(',', pos), s.size());
+      const std::string item = s.substr(pos, end - pos);
+      const size_t eq = item.find('=');
+      const std::string key = item.substr(0, eq);
+      const SwRow* r = row_of(key);
+      if (eq != std::string::npos && r && r->kind < SwKind::VAR) set.emplace(key, item.substr(eq + 1));      // the first mention of a key counts
+      else if (!item.empty() && std::find(unknown.begin(), unknown.end(), key) == unknown.end()) unknown.push_back(key);
+    }
   }
-  return false;
-}
-static int tune_int(const char* key, int dflt) {
-  std::string v;
-  return tune_str(key, &v) ? atoi(v.c_str()) : dflt;
-}
-static int tune_int3(const char* key, int v[3]) {     // "a/b/c"
-  std::string t;
-  return tune_str(key, &t) ? sscanf(t.c_str(), "%d/%d/%d", &v[0], &v[1], &v[2]) : 0;
-}
+  static const SwRow* row_of(const std::string& key) {
+    for (const SwRow& r : SW_TABLE)
+      if (r.kind == SwKind::PER_TAG ? key.compare(0, strlen(r.name), r.name) == 0 : key == r.name) return &r;
+    return nullptr;
+  }
+  // value text of row k (PER_TAG: for launch tag `tag`), or nullptr: the default stands
+  const std::string* text(Sw k, const std::string& tag = "") const {
+    const SwRow& r = SW_TABLE[(int)k];
+    if (r.read != moment) { fprintf(stderr, "grl: switch '%s' is not read at this moment\n", r.name); abort(); }
+    const auto it = set.find(r.name + tag);
+    return it == set.end() ? nullptr : &it->second;
+  }
+  int get(Sw k, const std::string& tag = "") const { const std::string* t = text(k, tag); return t ? atoi(t->c_str()) : SW_TABLE[(int)k].dflt; }
+  void get3(Sw k, int v[3]) const {     // TRIPLE: overwrites as many of v[0..2] as are given
+    if (const std::string* t = text(k)) sscanf(t->c_str(), "%d/%d/%d", &v[0], &v[1], &v[2]);
+  }
+  // "grl tune: <key>=<value> ..." of the rows moved off their default, and a line per GRL_TUNE key the table does not know
+  // (which is ignored, as ever)
+  void note() const {
+    std::string s;
+    for (auto& kv : set)
+      if (const SwRow* r = row_of(kv.first); r->kind != SwKind::INT || atoi(kv.second.c_str()) != r->dflt) s += " " + kv.first + "=" + kv.second;
+    if (!s.empty()) plan_note("grl tune:%s\n", s.c_str());
+    for (auto& u : unknown) plan_note("grl tune: unknown key '%s' ignored\n", u.c_str());
+  }
+};
 
 // ------------------------------------------------------------------------------------------------
 struct Var {
@@ -214,6 +306,7 @@ using namespace grl;
 
 struct grl_ctx {
   grl_config cfg;
+  const Switches sw{SwRead::CREATE};   // read where grl_create / the dry run of grl_query_sizes begin
   hipStream_t stream = nullptr;
   bool dry = false;
 
@@ -431,7 +524,7 @@ struct grl_ctx {
   // (measured on MI355X, SAC depth B = 256: 5 090 -> 5 194 / 5 227 / 5 232 updates/s at 4 / 8 / 16 per graph).  add(j, seq)
   // appends the op lists of update j.  by_parity: the updates alternate between two flavours, so a graph is also keyed by the
   // parity of its first update (groups are powers of two: every group of two or more ends on the other parity).
-  static int max_group() { return std::max(1, std::min(64, tune_int("graph_updates", 16))); }
+  static int max_group() { return std::max(1, std::min(64, Switches(SwRead::CALL).get(Sw::graph_updates))); }
   int run_grouped(const std::string& key, int j, int count, bool by_parity,
                   const std::function<void(int, std::vector<std::vector<Op>*>&)>& add) {
     const int limit = graphs_on() ? max_group() : 1;
@@ -914,22 +1007,20 @@ struct grl_ctx {
   }
   // workgroup shape of a v2 launch: narrow outputs -> 128x32; few 64x64 tiles -> 32x64 with the reduction
   // split over wave pairs; otherwise 64x64 (shape 2, a 4-way split, stays selectable by GRL_TUNE i2cfg_<tag>)
-  static int v2_pick_cfg(const std::vector<IgemmProb>& probs, int variant, const std::string& tag) {
-    const int forced = tune_int(("i2cfg_" + tag).c_str(), -1);
+  int v2_pick_cfg(const std::vector<IgemmProb>& probs, int variant, const std::string& tag) const {
+    const int forced = sw.get(Sw::i2cfg_, tag);
     if (forced >= 0) return forced;
     int maxN = 0;
     long tiles64 = 0;
-    bool ones = false, longk = true;
+    bool ones = false;
     for (auto& p : probs) {
       maxN = std::max(maxN, p.N);
       tiles64 += (long)p.split * ((p.M + 63) / 64) * ((p.N + 63) / 64);
       ones = ones || p.p_ones_i >= 0;
-      longk = longk && std::min(p.K, p.k_chunk) >= 256;
     }
     if (maxN <= 32) return 1;
     // measured on MI355X (scripts/cfg_sweep.sh): below ~1.5 64x64 tiles per CU the 32x64 shape with a
     // 2-way reduction split wins (twice the workgroups, 48 KB of LDS so that three share a CU)
-    (void)longk;
     if (!ones && variant != 2 && tiles64 < 400) return 3;
     return 0;
   }
@@ -973,15 +1064,11 @@ struct grl_ctx {
         op.tag = tag;
         op.flops += tmp_b[0].flops;
         op.flops_exec += tmp_b[0].flops_exec;
-        grl_ctx* self = this;
         const std::string t2 = tag;
         op.run = [la, lb, t2](hipStream_t s) {
           launch_igemm2_pair(v2_key(la), la->n_tiles, lb->n_tiles, s, la->d_probs, la->d_tiles, lb->d_probs, lb->d_tiles, t2.c_str());
         };
-        (void)self;
-        if (getenv("GRL_PLAN_DUMP"))
-          fprintf(stderr, "grl plan: %-14s carries %d filler tiles of '%s' behind its own %d\n", tag.c_str(), lb->n_tiles,
-                  ftag.c_str(), la->n_tiles);
+        plan_note("grl plan: %-14s carries %d filler tiles of '%s' behind its own %d\n", tag.c_str(), lb->n_tiles, ftag.c_str(), la->n_tiles);
         ops.push_back(std::move(op));
       } else {
         for (auto& o : tmp_a) ops.push_back(o);
@@ -1004,8 +1091,7 @@ struct grl_ctx {
       }
     for (auto& p : l->probs)
       if (p.p_k0 < p.K) l->np = 3;
-    const char* nv2 = getenv("GRL_NO_V2");
-    l->v2 = !(nv2 && nv2[0] == '1');
+    l->v2 = !sw.get(Sw::GRL_NO_V2);
     for (auto& p : l->probs) l->v2 = l->v2 && v2_prob_ok(p, variant);
     // ones rows / K tails select a kernel instantiation: they must be uniform over the launch
     {
@@ -1038,8 +1124,7 @@ struct grl_ctx {
     if (l->sk) {
       long total = 0;
       for (auto& p : l->probs) total += (p.M + 127) / 128;
-      long slots = 512;                                                // ~2 workgroups per CU, each streams `per` tiles
-      slots = std::max(1, tune_int("sk_wgs", (int)slots));
+      const long slots = std::max(1, sw.get(Sw::sk_wgs));              // default 512: ~2 workgroups per CU, each streams `per` tiles
       const int per = (int)std::max<long>(1, (total + slots - 1) / slots);
       std::vector<int4> work;
       double flops = 0;
@@ -1053,9 +1138,8 @@ struct grl_ctx {
       l->d_probs = upload_vec(wk, per_tile_descs(l->probs, work));
       l->d_tiles = upload_vec(wk, work);
       launches.push_back(l);
-      if (getenv("GRL_PLAN_DUMP"))
-        fprintf(stderr, "grl plan: %-14s streaming short-K kernel K %d  probs %zu  row tiles per workgroup %d  tiles %d\n",
-                tag.c_str(), l->sk, l->probs.size(), per, l->n_tiles);
+      plan_note("grl plan: %-14s streaming short-K kernel K %d  probs %zu  row tiles per workgroup %d  tiles %d\n", tag.c_str(), l->sk,
+                l->probs.size(), per, l->n_tiles);
       Op op;
       op.tag = tag;
       op.flops = op.flops_exec = flops;
@@ -1074,9 +1158,8 @@ struct grl_ctx {
     if (variant == 2) tiles = xcd_order(tiles, l->probs, BMt, BNt);
     if (variant == 1 && l->v2) tiles = lpt_order(tiles, l->probs, BMt, BNt, lpt_extra_tiles, lpt_extra_w, tag);
     l->n_tiles = (int)tiles.size();
-    if (getenv("GRL_PLAN_DUMP"))
-      fprintf(stderr, "grl plan: %-14s variant %d pm %d qm %d np %d  %s cfg %d flags %d  probs %zu  tiles %d\n", tag.c_str(),
-              variant, l->pm, l->qm, l->np, l->v2 ? "v2" : "v1", l->cfg, l->flags, l->probs.size(), l->n_tiles);
+    plan_note("grl plan: %-14s variant %d pm %d qm %d np %d  %s cfg %d flags %d  probs %zu  tiles %d\n", tag.c_str(), variant, l->pm,
+              l->qm, l->np, l->v2 ? "v2" : "v1", l->cfg, l->flags, l->probs.size(), l->n_tiles);
     {
       std::vector<IgemmProb> descs = per_tile_descs(l->probs, tiles);
 #ifdef GRL_TILE_TRACE
@@ -1180,14 +1263,12 @@ struct grl_ctx {
           const double cost = 0.48 * mx + 2.0 * slab_bytes / 4e6 + 0.02 * std::max(s1, std::max(s2, s3));
           if (cost < best) { best = cost; wsplit[0] = s1; wsplit[1] = s2; wsplit[2] = s3; }
         }
-    if (getenv("GRL_PLAN_DUMP"))
-      fprintf(stderr, "grl plan: weight-gradient reduction splits %d / %d / %d (model cost %.1f us)\n", wsplit[0], wsplit[1], wsplit[2], best);
+    plan_note("grl plan: weight-gradient reduction splits %d / %d / %d (model cost %.1f us)\n", wsplit[0], wsplit[1], wsplit[2], best);
   }
 
   // tiles a launch of these problems will have, and its workgroup shape (mirrors add_launch; -1: not on igemm2_kernel)
-  static int planned_tiles(const std::vector<IgemmProb>& probs, int variant, const std::string& tag, int* cfg_out) {
-    const char* nv2 = getenv("GRL_NO_V2");
-    bool v2 = !(nv2 && nv2[0] == '1');
+  int planned_tiles(const std::vector<IgemmProb>& probs, int variant, const std::string& tag, int* cfg_out) const {
+    bool v2 = !sw.get(Sw::GRL_NO_V2);
     for (auto& p : probs) v2 = v2 && v2_prob_ok(p, variant) && (p.K % 4) == 0 && p.p_ones_i < 0;
     if (!v2 || probs.empty()) return -1;
     const int cfg = v2_pick_cfg(probs, variant, tag);
@@ -1306,9 +1387,8 @@ struct grl_ctx {
       }
       for (double c : cu) mx = std::max(mx, c);
       if (model_max) *model_max = mx + (out.size() > 1024 ? 1e6 : 0);   // more than 4 per CU: not all resident, the model does not hold
-      else if (getenv("GRL_PLAN_DUMP"))
-        fprintf(stderr, "grl plan: weight-gradient list of %zu tiles: %.0f slabs, per CU avg %.1f max %.0f (round-robin placement model)\n",
-                out.size(), tot, tot / 256, mx);
+      else plan_note("grl plan: weight-gradient list of %zu tiles: %.0f slabs, per CU avg %.1f max %.0f (round-robin placement model)\n",
+                     out.size(), tot, tot / 256, mx);
     }
     return out;
   }
@@ -1351,12 +1431,10 @@ struct grl_ctx {
     }
     std::vector<int4> out(n);
     for (int j = 0; j < n; ++j) out[j] = bin[j % NB][j / NB];
-    if (getenv("GRL_PLAN_DUMP")) {
-      double tot = 0, mx = 0;
-      for (double c : load) { tot += c; mx = std::max(mx, c); }
-      fprintf(stderr, "grl plan: %-14s placement: %d tiles + %d fillers, 64x64-slab units per CU avg %.1f max %.1f\n", tag.c_str(), n,
-              extra_tiles, tot / NB, mx);
-    }
+    double tot = 0, mx = 0;
+    for (double c : load) { tot += c; mx = std::max(mx, c); }
+    plan_note("grl plan: %-14s placement: %d tiles + %d fillers, 64x64-slab units per CU avg %.1f max %.1f\n", tag.c_str(), n, extra_tiles,
+              tot / NB, mx);
     return out;
   }
 
@@ -1455,9 +1533,9 @@ static ConvGeom cnn_geom(int l, int C_img) {
 
 // --------------------------------------------------------------------------------------------------
 int grl_ctx::plan() {
-  if (cfg.algo == GRL_ALGO_SAC) return plan_sac();
-  if (cfg.algo == GRL_ALGO_AE) return plan_ae();
-  return plan_q();
+  const int e = cfg.algo == GRL_ALGO_SAC ? plan_sac() : (cfg.algo == GRL_ALGO_AE ? plan_ae() : plan_q());
+  sw.note();
+  return e;
 }
 
 #include "plan_sac.inl"

@@ -241,7 +241,7 @@ int grl_ctx::plan_q() {
   // ---- row-local chains (q_kernels.h) when every width fits the head primitives; else one GEMM launch per layer
   bool fused_q = false;
   {
-    bool ok = tune_int("fused_q", 1) && nb <= 64 && Lc + std::max(Lb, Lv) <= GRL_MAX_LAYERS;
+    bool ok = sw.get(Sw::fused_q) && nb <= 64 && Lc + std::max(Lb, Lv) <= GRL_MAX_LAYERS;
     for (int k = 0; k < Lc; ++k) ok = ok && c.q_common[k] <= HT_MAXW;
     for (int l = 0; l < Lb; ++l) ok = ok && c.q_branch[l] <= HT_MAXW;
     for (int l = 0; l < Lv; ++l) ok = ok && c.q_value[l] <= HT_MAXW;
@@ -265,11 +265,11 @@ int grl_ctx::plan_q() {
     std::vector<IgemmProb> l0;
     // matrix-core stages (q_mfma.h) when every width fits their 64-wide shape (GRL_TUNE q_mfma=0 keeps the VALU chains); they
     // also take layer 0 (K = obs_dim <= 128) into the chain: no GEMM launch in front of it (GRL_TUNE q_l0_chain=0 keeps it)
-    bool want_mfma = q_mfma_built() && tune_int("q_mfma", 1) != 0 && nb <= QM_W && D + 1 <= QM_MAXP;
+    bool want_mfma = q_mfma_built() && sw.get(Sw::q_mfma) != 0 && nb <= QM_W && D + 1 <= QM_MAXP;
     for (int k = 0; k < Lc; ++k) want_mfma = want_mfma && c.q_common[k] <= QM_W;
     for (int l = 0; l < Lb; ++l) want_mfma = want_mfma && c.q_branch[l] <= QM_W;
     for (int l = 0; l < Lv; ++l) want_mfma = want_mfma && c.q_value[l] <= QM_W;
-    const bool l0_chain = want_mfma && c.obs_dim <= 2 * QM_W && tune_int("q_l0_chain", 1) != 0;
+    const bool l0_chain = want_mfma && c.obs_dim <= 2 * QM_W && sw.get(Sw::q_l0_chain) != 0;
     for (int n = 0; n < 3; ++n) {
       const QNetP& W = *Wn[n];
       const QNetAct& a = net[n];
@@ -355,21 +355,20 @@ int grl_ctx::plan_q() {
     // the chained backward leaves its slabs and row sums to the fused apply launch (below): planned only where that launch is
     // certain to exist -- its LDS (~71 KB) fits the device and no trainable variable outgrows its gradient buffer -- so that a
     // device / shape that offers less keeps the three-launch form instead of failing at the end of the plan
-    bool qapply_feasible = tune_int("fused_qapply", 1) != 0 && device_lds_bytes() >= (int)(GRL_QAPPLY_MAX * 4 + 1024 * 4 + 3 * 256 * 4);
+    bool qapply_feasible = sw.get(Sw::fused_qapply) != 0 && device_lds_bytes() >= (int)(GRL_QAPPLY_MAX * 4 + 1024 * 4 + 3 * 256 * 4);
     for (auto& v : vars) if (v.trainable && v.numel > GRL_QAPPLY_MAX) qapply_feasible = false;
-    q_chain = q_chain_available(qf.mfma != 0, fits64) && tune_int("q_chain", 1) != 0 && qapply_feasible && qc_shape_ok(nb, D, c.obs_dim);
+    q_chain = q_chain_available(qf.mfma != 0, fits64) && sw.get(Sw::q_chain) != 0 && qapply_feasible && qc_shape_ok(nb, D, c.obs_dim);
     if (q_chain) {      // nothing reads the trunk's pre-activation gradients from memory any more: its chain keeps them in LDS;
       // the towers' are read back by the weight-gradient workgroups of the trunk launch when there is one (GRL_TUNE q_chain_late=0:
       // every tower chain forms its slabs itself, at its end)
-      const bool late = Lc > 0 && tune_int("q_chain_late", 1) != 0;
+      const bool late = Lc > 0 && sw.get(Sw::q_chain_late) != 0;
       if (!late) for (auto& h : hb) { h.g0 = nullptr; for (int l = 0; l < GRL_MAX_LAYERS; ++l) h.g[l] = nullptr; }
       for (auto& h : htr) { h.g0 = nullptr; for (int l = 0; l < GRL_MAX_LAYERS; ++l) h.g[l] = nullptr; }
     }
     qf.fwd = upload_vec(wk, hf);
     qf.bwd_tw = upload_vec(wk, hb);
     if (!htr.empty()) qf.bwd_tr = upload_vec(wk, htr);
-    if (getenv("GRL_PLAN_DUMP"))
-      fprintf(stderr, "grl plan: q chains       %s%s\n", qf.mfma ? "matrix-core stages (q_mfma.h)" : "VALU stages (q_kernels.h)",
+    plan_note("grl plan: q chains       %s%s\n", qf.mfma ? "matrix-core stages (q_mfma.h)" : "VALU stages (q_kernels.h)",
               q_chain ? ", loss + weight gradients inside the backward chains (q_chain.h)" : "");
     if (!l0.empty()) add_launch(ops_grads, "q_l0", 0, l0);
     Op op; op.tag = "q_fwd";
@@ -460,7 +459,7 @@ int grl_ctx::plan_q() {
       QChainArgs ca;
       memset(&ca, 0, sizeof(ca));
       ca.f = qf; ca.l = q_loss_args; ca.l.defer_finish = 1;
-      ca.late = (Lc > 0 && tune_int("q_chain_late", 1) != 0) ? 1 : 0;
+      ca.late = (Lc > 0 && sw.get(Sw::q_chain_late) != 0) ? 1 : 0;
       ca.tw = upload_vec(wk, ytw);
       if (Lc > 0) {
         QcHead y;
@@ -610,7 +609,7 @@ int grl_ctx::plan_q() {
   {
     // Full updates: reduction + clip + Adam as one launch (q_reduce_clip_adam_kernel) when every trainable variable is
     // exactly one reduction descriptor and fits the kernel's LDS buffer.  GRL_TUNE fused_qapply=0 keeps the three launches.
-    bool ok = tune_int("fused_qapply", 1) && !ops_grads.empty() && ops_grads.back().tag == "reduce_slabs";
+    bool ok = sw.get(Sw::fused_qapply) && !ops_grads.empty() && ops_grads.back().tag == "reduce_slabs";
     size_t n_tr = 0;
     for (auto& v : vars) {
       if (!v.trainable) continue;
@@ -623,7 +622,7 @@ int grl_ctx::plan_q() {
     for (auto& r : reduces) ok = ok && r.row_len == 0;     // the kernel reads plain (non-strided) slabs
     // ~71 KB of static LDS per workgroup: fits gfx950's 160 KB; any device that offers less keeps the three launches
     if (ok && device_lds_bytes() < (int)(GRL_QAPPLY_MAX * 4 + 1024 * 4 + 3 * 256 * 4)) ok = false;
-    if (getenv("GRL_PLAN_DUMP")) fprintf(stderr, "grl plan: q_apply       reduction + clip + Adam in one launch: %s (%zu variables)\n", ok ? "yes" : "no", n_tr);
+    plan_note("grl plan: q_apply       reduction + clip + Adam in one launch: %s (%zu variables)\n", ok ? "yes" : "no", n_tr);
     if (ok) {
       ops_grads_apply.assign(ops_grads.begin(), ops_grads.end() - 1);
       Op op; op.tag = "q_apply";
@@ -673,7 +672,7 @@ int grl_ctx::plan_q() {
         Op po; po.tag = "q_apply";
         po.run = apply_op(true);
         ops_grads_apply_per.push_back(po);
-        if (tune_int("per_inc", 1) && !ops_per_rng_g_inc.empty()) {      // multi-update calls on the device RNG (capi: grl_train_step_per)
+        if (sw.get(Sw::per_inc) && !ops_per_rng_g_inc.empty()) {      // multi-update calls on the device RNG (capi: grl_train_step_per)
           ops_grads_apply_per_r = ops_grads_apply_per;
           ops_grads_apply_per_r.back().run = apply_op(true, true);
         }
@@ -685,7 +684,7 @@ int grl_ctx::plan_q() {
         //   first : sampler (all block sums) | forward | towers | trunk + write-back + refresh | apply + sampler(t + 1)
         //   middle:                            forward[tick] | towers | trunk + write-back + refresh | apply + sampler(t + 1)
         //   last  :                            forward[tick] | towers | trunk + write-back + refresh | apply
-        if (tune_int("per_pf", 1) && q_chain && have_q_fwd_tick && have_q_bwd_wb && !ops_per_rng_g.empty()) {
+        if (sw.get(Sw::per_pf) && q_chain && have_q_fwd_tick && have_q_bwd_wb && !ops_per_rng_g.empty()) {
           per_pf.first = ops_per_rng_g;
           for (int v = 0; v < 3; ++v) {
             std::vector<Op>& dst = per_pf.part(v);
@@ -702,8 +701,7 @@ int grl_ctx::plan_q() {
           // (short_call_graph stays off here and on the SAC sequences that end in the exchange (pf_dp, built at connect): calls of
           //  <= 32 updates go out as first | grouped middles | last.  Turning it on is a speed change that needs a measurement.)
         }
-        if (getenv("GRL_PLAN_DUMP"))
-          fprintf(stderr, "grl plan: per_pf        multi-update prioritised calls, four launches per update (sampler on the apply launch): %s\n", per_pf.ok() ? "yes" : "no");
+        plan_note("grl plan: per_pf        multi-update prioritised calls, four launches per update (sampler on the apply launch): %s\n", per_pf.ok() ? "yes" : "no");
       }
       // "q_pf": uniform replay, calls of several updates on the device RNG -- FOUR launches per update instead of six: the index draw
       // and the gather of update t + 1 (rng_kernel + gather_norm_kernel) ride on the launch that ends update t, whose forward launch
@@ -711,7 +709,7 @@ int grl_ctx::plan_q() {
       //   first : rng | gather | forward | towers | trunk | apply + draw / gather(t + 1)
       //   middle:                forward[counter += 1, tick] | towers | trunk | apply + draw / gather(t + 1)
       //   last  :                forward[counter += 1, tick] | towers | trunk | apply (counter += 1)
-      if (!per_on && tune_int("q_pf", 1) && have_q_fwd_tick && fin && B <= 1024) {
+      if (!per_on && sw.get(Sw::q_pf) && have_q_fwd_tick && fin && B <= 1024) {
         Op fwd_adv = q_fwd_tick_op;
         {
           QFusedArgs ft = qf;
@@ -732,8 +730,7 @@ int grl_ctx::plan_q() {
           dst.push_back(ao);
         }
         q_pf.short_call_graph = true;
-        if (getenv("GRL_PLAN_DUMP"))
-          fprintf(stderr, "grl plan: q_pf          multi-update uniform calls, four launches per update (draw + gather on the apply launch)\n");
+        plan_note("grl plan: q_pf          multi-update uniform calls, four launches per update (draw + gather on the apply launch)\n");
       }
       *q_defer = 1;
       if (fin) {     // split compute / apply path of this plan: the batch means as a launch of their own, behind the reduction
@@ -770,7 +767,7 @@ int grl_ctx::plan_q() {
     const float* adv = aact.adv; const float* vv = aact.v; float* qo = q_aout; const int rows = NA, Dq = D, nq = nb;
     // the last launch also writes the Q-values to coherent host memory and counts its workgroups there: grl_act polls the
     // counter instead of copying device -> host and synchronising the stream (GRL_TUNE act_poll=0 keeps that)
-    if (!dry && tune_int("act_poll", 1) != 0 &&
+    if (!dry && sw.get(Sw::act_poll) != 0 &&
         hipHostMalloc((void**)&q_act_host, (size_t)NA * D * nb * 4, hipHostMallocCoherent) == hipSuccess) {
       if (hipHostMalloc((void**)&act_done_host, 64, hipHostMallocCoherent) == hipSuccess) {
         *act_done_host = 0u;
@@ -798,10 +795,9 @@ int grl_ctx::plan_q() {
       memset(q_io_host, 0, io_floats * 4);
       float* io_obs = q_io_host; float* io_explore = io_obs + (size_t)NA * c.obs_dim; float* io_bins = io_explore + (size_t)NA * D;
       for (int i = 0; i < NA * D; ++i) io_explore[i] = -1.f;
-      q_act_fused = tune_int("q_act", 1) != 0 &&
+      q_act_fused = sw.get(Sw::q_act) != 0 &&
                     qa_shape_ok(c.obs_dim, D, nb, Lc, c.q_common, Lb, c.q_branch, Lv, c.q_value);
-      if (getenv("GRL_PLAN_DUMP"))
-        fprintf(stderr, "grl plan: q_act         epsilon-greedy act: %s\n",
+      plan_note("grl plan: q_act         epsilon-greedy act: %s\n",
                 q_act_fused ? "one launch (q_act.h)" : "launch list of the Q-value path + select kernel");
       if (q_act_fused) {
         QActArgs qa;

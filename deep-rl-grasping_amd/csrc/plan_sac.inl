@@ -72,7 +72,7 @@ int grl_ctx::plan_sac() {
   if (cnn) {
     x_obs = wk.f32((int64_t)B * img_elems);
     x_next = wk.f32((int64_t)B * img_elems);
-    x_obs_b = tune_int("gather_ride", 1) != 0 ? wk.f32((int64_t)B * img_elems) : nullptr;     // second image buffer ("gather_ride" below)
+    x_obs_b = sw.get(Sw::gather_ride) != 0 ? wk.f32((int64_t)B * img_elems) : nullptr;     // second image buffer ("gather_ride" below)
     // Layer-1 activations of the two TRAINED networks (and their gradients below) sit side by side, pixel stride 64:
     // pi in columns 0..31, values_fn in 32..63.  Both networks read the same observations, so conv1's weight
     // gradient becomes ONE product obs-patches^T x [dY_pi | dY_vf] (N = 64: full 64x64 tiles, the gathered patches
@@ -90,11 +90,8 @@ int grl_ctx::plan_sac() {
   alloc_head(hPI, B, 2, A); alloc_head(hVF, B, 1, 1); alloc_head(hQF1, B, 1, 1); alloc_head(hQF2, B, 1, 1);
   alloc_head(hTGT, B, 1, 1); alloc_head(hQF1PI, B, 1, 1); alloc_head(hQF2PI, B, 1, 1);
   pi_a = wk.f32((int64_t)B * A); logp = wk.f32(B); ent = wk.f32(B);
-  {
-    const char* nf = getenv("GRL_NO_FUSED_HEADS");
-    fused_heads = !(nf && nf[0] == '1') && A <= HT_MAXA && (hid[0] % 4) == 0;
-    for (int l = 0; l < L; ++l) fused_heads = fused_heads && hid[l] <= HT_MAXW;
-  }
+  fused_heads = !sw.get(Sw::GRL_NO_FUSED_HEADS) && A <= HT_MAXA && (hid[0] % 4) == 0;
+  for (int l = 0; l < L; ++l) fused_heads = fused_heads && hid[l] <= HT_MAXW;
   Ap = (int)rup(A, 4);
   if (fused_heads) {
     // output gradients packed / row-padded so that the weight-gradient GEMM can fetch them 16 bytes at a time
@@ -111,7 +108,7 @@ int grl_ctx::plan_sac() {
   }
   if (fused_heads) {
     {
-      l0_split = std::max(1, tune_int("l0_split", 3));       // reduction of the layer-0 GEMM (K = 513) cut into partial sums
+      l0_split = std::max(1, sw.get(Sw::l0_split));       // reduction of the layer-0 GEMM (K = 513) cut into partial sums
       IgemmProb probe = blank();
       probe.M = B; probe.N = hid[0]; probe.K = F;
       set_split(probe, l0_split);
@@ -173,7 +170,7 @@ int grl_ctx::plan_sac() {
     const int per_block = ga.vec4 ? 1024 : 256;
     // rows per workgroup of the grouped form (elem_kernels.h: gather_norm_rows_body); GRL_TUNE gather_rows=1 keeps one row each
     {
-      int rows = tune_int("gather_rows", c.replay_rgb_u8 ? GATHER_ROWS_U8 : GATHER_ROWS_F32);
+      int rows = sw.text(Sw::gather_rows) ? sw.get(Sw::gather_rows) : (c.replay_rgb_u8 ? GATHER_ROWS_U8 : GATHER_ROWS_F32);
       if (!ga.vec4 || !gather_rows_built(rows) || B % rows) rows = 1;
       ga.rows = rows;
       if (!gather_rows_built(ga.rows)) return fail(GRL_ERR_INVALID, "gather: no kernel for this many rows per workgroup");
@@ -203,10 +200,8 @@ int grl_ctx::plan_sac() {
     // conv1 -> conv2 -> conv3 of the three networks: ONE sample-local launch (conv_stack.h; a workgroup owns a sample of a
     // network and keeps the activation chain in LDS) for 1 / 2 / 4 image channels; GRL_TUNE conv_stack=0 or any other channel
     // count: one implicit-GEMM launch per layer.  The target network's layer-1 / layer-2 activations are not stored.
-    {
-      const char* nv2 = getenv("GRL_NO_V2");      // (the scalar-gather fallback test runs the per-layer launches on igemm_kernel)
-      conv_stack = conv_stack_ok(C_img) && hw == 64 && tune_int("conv_stack", 1) != 0 && !(nv2 && nv2[0] == '1');
-    }
+    // (GRL_NO_V2: the scalar-gather fallback test runs the per-layer launches on igemm_kernel)
+    conv_stack = conv_stack_ok(C_img) && hw == 64 && sw.get(Sw::conv_stack) != 0 && !sw.get(Sw::GRL_NO_V2);
     if (conv_stack) {
       ConvStackArgs ca;
       memset(&ca, 0, sizeof(ca));
@@ -284,10 +279,9 @@ int grl_ctx::plan_sac() {
     fa.h[6] = mk_head(m_qf2, hQF2PI, nullptr, u_l0[3], pi_a, A, A);
     fa.B = B; fa.A = A; fa.eps = eps_buf; fa.pi_a = pi_a; fa.logp = logp; fa.ent = ent;
     {
-      const char* nm = getenv("GRL_NO_HEADS_MFMA");
       // heads_mfma.h: any layers up to 64 wide with 2A <= 64, and the shipped wide shape -- layers [128, 128], A <= 8,
       // whole 16-row blocks (the general form at that width runs out of registers: those stay on heads_kernels.h)
-      heads_mfma = !(nm && nm[0] == '1') && 2 * A <= 64;
+      heads_mfma = !sw.get(Sw::GRL_NO_HEADS_MFMA) && 2 * A <= 64;
       bool narrow = true;
       for (int l = 0; l < L; ++l) narrow = narrow && hid[l] <= 64;
       bool wide_ok = L == 2 && hid[0] == 128 && hid[1] == 128 && A <= 8 && B % HT_RB == 0;
@@ -310,7 +304,7 @@ int grl_ctx::plan_sac() {
       ha.log_ent_coef = params + ent_off; ha.da_pi = da_pi; ha.dmu = dmu; ha.dls = dls; ha.ld_dm = ld_dm;
       ha.rew = rew; ha.done = done; ha.gamma = c.gamma;
       ha.d_out[1] = d_v; ha.d_out[2] = d_qf1; ha.d_out[3] = d_qf2; ha.d_out[4] = d_qf1pi; ha.ld_d = ld_d;
-      if (tune_int("heads_stamps", 0)) {     // in-kernel phase stamps (scripts/heads_stamps.py)
+      if (sw.get(Sw::heads_stamps)) {     // in-kernel phase stamps (scripts/heads_stamps.py)
         ha.stamps = (unsigned long long*)wk.take(4 * 32 * 8);
         zero_once.push_back({ha.stamps, 4 * 32 * 8});
         dbg["heads_stamps"] = {(const float*)ha.stamps, 4 * 32 * 2};
@@ -545,7 +539,7 @@ int grl_ctx::plan_sac() {
     // 20.3 us, but the dense weight gradients that ride in conv3_bwd's empty slots go back into the weight-gradient launch
     // (30.5 -> 35 us), and the conv3 half is bound by its kernel stream: 16 output pixels per sample reuse every 4 KB of
     // kernel for 16 MFMAs, where the batched exact-tap launch reuses it over 128 rows (profiles/r05_ab_conv_stack_bwd.txt)
-    conv_stack_bwd = conv_stack && tune_int("conv_stack_bwd", 0) != 0;
+    conv_stack_bwd = conv_stack && sw.get(Sw::conv_stack_bwd) != 0;
     if (!conv_stack_bwd) {
       int cfg3 = -1;
       const int t3 = planned_tiles(bwd_pr[1], 1, "conv3_bwd", &cfg3);
@@ -553,7 +547,7 @@ int grl_ctx::plan_sac() {
     }
     int wsplit[3] = {72, 12, 6};   // reduction splits of conv1..3 (GRL_TUNE wg_split=a/b/c overrides the model's choice)
     pick_wgrad_splits(cg, ft, 2, wsplit, rider_budget);
-    tune_int3("wg_split", wsplit);
+    sw.get3(Sw::wg_split, wsplit);
     {   // conv1 of both networks: one problem over the side-by-side gradient buffer, columns 32n.. -> net n
       IgemmProb p = conv_wgrad(x_obs, ft[0], cg[0], g1[0], nullptr, wsplit[0], 2);
       p.c = wk.f32(p.slab_stride * p.split);
@@ -781,7 +775,7 @@ int grl_ctx::plan_sac() {
     // Full updates (no gradient exchange in between): every trainable element is the sum of one slab
     // column, so Adam + Polyak are applied where the sum is formed -- one launch and one pass over the
     // gradient bucket less.  log_ent_coef, whose gradient comes from the loss workgroup, is applied there.
-    if (has_loss && tune_int("fused_adam", 1)) {
+    if (has_loss && sw.get(Sw::fused_adam)) {
       ops_grads_apply.assign(ops_grads.begin(), ops_grads.end() - 1);
       Op fo; fo.tag = "reduce_adam";
       fo.join = true;
@@ -798,7 +792,7 @@ int grl_ctx::plan_sac() {
       //   first : gather (does not touch the Adam step size) | body, heads[tick] | reduce + Adam + gather(t+1, counter + 1)
       //   middle:                                              body, heads[tick, counter += 1] | reduce + Adam + gather(t+1)
       //   last  :                                              body, heads[tick, counter += 1] | reduce + Adam (counter += 1)
-      if (heads_mfma && tune_int("gather_prefetch", 1)) {
+      if (heads_mfma && sw.get(Sw::gather_prefetch)) {
         GatherArgs g1 = pf_ga;
         g1.use_rng = 1; g1.adam_tick = 0; g1.quiet = 0; g1.rng_ahead = 0;
         const int gx = pf_gx;
@@ -853,7 +847,7 @@ int grl_ctx::plan_sac() {
               conv_alt.run = [cb, Ci](hipStream_t s) { launch_conv_stack_fwd(Ci, cb, s); };
               have_conv_alt = true;
             }
-          int ride_rows = tune_int("ride_rows", GATHER_RIDE_ROWS);
+          int ride_rows = sw.get(Sw::ride_rows);
           if (!gather_ride_rows_built(ride_rows)) ride_rows = GATHER_RIDE_ROWS;
           if (have_conv_alt) {
             GatherArgs gx2 = g2;                         // extras of update t+1, carried by update t's reduction launch
@@ -901,8 +895,7 @@ int grl_ctx::plan_sac() {
               }
             }
             ride.alternate = ride.short_call_graph = true;
-            if (getenv("GRL_PLAN_DUMP"))
-              fprintf(stderr, "grl plan: gather_ride  %d image-gather workgroups of the next update ride on the head launch (%d tiles per row, %d rows each); extras on the reduction launch\n",
+            plan_note("grl plan: gather_ride  %d image-gather workgroups of the next update ride on the head launch (%d tiles per row, %d rows each); extras on the reduction launch\n",
                       gx * (2 * B / ride_rows), gx, ride_rows);
           }
         }
@@ -933,7 +926,7 @@ int grl_ctx::plan_sac() {
       if (hipHostMalloc((void**)&act_io_host, (size_t)2 * NA * A * 4, 0) != hipSuccess) return fail(GRL_ERR_HIP, "hipHostMalloc failed");
       memset(act_io_host, 0, (size_t)2 * NA * A * 4);
       // (GRL_TUNE act_poll=0 keeps the stream synchronisation at the end of grl_act)
-      if (tune_int("act_poll", 1) != 0 && hipHostMalloc((void**)&act_done_host, 64, hipHostMallocCoherent) == hipSuccess) *act_done_host = 0u;
+      if (sw.get(Sw::act_poll) != 0 && hipHostMalloc((void**)&act_done_host, 64, hipHostMallocCoherent) == hipSuccess) *act_done_host = 0u;
       else act_done_host = nullptr;
     }
     a_eps = act_io_host;
@@ -961,7 +954,7 @@ int grl_ctx::plan_sac() {
     }
     // the policy head on the matrix cores (act_mfma.h) for the shapes it covers (GRL_TUNE act_mfma=0: the VALU kernel): the
     // extractor's dense layer then runs as a split-K GEMM whose partial sums the head kernel adds up while it stages its input
-    const bool mfma_heads = act_mfma_built() && am_shape_ok(F, L, hid, A) && tune_int("act_mfma", 1) != 0;
+    const bool mfma_heads = act_mfma_built() && am_shape_ok(F, L, hid, A) && sw.get(Sw::act_mfma) != 0;
     float* fc_parts = nullptr;
     int fc_split = 0;
     if (cnn) {

@@ -274,3 +274,11 @@ def test_auto_encoder_features_are_batched_under_grl_num_envs_gpu(tmp_path, monk
                 assert np.allclose(obs[k, :100], z1, atol=1e-6, rtol=1e-6) and obs[k, 100] == raw[k, 4096]
     finally:
         env.close()
+
+
+def test_plan_dump_names_known_and_unknown_switches_gpu(monkeypatch, capfd):
+    """tests/test_hostemu_switches.py::test_known_unknown_and_prefix_keys_dqn on the real library: the DQN handle at B = 16 under
+    GRL_TUNE=q_chain_late=0,bogus=1,fused_qapply=0 (creation only, no update)."""
+    import switch_util as su
+    su.check_mixed_string(lambda tune: su.dqn_dump(monkeypatch, capfd, tune), matrix_cores=True)
+
