@@ -260,6 +260,14 @@ int grl_set_running_stats(grl_handle h, const double* mean, const double* var, d
   return GRL_OK;
 }
 
+// DQN / BDQ handles keep their running statistics per process: on a connected handle the calls that update them are refused
+// BEFORE anything moves (the merge over the ranks, dp_norm_*, is the SAC handles')
+static int stats_update_refused(grl_handle h) {
+  if (h->dp_on && h->cfg.algo != GRL_ALGO_SAC)
+    return fail(GRL_ERR_STATE, "this DQN / BDQ handle is connected to a data-parallel exchange: merging its running statistics over the ranks is not implemented (keep them on the host)");
+  return GRL_OK;
+}
+
 // RunningMeanStd.update over `n` raw observations that are already on the device
 static int norm_update_from(grl_handle h, const float* dev_obs, int n) {
   const grl_config& c = h->cfg;
@@ -289,6 +297,7 @@ int grl_norm_update(grl_handle h, const float* obs, int n) {
   if (!h || !obs || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (!h->n_mean) return fail(GRL_ERR_STATE, "this handle keeps no running statistics");
   if (n > h->stg_n) return fail(GRL_ERR_INVALID, "more observations than one env step of act_batch environments");
+  if (int e = stats_update_refused(h)) return e;
   if (int e = copy_from_caller(h, h->n_stage, obs, (size_t)n * h->n_elems * 4)) return e;
   return norm_update_from(h, h->n_stage, n);
 }
@@ -406,10 +415,12 @@ static int ob_stage_release(grl_handle h) {
 
 int grl_observe(grl_handle h, const float* obs, int n, int flags) {
   if (!h || !obs || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
-  if (!h->ob_latest) return fail(GRL_ERR_STATE, "this handle keeps no observed observations (SAC handles do)");
+  if (!h->ob_latest) return fail(GRL_ERR_STATE, "this handle keeps no observed observations (SAC / DQN / BDQ handles do)");
   if (n > h->stg_n) return fail(GRL_ERR_INVALID, "more observations than one env step of act_batch environments");
   if (flags & ~GRL_OBSERVE_UPDATE_STATS) return fail(GRL_ERR_INVALID, "unknown flag bits");
   if ((flags & GRL_OBSERVE_UPDATE_STATS) && !h->n_mean) return fail(GRL_ERR_STATE, "this handle keeps no running statistics");
+  if (flags & GRL_OBSERVE_UPDATE_STATS)
+    if (int e = stats_update_refused(h)) return e;
   const size_t bytes = (size_t)n * h->ob_elems * 4;
   if (h->ob_n > 0)   // the previous step's observations become the `obs` side of the next replay rows
     HIPCHK(hipMemcpyAsync(h->ob_prev, h->ob_latest, (size_t)h->ob_n * h->ob_elems * 4, hipMemcpyDeviceToDevice, h->stream));
@@ -426,7 +437,7 @@ int grl_replay_add_observed(grl_handle h, const float* act, const float* rew, co
                             const int32_t* term_rows, const float* term_obs, int n_term) {
   if (!h || !act || !rew || !done || n < 1 || n_term < 0 || n_term > n) return fail(GRL_ERR_INVALID, "bad argument");
   if (n_term > 0 && (!term_rows || !term_obs)) return fail(GRL_ERR_INVALID, "terminal rows without their observations");
-  if (!h->ob_latest) return fail(GRL_ERR_STATE, "this handle keeps no observed observations (SAC handles do)");
+  if (!h->ob_latest) return fail(GRL_ERR_STATE, "this handle keeps no observed observations (SAC / DQN / BDQ handles do)");
   if (h->ob_n != n || h->ob_n_prev != n)
     return fail(GRL_ERR_STATE, "grl_replay_add_observed needs two consecutive grl_observe calls of n observations each");
   float* pin = nullptr;
@@ -658,11 +669,13 @@ static int act_wait(grl_handle h, unsigned wgs) {
 
 // grl_act(GRL_ACT_GREEDY) on a DQN / BDQ handle: bins [n, D] (plan_q.inl; q_act.h).  Observations, overrides and bins live
 // in coherent host memory the launch reads and writes: the previous call has waited for its launch, so they are free
-static int act_greedy(grl_handle h, const float* obs, int n, const float* explore, float* out) {
+// raw: VecNormalize applied on the device; observed: the rows grl_observe uploaded (nothing but the overrides moves)
+static int act_greedy(grl_handle h, const float* obs, int n, const float* explore, float* out, bool raw, bool observed) {
   if (!h->q_io_host) return fail(GRL_ERR_STATE, "this handle has no act path");
   const int D = h->qD, od = h->cfg.obs_dim;
   float* io_obs = h->q_io_host; float* io_explore = io_obs + (size_t)h->NA * od; float* io_bins = io_explore + (size_t)h->NA * D;
-  if (h->q_act_fused) memcpy(io_obs, obs, (size_t)n * od * 4);
+  if (observed) {}
+  else if (h->q_act_fused) memcpy(io_obs, obs, (size_t)n * od * 4);
   else {
     if (int e = pin_reserve(h, (size_t)n * od, 0)) return e;
     memcpy(h->pin_in, obs, (size_t)n * od * 4);
@@ -671,7 +684,8 @@ static int act_greedy(grl_handle h, const float* obs, int n, const float* explor
   if (explore) memcpy(io_explore, explore, (size_t)n * D * 4);
   else for (int i = 0; i < n * D; ++i) io_explore[i] = -1.f;
   __atomic_thread_fence(__ATOMIC_RELEASE);
-  if (int e = h->run_seq("act_greedy", {&h->ops_act_greedy})) return e;
+  const int v = (observed ? 2 : 0) | (raw ? 1 : 0);
+  if (int e = h->run_seq(v ? std::string("act_greedy") + char('0' + v) : std::string("act_greedy"), {&h->ops_act_greedy[v]})) return e;
   if (int e = act_wait(h, h->q_greedy_wgs)) return e;
   memcpy(out, io_bins, (size_t)n * D * 4);
   return GRL_OK;
@@ -685,13 +699,14 @@ int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps, 
   const bool observed = (flags & GRL_ACT_OBSERVED) != 0;  // act on what grl_observe uploaded: no second upload
   const bool q = h->cfg.algo != GRL_ALGO_SAC;   // DQN / BDQ: Q-values [n, D*bins]
   if (!observed && !obs) return fail(GRL_ERR_INVALID, "bad argument");
-  if (q && (raw || observed)) return fail(GRL_ERR_STATE, "the Q handles take normalised observations handed to grl_act");
+  if (q && (raw || observed) && !(flags & GRL_ACT_GREEDY))
+    return fail(GRL_ERR_STATE, "the Q-value form of grl_act takes normalised observations handed to it (GRL_ACT_GREEDY accepts GRL_ACT_RAW_OBS / GRL_ACT_OBSERVED)");
   if (raw && !h->n_mean) return fail(GRL_ERR_STATE, "this handle has no normalising act path");
   if (observed && h->ob_n != n) return fail(GRL_ERR_STATE, "n differs from the number of observations grl_observe holds");
   if (n > h->NA) return fail(GRL_ERR_INVALID, "n exceeds act_batch");
   if (flags & GRL_ACT_GREEDY) {
     if (!q) return fail(GRL_ERR_STATE, "GRL_ACT_GREEDY is defined for DQN / BDQ handles");
-    return act_greedy(h, obs, n, eps, out);
+    return act_greedy(h, obs, n, eps, out, raw, observed);
   }
   if (!q && !deterministic && !eps) return fail(GRL_ERR_INVALID, "stochastic action needs eps");
   const int64_t oe = (!q && h->cnn) ? (int64_t)h->hw * h->hw * h->cfg.obs_channels : h->cfg.obs_dim;

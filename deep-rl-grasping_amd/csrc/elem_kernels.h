@@ -168,6 +168,12 @@ __device__ __forceinline__ float norm_elem(float x, double mu, double sd, int no
   if (FAST255 || normalize) y = (float)clip_sym(((double)x - mu) / sd, clip);
   return FAST255 ? div255_exact(y) : scale_elem(y, scale_div);
 }
+// ... on an observation handed to the ACT path of a DQN / BDQ handle (q_act.h, act_ingest_kernel with nan_through): norm_elem,
+// with a NaN observation left a NaN, as np.clip leaves it (clip_sym alone turns it into +clip): the bins are then those the same
+// call gives for the host's VecNormalize.normalize_obs of that row
+__device__ __forceinline__ float norm_obs_act(float x, double mu, double sd, double clip) {
+  return x != x ? x : norm_elem(x, mu, sd, 1, clip, 1.f);
+}
 // The same value (normalize = 1) with the float64 division replaced by quot_refined on r = RN(1 / sd)
 template <bool FAST255 = false>
 __device__ __forceinline__ float norm_elem_rcp(float x, double mu, double sd, double r, double clip, float scale_div) {
@@ -540,6 +546,7 @@ struct ActIngestArgs {
   // the device (grl_norm_update) -- the same float64 expression as at replay-sample time (norm_elem)
   int normalize; double clip_obs;
   const double* mean; const double* stdv; const double* dmean; const double* dstd;
+  int nan_through;     // vector observations, normalize = 1: a NaN observation stays a NaN (norm_obs_act; the DQN / BDQ handles)
 };
 
 #ifndef GRL_ELEM_TYPES_ONLY
@@ -549,7 +556,8 @@ __global__ __launch_bounds__(256) void act_ingest_kernel(ActIngestArgs a) {
   if (a.vec_dim > 0) {
     if (e < a.vec_dim) {
       const float x = a.obs[(long)k * a.vec_dim + e];
-      a.x[(long)k * a.ldx + e] = a.normalize ? norm_elem(x, a.mean[e], a.stdv[e], 1, a.clip_obs, a.scale_div) : x;
+      a.x[(long)k * a.ldx + e] = !a.normalize ? x : a.nan_through ? norm_obs_act(x, a.mean[e], a.stdv[e], a.clip_obs)
+                                                                  : norm_elem(x, a.mean[e], a.stdv[e], 1, a.clip_obs, a.scale_div);
     }
     return;
   }

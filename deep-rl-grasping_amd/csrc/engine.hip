@@ -332,7 +332,7 @@ struct grl_ctx {
   float* n_stage = nullptr;
   int64_t n_elems = 0;
   int n_parity = 0;
-  std::vector<Op> ops_act_in[4];  // entry launch of the SAC act path: [(observed by grl_observe) << 1 | (raw: VecNormalize applied on the device)]
+  std::vector<Op> ops_act_in[4];  // entry launch of the SAC act path (DQN / BDQ: of the launch-list route of GRL_ACT_GREEDY): [(observed by grl_observe) << 1 | (raw: VecNormalize applied on the device)]
   // observations uploaded once per env step (grl_observe): newest, the one before, terminal rows, [act | rew | done | next_row]
   float *ob_latest = nullptr, *ob_prev = nullptr, *ob_term = nullptr;
   int64_t ob_elems = 0;
@@ -378,7 +378,7 @@ struct grl_ctx {
   float* q_io_host = nullptr;
   unsigned q_greedy_wgs = 0;
   bool q_act_fused = false;
-  std::vector<Op> ops_act_greedy;
+  std::vector<Op> ops_act_greedy[4];   // [(observed by grl_observe) << 1 | (raw: VecNormalize applied on the device)], as ops_act_in
   unsigned* act_done_host = nullptr;   // SAC: completion counter of the act path's last launch (coherent host memory), polled by grl_act
   unsigned act_done_wgs = 0, act_done_seen = 0;    // increments per call (0: no counter, synchronise the stream); expected value
   HeadAct ahPI;

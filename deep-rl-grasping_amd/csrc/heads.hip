@@ -94,9 +94,21 @@ void launch_q_bwd(const QFusedArgs& a, hipStream_t s) {
   if (a.bwd_tr) hipLaunchKernelGGL(q_bwd_trunk_kernel, trunk, dim3(256), 0, s, a);
 }
 unsigned q_act_workgroups(const QActArgs& a) { return (unsigned)((a.rows + HT_RB - 1) / HT_RB) * (unsigned)a.D; }
+#ifdef GRL_HOSTEMU
 void launch_q_act(const QActArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(q_act_kernel, dim3((a.rows + HT_RB - 1) / HT_RB, a.D), dim3(256), 0, s, a);
 }
+void launch_q_act_norm(const QActArgs& a, const QActNorm& nm, hipStream_t s) {
+  hipLaunchKernelGGL(q_act_norm_kernel, dim3((a.rows + HT_RB - 1) / HT_RB, a.D), dim3(256), 0, s, a, nm);
+}
+#else
+void launch_q_act(const QActArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL((q_act_kernel_t<>), dim3((a.rows + HT_RB - 1) / HT_RB, a.D), dim3(256), 0, s, a);
+}
+void launch_q_act_norm(const QActArgs& a, const QActNorm& nm, hipStream_t s) {
+  hipLaunchKernelGGL((q_act_kernel_t<QActNorm>), dim3((a.rows + HT_RB - 1) / HT_RB, a.D), dim3(256), 0, s, a, nm);
+}
+#endif
 void launch_q_select(const float* q, int rows, int D, int n, const float* explore, float* bins, unsigned* done, hipStream_t s) {
   hipLaunchKernelGGL(q_select_kernel, dim3((rows * D + 255) / 256), dim3(256), 0, s, q, rows, D, n, explore, bins, done);
 }

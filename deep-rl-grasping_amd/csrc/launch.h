@@ -53,6 +53,7 @@ void launch_act_heads_mfma(const ActHeadsArgs& a, hipStream_t s);     // one wor
 void launch_q_fwd(const QFusedArgs& a, hipStream_t s);
 void launch_q_bwd(const QFusedArgs& a, hipStream_t s);     // towers, then the trunk (when there is one)
 void launch_q_bwd_chain(const QChainArgs& a, hipStream_t s);     // the same with loss + weight gradients inside (q_chain.h)
+void launch_q_act_norm(const QActArgs& a, const QActNorm& nm, hipStream_t s);     // ... on raw observations: VecNormalize.normalize_obs applied as they are staged
 void launch_q_act(const QActArgs& a, hipStream_t s);     // grl_act(GRL_ACT_GREEDY): forward + dueling + arg-max + override, grid (rows / 16, D) (q_act.h)
 unsigned q_act_workgroups(const QActArgs& a);            // ... and the increments it leaves in the completion counter
 // the same result behind the launch list of the Q-value path: arg-max + override over q [rows, D, n]; ceil(rows * D / 256) workgroups

@@ -85,6 +85,12 @@ int grl_ctx::plan_q() {
   s_std = (double*)st.take((size_t)img_elems * 8);
   s_dmean = (double*)st.take(8); s_dstd = (double*)st.take(8);
   s_ret = (double*)st.take(8);
+  // VecNormalize running statistics on the device (grl_norm_update / grl_observe), as on SAC handles -- behind everything the
+  // arena held before them: every earlier offset stays where it was
+  n_elems = c.obs_dim;
+  n_count = (double*)st.take(16);
+  n_mean = (double*)st.take((size_t)n_elems * 8);
+  n_var = (double*)st.take((size_t)n_elems * 8);
   grads = gr.f32(n_train);
   const int64_t cap = c.replay_capacity;
   rp_obs = rp.f32(cap * img_elems); rp_next = rp.f32(cap * img_elems);
@@ -93,6 +99,11 @@ int grl_ctx::plan_q() {
   stg_n = std::max(NA, 64);
   stg_obs = wk.f32((int64_t)stg_n * c.obs_dim); stg_next = wk.f32((int64_t)stg_n * c.obs_dim);
   stg_act = wk.f32((int64_t)stg_n * A); stg_rew = wk.f32(stg_n); stg_done = wk.f32(stg_n);
+  // raw observations of one env step for grl_norm_update; the observed observations of grl_observe (newest, the one before,
+  // terminal rows), uploaded once each
+  n_stage = wk.f32((int64_t)stg_n * c.obs_dim);
+  ob_latest = wk.f32((int64_t)stg_n * c.obs_dim); ob_prev = wk.f32((int64_t)stg_n * c.obs_dim); ob_term = wk.f32((int64_t)stg_n * c.obs_dim);
+  ob_elems = c.obs_dim;
   idx_buf = (int64_t*)wk.take((size_t)B * 8);
   eps_buf = wk.f32(std::max(B, B * A));      // importance weights [B]
   for (int n = 0; n < 3; ++n) feat[n] = wk.f32((int64_t)B * ldf);
@@ -758,6 +769,19 @@ int grl_ctx::plan_q() {
       hipLaunchKernelGGL(act_ingest_kernel, dim3((elems + 255) / 256, ia.n), dim3(256), 0, s, ia);
     };
     ops_act.push_back(op);
+    {   // entry launch of the GRL_ACT_GREEDY launch list: [observed by grl_observe | handed to grl_act] x [raw | already normalised]
+      ActIngestArgs ian = ia;
+      ian.normalize = 1; ian.clip_obs = c.clip_obs; ian.mean = s_mean; ian.stdv = s_std; ian.nan_through = 1;
+      for (int v = 0; v < 4; ++v) {
+        ActIngestArgs iv = (v & 1) ? ian : ia;
+        if (v & 2) iv.obs = ob_latest;
+        Op oi; oi.tag = "act_ingest";
+        oi.run = [iv, elems](hipStream_t s) {
+          hipLaunchKernelGGL(act_ingest_kernel, dim3((elems + 255) / 256, iv.n), dim3(256), 0, s, iv);
+        };
+        ops_act_in[v].push_back(oi);
+      }
+    }
     std::vector<std::vector<IgemmProb>> sc1, sh1;
     std::vector<IgemmProb> so1;
     fwd_stages(Pon, aact, afeat, ldf, NA, sc1, sh1, so1);
@@ -815,15 +839,26 @@ int grl_ctx::plan_q() {
         }
         qa.explore = io_explore; qa.bins = io_bins; qa.done = dn;
         q_greedy_wgs = dn ? q_act_workgroups(qa) : 0u;
-        Op og; og.tag = "q_act";
-        og.run = [qa](hipStream_t s) { launch_q_act(qa, s); };
-        ops_act_greedy.push_back(og);
+        // [observed: the rows grl_observe left in ob_latest] x [raw: q_act_norm_kernel with the statistics the handle holds]
+        for (int v = 0; v < 4; ++v) {
+          QActArgs qv = qa;
+          if (v & 2) qv.obs = ob_latest;
+          const QActNorm nm{s_mean, s_std, (double)c.clip_obs};
+          Op og; og.tag = "q_act";
+          if (v & 1) og.run = [qv, nm](hipStream_t s) { launch_q_act_norm(qv, nm, s); };
+          else og.run = [qv](hipStream_t s) { launch_q_act(qv, s); };
+          ops_act_greedy[v].push_back(og);
+        }
       } else {
-        ops_act_greedy = ops_act;       // (dueling_kernel counts its workgroups too: both counts are expected)
+        // (dueling_kernel counts its workgroups too: both counts are expected)
         q_greedy_wgs = dn ? act_done_wgs + (unsigned)((rows * Dq + 255) / 256) : 0u;
         Op og; og.tag = "q_select";
         og.run = [qo, rows, Dq, nq, io_explore, io_bins, dn](hipStream_t s) { launch_q_select(qo, rows, Dq, nq, io_explore, io_bins, dn, s); };
-        ops_act_greedy.push_back(og);
+        for (int v = 0; v < 4; ++v) {     // the launch list of the Q-value path behind the entry launch of the variant
+          ops_act_greedy[v] = ops_act_in[v];
+          ops_act_greedy[v].insert(ops_act_greedy[v].end(), ops_act.begin() + 1, ops_act.end());
+          ops_act_greedy[v].push_back(og);
+        }
       }
     }
   }

@@ -18,6 +18,10 @@
 //     counts itself into the completion counter as dueling_kernel does: grl_act polls it.
 // Observations and overrides are read from coherent host memory directly (a few hundred bytes per row): the call is a host
 // memcpy, this launch and the poll -- no copy engine in front of it.
+// GRL_ACT_RAW_OBS / GRL_ACT_OBSERVED (VecNormalize statistics on the device, observations uploaded once by grl_observe): the
+// normalising instantiation reads RAW rows -- from the same host memory, or from the rows grl_observe left on the device -- and
+// applies VecNormalize.normalize_obs while it stages them (norm_obs_act, elem_kernels.h: the float64 expression of the gather);
+// its 2 x obs_dim doubles of statistics are requested with the observations, in front of every stage operand.
 // Shapes outside qa_shape_ok (widths or bins above 64, observations above 128 values, more than 7 branches, more than
 // GRL_MAX_LAYERS layers from observation to tower output) keep the launch list of the Q-value path and get q_select_kernel
 // behind dueling_kernel.  The k-order of a stage is the MFMA's: bins agree with the arg-max of the Q-value path / the oracle
@@ -43,6 +47,12 @@ struct QActArgs {      // passed by value: the kernel reaches every weight point
   const float* explore;            // [rows, D]: >= 0 overrides the greedy bin (coherent host memory)
   float* bins;                     // [rows, D] chosen bins as float32 (coherent host memory)
   unsigned* done;                  // completion counter, one increment per workgroup, or nullptr
+};
+// second argument of q_act_norm_kernel: `obs` holds RAW observations -- coherent host memory, or the rows grl_observe left on
+// the device -- and VecNormalize.normalize_obs is applied while they are staged
+struct QActNorm {
+  const double* mean; const double* stdv;   // [obs_dim] running mean and sqrt(var + eps) (s_mean / s_std of the handle)
+  double clip_obs;
 };
 
 static inline bool qa_shape_ok(int obs_dim, int D, int nb, int Lc, const int* common, int Lb, const int* branch, int Lv, const int* value) {
@@ -84,6 +94,7 @@ __global__ __launch_bounds__(256) void q_select_kernel(const float* qv, int rows
 
 #ifdef GRL_HOSTEMU
 #include "q_act_ref1.h"   // tests/hostemu: the emulation build only
+#include "q_act_ref2.h"
 #else
 
 struct __attribute__((aligned(16))) QaLds {
@@ -94,7 +105,17 @@ struct __attribute__((aligned(16))) QaLds {
   float v[HT_RB];
 };
 
-__global__ __launch_bounds__(256) void q_act_kernel(QActArgs a) {
+// NORM: the observations are raw.  The 2 x 8 float64 statistics of the thread's eight staged values are requested with the
+// observations, in front of every stage operand (one round trip for all of it), and norm_obs_act -- the expression of the gather
+// and of act_ingest_kernel -- runs on the values once the weight loads are in flight, before they are staged in LDS.
+// The kernel is a template over its trailing parameters -- none (q_act_kernel_t<>, the code the kernel always had), or one
+// QActNorm (q_act_kernel_t<QActNorm>; the emulation build names the two q_act_kernel / q_act_norm_kernel) -- so that the plain instantiation's argument list and body stay exactly what they were.
+__device__ __forceinline__ const QActNorm* qa_norm_of() { return nullptr; }
+__device__ __forceinline__ const QActNorm* qa_norm_of(const QActNorm& nm) { return &nm; }
+template <class... NM>
+__global__ __launch_bounds__(256) void q_act_kernel_t(QActArgs a, NM... nm_) {
+  constexpr bool NORM = sizeof...(NM) > 0;
+  const QActNorm* const nm = qa_norm_of(nm_...);
   __shared__ QaLds s;
   const int t = threadIdx.x, w = t >> 6, l = t & 63, c = l & 15, q = l >> 4;
   const int n = 16 * w + c, row0 = blockIdx.x * HT_RB, rows = a.rows, br = blockIdx.y, Lc = a.Lc, K0 = a.obs_dim, nb = a.nb;
@@ -108,6 +129,15 @@ __global__ __launch_bounds__(256) void q_act_kernel(QActArgs a) {
   for (int j = 0; j < 8; ++j) {
     const int col = (t & 15) + 16 * j;
     xv[j] = (xrow < rows && col < K0) ? QM_G(a.obs)[(long)xrow * a.ld_obs + col] : 0.f;
+  }
+  double xm[NORM ? 8 : 1], xs[NORM ? 8 : 1];
+  if (NORM) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int col = (t & 15) + 16 * j;
+      xm[j] = col < K0 ? nm->mean[col] : 0.0;
+      xs[j] = col < K0 ? nm->stdv[col] : 1.0;
+    }
   }
   float ex = -1.f;
   if (t < HT_RB && row0 + t < rows) ex = QM_G(a.explore)[(long)(row0 + t) * a.D + br];
@@ -145,6 +175,11 @@ __global__ __launch_bounds__(256) void q_act_kernel(QActArgs a) {
   qm_load_b(oa, TA.ow, ka, nb, nb, 1, n, q);
   qm_load_b(ov, TV.ow, kv, 1, 1, 1, n, q);
   const float boa = n < nb ? QM_G(TA.ob)[n] : 0.f, bov = n < 1 ? QM_G(TV.ob)[0] : 0.f;
+  if (NORM) {      // (rows beyond `rows` and columns beyond obs_dim stay the zeros they were loaded as)
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (xrow < rows && (t & 15) + 16 * j < K0) xv[j] = norm_obs_act(xv[j], xm[j], xs[j], nm->clip_obs);
+  }
   // ---- stage the observations (every element of both chunks is written: nothing to clear)
 #pragma unroll
   for (int j = 0; j < 8; ++j) s.x[j >> 2][xr][(t & 15) + 16 * (j & 3)] = xv[j];

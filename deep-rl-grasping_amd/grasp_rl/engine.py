@@ -344,7 +344,7 @@ class SacEngine:
         check(self.lib, self.lib.grl_allreduce_status(self.h, C.byref(n), C.byref(err)))
         return n.value
 
-    # ---- VecNormalize running statistics kept on the device (grl_norm_update; SAC handles)
+    # ---- VecNormalize running statistics kept on the device (grl_norm_update; SAC / DQN / BDQ handles)
     def norm_update(self, obs):
         """RunningMeanStd.update(obs) of one env step's raw observations [n, ...] on the device (stream-ordered)."""
         obs = np.ascontiguousarray(obs, dtype=np.float32)
@@ -679,9 +679,10 @@ class SacEngine:
 
 
 class QEngine(SacEngine):
-    """DQN / BDQ handle (``_capi.make_q_config``): same arenas and calls; the explicit-noise slot of
-    ``train`` / ``compute_grads`` carries prioritised-replay importance weights [n_steps, B] and
-    ``act`` returns dueling Q-values [n, branches, bins]."""
+    """DQN / BDQ handle (``_capi.make_q_config``): same arenas and calls -- ``norm_update``, ``set_running_stats``,
+    ``get_obs_stats``, ``observe`` / ``observe_rows`` and ``replay_add_observed`` (action columns: the bins [n, branches]) as
+    on a SAC handle; the explicit-noise slot of ``train`` / ``compute_grads`` carries prioritised-replay importance weights
+    [n_steps, B] and ``act`` returns dueling Q-values [n, branches, bins]."""
 
     def __init__(self, cfg, backend=None, lib_path=None, device="cuda:0"):
         super().__init__(cfg, backend=backend, lib_path=lib_path, device=device)
@@ -709,19 +710,25 @@ class QEngine(SacEngine):
     def act(self, obs, deterministic=True, eps=None):
         return self.q_values(obs).argmax(axis=2)
 
-    def act_bins(self, obs, explore=None):
+    def act_bins(self, obs, explore=None, raw=False, observed=False):
         """Epsilon-greedy bins [n, branches] (int64) of n <= act_batch observations: the arg-max of the dueling Q-values per
         branch, formed on the device (grl_act with GRL_ACT_GREEDY; one launch, csrc/q_act.h).  explore [n, branches]: an
         entry >= 0 replaces the greedy bin of that (row, branch), a negative one keeps it; None = all greedy.  The caller
-        draws the randomness."""
-        obs = np.ascontiguousarray(obs, dtype=np.float32)
-        n = obs.shape[0]
+        draws the randomness.  raw=True: `obs` are un-normalised observations, VecNormalize is applied on the device
+        (norm_update statistics).  observed=True: act on the observations the last `observe` uploaded (`obs` is then only
+        looked at for its length)."""
+        if observed:
+            n, po = int(obs if np.isscalar(obs) else len(obs)), None
+        else:
+            obs = np.ascontiguousarray(obs, dtype=np.float32)
+            n, po = obs.shape[0], obs.ctypes.data
         out = np.empty((n, self.D), np.float32)
         pe = None
         if explore is not None:
             explore = np.ascontiguousarray(explore, dtype=np.float32).reshape(n, self.D)
             pe = explore.ctypes.data
-        check(self.lib, self.lib.grl_act(self.h, obs.ctypes.data, n, _capi.ACT_GREEDY, pe, out.ctypes.data))
+        flags = _capi.ACT_GREEDY | (2 if raw else 0) | (4 if observed else 0)
+        check(self.lib, self.lib.grl_act(self.h, po, n, flags, pe, out.ctypes.data))
         return out.astype(np.int64)
 
     def update_target(self):

@@ -39,6 +39,7 @@ from . import policies as pol
 from . import save_util
 from . import spaces as sp
 from .callbacks import as_callback
+from .sac import resolve_device_norm
 from .checkpoint import CheckpointMixin
 from .vec_env import DummyVecEnv, VecEnv, expand_training_env, unwrap_vec_normalize
 
@@ -63,10 +64,19 @@ class _QModel(CheckpointMixin):
                  prioritized_replay_alpha=0.6, prioritized_replay_beta0=0.4, prioritized_replay_beta_iters=None,
                  prioritized_replay_eps=1e-6, param_noise=False, n_cpu_tf_sess=None, verbose=0, tensorboard_log=None,
                  _init_setup_model=True, policy_kwargs=None, full_tensorboard_log=False, seed=None, device="cuda:0",
-                 data_parallel=None, dp_exchange="ingraph"):
+                 data_parallel=None, dp_exchange="ingraph", device_norm=None):
         if param_noise:
             raise NotImplementedError("param_noise is not implemented")
         import os
+        # The VecNormalize observation statistics on the device while learning (grl_observe / grl_norm_update on the Q handle), as
+        # ``sb.SAC(device_norm=...)``: every observation crosses the bus once, the loop acts on the uploaded rows (GRL_ACT_OBSERVED),
+        # appends with ``replay_add_observed`` and pushes no statistics before an update.  True / False / "auto"; None reads
+        # GRL_DEVICE_NORM, and for these two classes an UNSET variable means off (SAC: auto).  True and "auto" go through
+        # ``sac.resolve_device_norm``; under data parallelism the host path is taken (the Q handles do not merge their device
+        # statistics over the ranks).
+        if device_norm is None:
+            device_norm = {"0": False, "1": True, "auto": "auto"}.get(os.environ.get("GRL_DEVICE_NORM", "0"), False)
+        self.device_norm = device_norm if device_norm == "auto" else bool(device_norm)
         if data_parallel is None:
             data_parallel = os.environ.get("GRL_DATA_PARALLEL") or None
         self.data_parallel, self.dp_exchange = data_parallel, dp_exchange
@@ -199,6 +209,7 @@ class _QModel(CheckpointMixin):
         per row (always_draw: also when eps is 0, as the learn loop does) and, only for a row that explores, its D bins: the
         stream the single-env loop consumes -- and the greedy rows are chosen on the device, one call per act_batch rows
         (engine.act_bins; skipped when every row explores)."""
+        raw, observed = getattr(self, "_act_device", (False, False))    # (the learn loop, statistics on the device)
         obs = np.asarray(obs, np.float32).reshape(-1, self.observation_space.shape[0])
         explore = np.full((obs.shape[0], self.D), -1, np.int64)
         if always_draw or eps > 0:
@@ -207,8 +218,11 @@ class _QModel(CheckpointMixin):
                     explore[i] = self._rng.integers(0, self.bins, self.D)
         if np.all(explore >= 0):
             return explore
+        if observed:      # the env wrapper uploaded these rows already (engine.observe): only the overrides and the bins move
+            return self.engine.act_bins(obs.shape[0], explore, raw=raw, observed=True)
         cap = self.engine.cfg.act_batch
-        return np.concatenate([self.engine.act_bins(obs[k:k + cap], explore[k:k + cap]) for k in range(0, obs.shape[0], cap)])
+        kw = {"raw": True} if raw else {}
+        return np.concatenate([self.engine.act_bins(obs[k:k + cap], explore[k:k + cap], **kw) for k in range(0, obs.shape[0], cap)])
 
     def _bins_to_env_action(self, bins):
         raise NotImplementedError
@@ -236,6 +250,8 @@ class _QModel(CheckpointMixin):
         rt, dp = self._dp_rt, self._dp
         W = 1 if rt is None else rt.world
         lead = rt is None or rt.rank == 0
+        # (decided from the callback the USER handed over; data parallel: the host path, whose moments are gathered over the ranks)
+        device_norm = rt is None and self.device_norm is not False and resolve_device_norm(self.device_norm, callback, None, None)
         callback = as_callback(callback if lead else None)      # data parallel: evaluation / checkpoints / logging on rank 0 only
         callback.init_callback(self)
         eng, vn = self.engine, self._vec_normalize_env
@@ -250,20 +266,26 @@ class _QModel(CheckpointMixin):
         self.episode_reward = np.zeros((self.n_envs,))
         writer = logger.SummaryWriter(self.tensorboard_log, tb_log_name or type(self).__name__) \
             if getattr(self, "tensorboard_log", None) else None
-        if resume is not None and vn is not None:
-            obs = vn.reset_restored(resume["ret"])      # this first observation is in the restored statistics already
-        else:
-            obs = self.env.reset()
-        obs_ = vn.get_original_obs() if vn is not None else obs
-        start = time.time()
-        callback.on_training_start(locals(), globals())
-        callback.on_rollout_start()
+        if device_norm and vn is not None and vn.norm_obs and eng.cfg.normalize in (1, 2):
+            # restored: the device holds the statistics of the saved run already, in both halves of their double buffer
+            vn.attach_device(eng, upload=resume is None)
         finished = False
         try:
+            if resume is not None and vn is not None:
+                obs = vn.reset_restored(resume["ret"])      # this first observation is in the restored statistics already
+            else:
+                obs = self.env.reset()
+            obs_ = vn.get_original_obs() if vn is not None else obs
+            start = time.time()
+            callback.on_training_start(locals(), globals())
+            callback.on_rollout_start()
             self._learn_loop(total_timesteps, callback, log_interval, rt, dp, W, lead, eng, vn, obs, obs_, beta_schedule,
                              episode_rewards, episode_successes, start)
             finished = True
         finally:
+            self._act_device = (False, False)
+            if vn is not None and vn._dev is not None:     # whatever ended the loop: the wrapper carries the statistics again
+                vn.detach_device()
             if rt is not None and vn is not None:          # the collective hook must not outlive the collective loop
                 for rms in (vn.obs_rms, vn.ret_rms):
                     rms.__dict__.pop("gather", None)
@@ -284,9 +306,13 @@ class _QModel(CheckpointMixin):
         # MORE steps from where the counter stands; the schedules keep reading the counter itself
         end = self.num_timesteps + total_timesteps
         N = self.n_envs
+        serial = vn.observed_serial if vn is not None else None     # engine.observe ticket of `obs` (device-side statistics)
         while self.num_timesteps < end:
             eps = self.exploration.value(self.num_timesteps)
+            raw_obs = vn is not None and vn.hands_out_raw_observations     # (a callback may toggle vn.training)
+            self._act_device = (raw_obs, raw_obs and serial is not None)
             bins = self._act_bins(obs, eps, always_draw=True)         # [N, D]: one device call for all rows
+            self._act_device = (False, False)
             env_action = np.asarray([self._bins_to_env_action(b) for b in bins])
             new_obs, rew, done, info = self.env.step(env_action)
             before = self.num_timesteps
@@ -297,12 +323,18 @@ class _QModel(CheckpointMixin):
                 stop = rt.any(stop)                 # rank 0's callbacks decide for every replica; no rank runs ahead
             if stop:
                 break
-            new_obs_, rew_ = (vn.get_original_obs(), vn.get_original_reward()) if vn is not None else (new_obs, rew)
+            new_serial = vn.observed_serial if vn is not None else None
             # N rows in env order.  A finished row carries done = 1, which masks the bootstrap term: the auto-reset observation
             # it holds as its next observation is never used
-            eng.replay_add(np.asarray(obs_, np.float32), bins.astype(np.float32).reshape(N, -1),
-                           np.asarray(rew_, np.float32), np.asarray(new_obs_, np.float32), np.asarray(done, np.float32))
-            obs, obs_ = new_obs, new_obs_
+            if serial is not None and new_serial == serial + 1:
+                # both sides of the transitions are on the device already (uploaded once each by the wrapper)
+                new_obs_, rew_ = vn.old_obs, vn.old_rews
+                eng.replay_add_observed(bins.astype(np.float32).reshape(N, -1), rew_, done)
+            else:
+                new_obs_, rew_ = (vn.get_original_obs(), vn.get_original_reward()) if vn is not None else (new_obs, rew)
+                eng.replay_add(np.asarray(obs_, np.float32), bins.astype(np.float32).reshape(N, -1),
+                               np.asarray(rew_, np.float32), np.asarray(new_obs_, np.float32), np.asarray(done, np.float32))
+            obs, obs_, serial = new_obs, new_obs_, new_serial
             self.episode_reward += np.asarray(rew_, np.float64).reshape(N)
             for i in range(N):
                 if done[i] and isinstance(info[i], dict) and info[i].get("is_success") is not None:
@@ -317,7 +349,10 @@ class _QModel(CheckpointMixin):
             if n_upd > 0:
                 callback.on_rollout_end()
                 if vn is not None and eng.cfg.normalize:
-                    eng.set_obs_stats(vn.obs_rms.mean, vn.obs_rms.var, float(vn.ret_rms.var))
+                    if vn.hands_out_raw_observations:     # observation statistics live on the device: only the return variance moves
+                        eng.set_ret_var(float(vn.ret_rms.var))
+                    else:
+                        eng.set_obs_stats(vn.obs_rms.mean, vn.obs_rms.var, float(vn.ret_rms.var))
                 if callable(self.learning_rate):    # stable-baselines evaluates the schedule per update: lr(1 - step / total)
                     eng.set_learning_rate(self.learning_rate(1.0 - (self.num_timesteps - 1) / max(1, self._schedule_total)))
                 if self.prioritized_replay:

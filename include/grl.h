@@ -164,7 +164,7 @@ int grl_set_learning_rate(grl_handle h, float lr);
 /* VecNormalize statistics (host float64, HWC layout of the observation space or [obs_dim]);
    obs_var/ret_var are variances, epsilon is added inside.  Copied before returning. */
 int grl_set_obs_stats(grl_handle h, const double* obs_mean, const double* obs_var, double ret_var);
-/* The same statistics maintained ON THE DEVICE (SAC handles).  VecNormalize.step_wait -> obs_rms.update(obs)
+/* The same statistics maintained ON THE DEVICE (SAC, DQN and BDQ handles).  VecNormalize.step_wait -> obs_rms.update(obs)
    (stable-baselines RunningMeanStd.update / update_from_moments, wrapper created at sb_helper.py:117-119): merges the
    batch moments of the n raw observations of one env step (HOST pointer, env layout [n, 64, 64, C+1] or [n, obs_dim],
    n <= max(act_batch, 64)) into the running mean / variance / count in device memory -- float32 batch moments like
@@ -175,7 +175,9 @@ int grl_set_obs_stats(grl_handle h, const double* obs_mean, const double* obs_va
    mean / var [env layout] and count out for pickling.
    On a handle connected for data parallelism (grl_allreduce_connect) grl_norm_update merges the batch moments of ALL
    ranks, in rank order, into every replica (csrc/dp_kernels.h) -- the arithmetic of
-   grasp_rl.parallel.share_running_stats on the host; all ranks must call it the same number of times. */
+   grasp_rl.parallel.share_running_stats on the host; all ranks must call it the same number of times.  That merge is the
+   SAC handles': on a connected DQN / BDQ handle grl_norm_update and grl_observe(GRL_OBSERVE_UPDATE_STATS) are GRL_ERR_STATE
+   before anything moves (keep the statistics on the host there). */
 int grl_norm_update(grl_handle h, const float* obs, int n);
 int grl_set_running_stats(grl_handle h, const double* obs_mean, const double* obs_var, double count);
 int grl_set_ret_var(grl_handle h, double ret_var);
@@ -277,20 +279,24 @@ int grl_get_metrics(grl_handle h, grl_metrics* out);
 /* host: actor forward for n <= act_batch observations (env layout, host ptr); `flags` is a mask of the bits below
    (any other bit: GRL_ERR_INVALID).
      GRL_ACT_DETERMINISTIC  tanh(mu) instead of a sample;
-     GRL_ACT_RAW_OBS        (SAC handles) the observations are RAW and VecNormalize.normalize_obs is applied on the device
+     GRL_ACT_RAW_OBS        (SAC handles; DQN / BDQ handles with GRL_ACT_GREEDY) the observations are RAW and VecNormalize.normalize_obs is applied on the device
                             with the statistics grl_norm_update / grl_observe maintain (otherwise they are already
-                            normalised, as VecNormalize hands them out);
-     GRL_ACT_OBSERVED       (SAC handles) act on the n observations the last grl_observe uploaded; `obs` is ignored
-                            (may be NULL) and nothing but eps and the actions crosses the bus.
+                            normalised, as VecNormalize hands them out).  On a DQN / BDQ handle a NaN observation stays a
+                            NaN, as np.clip leaves it;
+     GRL_ACT_OBSERVED       (SAC handles; DQN / BDQ handles with GRL_ACT_GREEDY) act on the n observations the last grl_observe uploaded; `obs` is ignored
+                            (may be NULL) and nothing but eps and the actions crosses the bus; GRL_ERR_STATE when n differs
+                            from the rows held.
    eps_or_null: [n,act_dim] noise for stochastic actions (host).  Synchronises the stream.
    DQN / BDQ handles: out receives the dueling Q-values [n, q_branches*q_bins] (normalised observations only:
-   GRL_ACT_RAW_OBS / GRL_ACT_OBSERVED are GRL_ERR_STATE on them), or with
+   GRL_ACT_RAW_OBS / GRL_ACT_OBSERVED are GRL_ERR_STATE in this form), or with
      GRL_ACT_GREEDY         (DQN / BDQ handles; GRL_ERR_STATE on the others) the epsilon-greedy ACTION of every row: out
                             receives the bins [n, q_branches] as float32 -- the arg-max of the Q-values over the bins of each
                             branch (lowest index among equal values, as np.argmax), formed on the device -- and eps_or_null
                             is the exploration table explore[n, q_branches] (host) or NULL (all greedy): an entry >= 0
                             replaces the greedy bin of that (row, branch) and comes back verbatim, a negative entry keeps
-                            it.  The caller draws the randomness.  One launch for networks whose widths and bins fit 64,
+                            it.  The caller draws the randomness.  Combines with GRL_ACT_RAW_OBS and GRL_ACT_OBSERVED, each
+                            with the meaning above (the one-launch kernel then normalises the rows while it stages them).
+                            One launch for networks whose widths and bins fit 64,
                             observations up to 128 values and up to 7 branches (csrc/q_act.h); other shapes run the launches
                             of the Q-value path plus a select launch.  Stands behind stable-baselines DQN.learn's
                             `self.act(...)` as entered from sb_helper.py:159-177 and `model.predict` in utils.py:71. */
@@ -301,7 +307,8 @@ int grl_get_metrics(grl_handle h, grl_metrics* out);
 int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps_or_null,
             float* out_actions);
 
-/* One env step's observations uploaded ONCE (SAC handles).  In SAC.learn the observations an env step returns are used
+/* One env step's observations uploaded ONCE (SAC, DQN and BDQ handles; on the latter two `act` holds the chosen bins
+   [n, q_branches] as float32).  In SAC.learn the observations an env step returns are used
    three times -- RunningMeanStd.update (VecNormalize.step_wait), the next model.predict-style action, and two
    replay_buffer.add rows (new_obs of this step, obs of the next; stable-baselines' learn loop entered at
    sb_helper.py:175-177).  grl_observe copies obs [n, env layout] (host ptr, n <= max(act_batch, 64); copied before the
