@@ -22,15 +22,19 @@ static const struct { const char* name; size_t off, size; } k_cfg_fields[] = {
   GRL_CFG_FIELD(q_n_branch), GRL_CFG_FIELD(q_branch), GRL_CFG_FIELD(q_n_value), GRL_CFG_FIELD(q_value), GRL_CFG_FIELD(q_huber),
   GRL_CFG_FIELD(q_double), GRL_CFG_FIELD(q_grad_clip), GRL_CFG_FIELD(q_trunk_scale), GRL_CFG_FIELD(q_per), GRL_CFG_FIELD(q_per_alpha),
   GRL_CFG_FIELD(q_per_eps), GRL_CFG_FIELD(replay_rgb_u8), GRL_CFG_FIELD(q_per_stratified), GRL_CFG_FIELD(q_per_alpha64),
-  GRL_CFG_FIELD(q_loss_sum_branches),
+  GRL_CFG_FIELD(q_loss_sum_branches), GRL_CFG_FIELD(q_layer_norm),
 };
 #undef GRL_CFG_FIELD
 
-// FNV-1a over the bytes of every field in field order (padding between fields never enters)
+// FNV-1a over the bytes of every field in field order (padding between fields never enters).  q_layer_norm, appended after
+// blobs of this layout existed, enters only when set: a blob written before the field existed hashes as it did then (its
+// configuration bytes hold zeros there) and is still accepted by a handle without layer normalisation.
 static uint64_t cfg_hash(const grl_config& c) {
   uint64_t hsh = 0xcbf29ce484222325ull;
-  for (const auto& f : k_cfg_fields)
+  for (const auto& f : k_cfg_fields) {
+    if (f.off == offsetof(grl_config, q_layer_norm) && c.q_layer_norm == 0) continue;
     for (size_t k = 0; k < f.size; ++k) hsh = (hsh ^ ((const uint8_t*)&c)[f.off + k]) * 0x100000001b3ull;
+  }
   return hsh;
 }
 

@@ -38,6 +38,7 @@
 #include "per_kernels.h"
 #include "ae_kernels.h"
 #include "q_apply_kernels.h"
+#include "ln_kernels.h"
 #include "dp_kernels.h"
 
 namespace grl {

@@ -9,6 +9,10 @@ struct QNetP {
   std::vector<int64_t> cw, cb;                    // trunk
   std::vector<std::vector<int64_t>> bw, bb;       // [branch][hidden..., out]
   std::vector<int64_t> vw, vb;                    // value tower [hidden..., out]
+  // layer normalisation (grl_config.q_layer_norm): beta / gamma of every HIDDEN layer, empty otherwise
+  std::vector<int64_t> cbeta, cgam;
+  std::vector<std::vector<int64_t>> bbeta, bgam;
+  std::vector<int64_t> vbeta, vgam;
 };
 struct QNetAct {
   std::vector<float*> zc;
@@ -16,6 +20,11 @@ struct QNetAct {
   float* adv = nullptr;
   std::vector<float*> zv;
   float* v = nullptr;
+  // layer normalisation, the pass that is differentiated only: pre-activations kept beside the activations, and the rows'
+  // (mean, rstd) -- every other pass normalises in place (ln_kernels.h)
+  std::vector<float*> uc, sc;
+  std::vector<std::vector<float*>> ub, sb;
+  std::vector<float*> uv, sv;
 };
 }  // namespace
 
@@ -35,6 +44,10 @@ int grl_ctx::plan_q() {
   img_elems = c.obs_dim; F = c.obs_dim; Fc = 0; ldf = (int)rup(F, 4); C_img = 0; hw = c.img_hw;
   const std::string scope = c.algo == GRL_ALGO_DQN ? "deepq" : "bdq";
   auto fcname = [](int k) { return k == 0 ? std::string("fully_connected") : "fully_connected_" + std::to_string(k); };
+  // layer normalisation in front of every hidden layer's ReLU: tf.contrib.layers.layer_norm creates `LayerNorm[_k]/beta:0`, then
+  // `/gamma:0`, inside the scope that holds the layer, behind the layer's own variables (no shipped model pins it)
+  const bool ln = c.q_layer_norm != 0;
+  auto lnname = [](int k) { return k == 0 ? std::string("LayerNorm") : "LayerNorm_" + std::to_string(k); };
 
   // ---------------- layout (TF creation order of the shipped zips)
   add_var(scope + "/eps:0", {}, false);   // exploration epsilon: stored with the model, never trained
@@ -43,15 +56,24 @@ int grl_ctx::plan_q() {
     for (int k = 0; k < Lc; ++k) {
       P.cw.push_back(add_var(pre + "/common_net/" + fcname(k) + "/weights:0", {d, c.q_common[k]}, tr));
       P.cb.push_back(add_var(pre + "/common_net/" + fcname(k) + "/biases:0", {c.q_common[k]}, tr));
+      if (ln) {
+        P.cbeta.push_back(add_var(pre + "/common_net/" + lnname(k) + "/beta:0", {c.q_common[k]}, tr));
+        P.cgam.push_back(add_var(pre + "/common_net/" + lnname(k) + "/gamma:0", {c.q_common[k]}, tr));
+      }
       d = c.q_common[k];
     }
-    int k = 0;
-    P.bw.resize(D); P.bb.resize(D);
+    int k = 0, kn = 0;
+    P.bw.resize(D); P.bb.resize(D); P.bbeta.resize(D); P.bgam.resize(D);
     for (int br = 0; br < D; ++br) {
       int dd = d;
       for (int l = 0; l < Lb; ++l, ++k) {
         P.bw[br].push_back(add_var(pre + "/action_value/" + fcname(k) + "/weights:0", {dd, c.q_branch[l]}, tr));
         P.bb[br].push_back(add_var(pre + "/action_value/" + fcname(k) + "/biases:0", {c.q_branch[l]}, tr));
+        if (ln) {     // (the branches share the scope: the LayerNorm count runs on over them, as the fully_connected count does)
+          P.bbeta[br].push_back(add_var(pre + "/action_value/" + lnname(kn) + "/beta:0", {c.q_branch[l]}, tr));
+          P.bgam[br].push_back(add_var(pre + "/action_value/" + lnname(kn) + "/gamma:0", {c.q_branch[l]}, tr));
+          ++kn;
+        }
         dd = c.q_branch[l];
       }
       P.bw[br].push_back(add_var(pre + "/action_value/" + fcname(k) + "/weights:0", {dd, nb}, tr));
@@ -62,6 +84,10 @@ int grl_ctx::plan_q() {
     for (int l = 0; l < Lv; ++l) {
       P.vw.push_back(add_var(pre + "/state_value/" + fcname(l) + "/weights:0", {dd, c.q_value[l]}, tr));
       P.vb.push_back(add_var(pre + "/state_value/" + fcname(l) + "/biases:0", {c.q_value[l]}, tr));
+      if (ln) {
+        P.vbeta.push_back(add_var(pre + "/state_value/" + lnname(l) + "/beta:0", {c.q_value[l]}, tr));
+        P.vgam.push_back(add_var(pre + "/state_value/" + lnname(l) + "/gamma:0", {c.q_value[l]}, tr));
+      }
       dd = c.q_value[l];
     }
     P.vw.push_back(add_var(pre + "/state_value/" + fcname(Lv) + "/weights:0", {dd, 1}, tr));
@@ -120,6 +146,14 @@ int grl_ctx::plan_q() {
   };
   QNetAct net[3], gact, aact;           // online(s), online(s'), target(s'); gradients; act path
   for (int n = 0; n < 3; ++n) alloc_net(net[n], B);
+  if (ln) {     // the differentiated pass keeps its pre-activations and the rows' statistics
+    QNetAct& a = net[0];
+    for (int k = 0; k < Lc; ++k) { a.uc.push_back(wk.f32((int64_t)B * c.q_common[k])); a.sc.push_back(wk.f32(2 * (int64_t)B)); }
+    a.ub.resize(D); a.sb.resize(D);
+    for (int br = 0; br < D; ++br)
+      for (int l = 0; l < Lb; ++l) { a.ub[br].push_back(wk.f32((int64_t)B * c.q_branch[l])); a.sb[br].push_back(wk.f32(2 * (int64_t)B)); }
+    for (int l = 0; l < Lv; ++l) { a.uv.push_back(wk.f32((int64_t)B * c.q_value[l])); a.sv.push_back(wk.f32(2 * (int64_t)B)); }
+  }
   alloc_net(gact, B);                   // same shapes: gradient w.r.t. each pre-activation ...
   // ... except the output gradients, which the weight-gradient GEMM fetches 16 bytes at a time: every branch's bins start
   // 16-byte aligned (nbp floats apart), the value gradient has a row stride of 4; the padding stays zero
@@ -134,23 +168,38 @@ int grl_ctx::plan_q() {
   const int hdim = Lc > 0 ? c.q_common[Lc - 1] : c.obs_dim;
 
   // forward stages of one net
+  // (layer normalisation: the dense launches leave the pre-activations -- beside the activations where the pass keeps them,
+  //  else in their place -- and ln_common / ln_hidden list the tensors the ln_relu_fwd launch behind each level turns into them)
+  auto ln_fwd = [&](float* u, float* z, int64_t beta, int64_t gam, float* stat, int H) {
+    LnDesc d;
+    memset(&d, 0, sizeof(d));
+    d.u = u; d.z = z; d.gamma = P + gam; d.beta = P + beta; d.stat = stat; d.H = H;
+    return d;
+  };
+  const int hid_act = ln ? ACT_NONE : ACT_RELU;
   auto fwd_stages = [&](const QNetP& W, const QNetAct& a, const float* x, int ldx, int rows,
                         std::vector<std::vector<IgemmProb>>& st_common, std::vector<std::vector<IgemmProb>>& st_hidden,
-                        std::vector<IgemmProb>& st_out) {
+                        std::vector<IgemmProb>& st_out, std::vector<std::vector<LnDesc>>& ln_common,
+                        std::vector<std::vector<LnDesc>>& ln_hidden) {
+    const bool keep = !a.uv.empty();
     const float* in = x; int ldin = ldx, kin = c.obs_dim;
-    st_common.resize(Lc);
+    st_common.resize(Lc); ln_common.resize(Lc);
     for (int k = 0; k < Lc; ++k) {
+      float* pre = keep ? a.uc[k] : a.zc[k];
       st_common[k].push_back(dense_fwd(in, ldin, kin, nullptr, 0, 0, rows, P + W.cw[k], c.q_common[k], P + W.cb[k],
-                                       a.zc[k], c.q_common[k], ACT_RELU));
+                                       pre, c.q_common[k], hid_act));
+      if (ln) ln_common[k].push_back(ln_fwd(pre, a.zc[k], W.cbeta[k], W.cgam[k], keep ? a.sc[k] : nullptr, c.q_common[k]));
       in = a.zc[k]; ldin = kin = c.q_common[k];
     }
     const float* h = in; const int ldh = ldin;
-    st_hidden.resize(std::max(Lb, Lv));
+    st_hidden.resize(std::max(Lb, Lv)); ln_hidden.resize(std::max(Lb, Lv));
     for (int br = 0; br < D; ++br) {
       const float* z = h; int ldz = ldh, kz = hdim;
       for (int l = 0; l < Lb; ++l) {
+        float* pre = keep ? a.ub[br][l] : a.zb[br][l];
         st_hidden[l].push_back(dense_fwd(z, ldz, kz, nullptr, 0, 0, rows, P + W.bw[br][l], c.q_branch[l],
-                                         P + W.bb[br][l], a.zb[br][l], c.q_branch[l], ACT_RELU));
+                                         P + W.bb[br][l], pre, c.q_branch[l], hid_act));
+        if (ln) ln_hidden[l].push_back(ln_fwd(pre, a.zb[br][l], W.bbeta[br][l], W.bgam[br][l], keep ? a.sb[br][l] : nullptr, c.q_branch[l]));
         z = a.zb[br][l]; ldz = kz = c.q_branch[l];
       }
       st_out.push_back(dense_fwd(z, ldz, kz, nullptr, 0, 0, rows, P + W.bw[br][Lb], nb, P + W.bb[br][Lb],
@@ -158,8 +207,10 @@ int grl_ctx::plan_q() {
     }
     const float* z = h; int ldz = ldh, kz = hdim;
     for (int l = 0; l < Lv; ++l) {
+      float* pre = keep ? a.uv[l] : a.zv[l];
       st_hidden[l].push_back(dense_fwd(z, ldz, kz, nullptr, 0, 0, rows, P + W.vw[l], c.q_value[l], P + W.vb[l],
-                                       a.zv[l], c.q_value[l], ACT_RELU));
+                                       pre, c.q_value[l], hid_act));
+      if (ln) ln_hidden[l].push_back(ln_fwd(pre, a.zv[l], W.vbeta[l], W.vgam[l], keep ? a.sv[l] : nullptr, c.q_value[l]));
       z = a.zv[l]; ldz = kz = c.q_value[l];
     }
     st_out.push_back(dense_fwd(z, ldz, kz, nullptr, 0, 0, rows, P + W.vw[Lv], 1, P + W.vb[Lv], a.v, 1, ACT_NONE));
@@ -249,10 +300,25 @@ int grl_ctx::plan_q() {
     };
     ops_grads.push_back(op);
   }
+  // one ln_relu_fwd / ln_relu_bwd launch over all tensors of a layer level (ln_kernels.h)
+  int ln_tensors = 0;
+  auto add_ln = [&](std::vector<Op>& ops, const char* tag, bool bwd, const std::vector<LnDesc>& descs, int rows) {
+    if (descs.empty()) return;
+    int npl = 1;
+    for (auto& d : descs) npl = std::max(npl, ln_npl(d.H));
+    const LnDesc* dd = upload_vec(wk, descs);
+    const int nd = (int)descs.size();
+    Op op; op.tag = tag;
+    if (bwd) op.run = [dd, nd, rows, npl](hipStream_t s) { launch_ln_relu_bwd(dd, nd, rows, npl, s); };
+    else op.run = [dd, nd, rows, npl](hipStream_t s) { launch_ln_relu_fwd(dd, nd, rows, npl, s); };
+    ops.push_back(op);
+    ln_tensors += nd;
+  };
   // ---- row-local chains (q_kernels.h) when every width fits the head primitives; else one GEMM launch per layer
+  // (layer normalisation: always the per-layer launches -- the chains and the one-launch act do not normalise)
   bool fused_q = false;
   {
-    bool ok = sw.get(Sw::fused_q) && nb <= 64 && Lc + std::max(Lb, Lv) <= GRL_MAX_LAYERS;
+    bool ok = !ln && sw.get(Sw::fused_q) && nb <= 64 && Lc + std::max(Lb, Lv) <= GRL_MAX_LAYERS;
     for (int k = 0; k < Lc; ++k) ok = ok && c.q_common[k] <= HT_MAXW;
     for (int l = 0; l < Lb; ++l) ok = ok && c.q_branch[l] <= HT_MAXW;
     for (int l = 0; l < Lv; ++l) ok = ok && c.q_value[l] <= HT_MAXW;
@@ -396,14 +462,21 @@ int grl_ctx::plan_q() {
   } else {
     std::vector<std::vector<IgemmProb>> sc_[3], sh_[3];
     std::vector<IgemmProb> so_[3];
-    fwd_stages(Pon, net[0], feat[0], ldf, B, sc_[0], sh_[0], so_[0]);
-    fwd_stages(Pon, net[1], feat[2], ldf, B, sc_[1], sh_[1], so_[1]);
-    fwd_stages(Ptg, net[2], feat[2], ldf, B, sc_[2], sh_[2], so_[2]);
-    auto merged = [&](std::vector<IgemmProb> a, const std::vector<IgemmProb>& b, const std::vector<IgemmProb>& d) {
+    std::vector<std::vector<LnDesc>> lc_[3], lh_[3];
+    fwd_stages(Pon, net[0], feat[0], ldf, B, sc_[0], sh_[0], so_[0], lc_[0], lh_[0]);
+    fwd_stages(Pon, net[1], feat[2], ldf, B, sc_[1], sh_[1], so_[1], lc_[1], lh_[1]);
+    fwd_stages(Ptg, net[2], feat[2], ldf, B, sc_[2], sh_[2], so_[2], lc_[2], lh_[2]);
+    auto merged = [&](auto a, const auto& b, const auto& d) {
       a.insert(a.end(), b.begin(), b.end()); a.insert(a.end(), d.begin(), d.end()); return a;
     };
-    for (int k = 0; k < Lc; ++k) add_launch(ops_grads, "q_fwd", 0, merged(sc_[0][k], sc_[1][k], sc_[2][k]));
-    for (size_t l = 0; l < sh_[0].size(); ++l) add_launch(ops_grads, "q_fwd", 0, merged(sh_[0][l], sh_[1][l], sh_[2][l]));
+    for (int k = 0; k < Lc; ++k) {
+      add_launch(ops_grads, "q_fwd", 0, merged(sc_[0][k], sc_[1][k], sc_[2][k]));
+      add_ln(ops_grads, "q_ln_fwd", false, merged(lc_[0][k], lc_[1][k], lc_[2][k]), B);
+    }
+    for (size_t l = 0; l < sh_[0].size(); ++l) {
+      add_launch(ops_grads, "q_fwd", 0, merged(sh_[0][l], sh_[1][l], sh_[2][l]));
+      add_ln(ops_grads, "q_ln_fwd", false, merged(lh_[0][l], lh_[1][l], lh_[2][l]), B);
+    }
     add_launch(ops_grads, "q_fwd", 0, merged(so_[0], so_[1], so_[2]));
   }
   QLossArgs q_loss_args;
@@ -503,23 +576,52 @@ int grl_ctx::plan_q() {
       op.run = [fa](hipStream_t s) { launch_q_bwd(fa, s); };
       ops_grads.push_back(op);
     } else {
+      // layer normalisation: the backward-data launches leave the gradient w.r.t. the layer's OUTPUT (no ReLU mask) and one
+      // ln_relu_bwd launch per level turns it, in place, into the gradient w.r.t. the pre-activation that the next
+      // backward-data launch and the weight-gradient launch read; beta / gamma gradients leave as slabs per block of rows
+      auto relu_mask = [&](const float* z) { return ln ? nullptr : z; };
+      auto ln_bwd = [&](const float* u, float* stat, int64_t beta, int64_t gam, float* dz, int H) {
+        LnDesc d;
+        memset(&d, 0, sizeof(d));
+        d.u = u; d.stat = stat; d.gamma = P + gam; d.beta = P + beta; d.dz = dz; d.H = H;
+        const int n_sl = ln_bwd_slabs(B);
+        d.slab = wk.f32((int64_t)n_sl * 2 * H);
+        ReduceDesc r;
+        memset(&r, 0, sizeof(r));
+        r.src = d.slab; r.splits = n_sl; r.slab_stride = 2 * (int64_t)H; r.dst = grads + beta; r.n = H;
+        reduces.push_back(r);
+        r.src = d.slab + H; r.dst = grads + gam;
+        reduces.push_back(r);
+        return d;
+      };
       std::vector<IgemmProb> pr;      // output layers -> last hidden
-      for (int br = 0; br < D; ++br)
+      std::vector<LnDesc> lt;
+      for (int br = 0; br < D; ++br) {
         pr.push_back(dense_bwd({{gact.adv + br * nbp, D * nbp, nb, P + Pon.bw[br][Lb]}}, B, 0, c.q_branch[Lb - 1],
-                               gact.zb[br][Lb - 1], c.q_branch[Lb - 1], a.zb[br][Lb - 1]));
+                               gact.zb[br][Lb - 1], c.q_branch[Lb - 1], relu_mask(a.zb[br][Lb - 1])));
+        if (ln) lt.push_back(ln_bwd(a.ub[br][Lb - 1], a.sb[br][Lb - 1], Pon.bbeta[br][Lb - 1], Pon.bgam[br][Lb - 1], gact.zb[br][Lb - 1], c.q_branch[Lb - 1]));
+      }
       pr.push_back(dense_bwd({{gact.v, ld_dv, 1, P + Pon.vw[Lv]}}, B, 0, c.q_value[Lv - 1], gact.zv[Lv - 1], c.q_value[Lv - 1],
-                             a.zv[Lv - 1]));
+                             relu_mask(a.zv[Lv - 1])));
+      if (ln) lt.push_back(ln_bwd(a.uv[Lv - 1], a.sv[Lv - 1], Pon.vbeta[Lv - 1], Pon.vgam[Lv - 1], gact.zv[Lv - 1], c.q_value[Lv - 1]));
       add_launch(ops_grads, "q_bwd", 1, pr);
+      add_ln(ops_grads, "q_ln_bwd", true, lt, B);
       for (int l = std::max(Lb, Lv) - 1; l >= 1; --l) {
         std::vector<IgemmProb> p2;
+        lt.clear();
         if (l < Lb)
-          for (int br = 0; br < D; ++br)
+          for (int br = 0; br < D; ++br) {
             p2.push_back(dense_bwd({{gact.zb[br][l], c.q_branch[l], c.q_branch[l], P + Pon.bw[br][l]}}, B, 0,
-                                   c.q_branch[l - 1], gact.zb[br][l - 1], c.q_branch[l - 1], a.zb[br][l - 1]));
-        if (l < Lv)
+                                   c.q_branch[l - 1], gact.zb[br][l - 1], c.q_branch[l - 1], relu_mask(a.zb[br][l - 1])));
+            if (ln) lt.push_back(ln_bwd(a.ub[br][l - 1], a.sb[br][l - 1], Pon.bbeta[br][l - 1], Pon.bgam[br][l - 1], gact.zb[br][l - 1], c.q_branch[l - 1]));
+          }
+        if (l < Lv) {
           p2.push_back(dense_bwd({{gact.zv[l], c.q_value[l], c.q_value[l], P + Pon.vw[l]}}, B, 0, c.q_value[l - 1],
-                                 gact.zv[l - 1], c.q_value[l - 1], a.zv[l - 1]));
+                                 gact.zv[l - 1], c.q_value[l - 1], relu_mask(a.zv[l - 1])));
+          if (ln) lt.push_back(ln_bwd(a.uv[l - 1], a.sv[l - 1], Pon.vbeta[l - 1], Pon.vgam[l - 1], gact.zv[l - 1], c.q_value[l - 1]));
+        }
         add_launch(ops_grads, "q_bwd", 1, p2);
+        add_ln(ops_grads, "q_ln_bwd", true, lt, B);
       }
       if (Lc > 0) {   // into the shared trunk: sum over the D+1 towers in chunks of three reduction parts
         std::vector<BwdPart> towers;
@@ -528,15 +630,18 @@ int grl_ctx::plan_q() {
         for (size_t t0 = 0; t0 < towers.size(); t0 += 3) {
           std::vector<BwdPart> chunk(towers.begin() + t0, towers.begin() + std::min(towers.size(), t0 + 3));
           const bool last = t0 + 3 >= towers.size();
-          IgemmProb p = dense_bwd(chunk, B, 0, hdim, gact.zc[Lc - 1], hdim, last ? a.zc[Lc - 1] : nullptr);
+          IgemmProb p = dense_bwd(chunk, B, 0, hdim, gact.zc[Lc - 1], hdim, last ? relu_mask(a.zc[Lc - 1]) : nullptr);
           p.accumulate = t0 > 0 ? 1 : 0;
           p.out_scale = c.q_trunk_scale;
           add_launch(ops_grads, "q_bwd", 1, {p});
         }
-        for (int k = Lc - 1; k >= 1; --k)
+        if (ln) add_ln(ops_grads, "q_ln_bwd", true, {ln_bwd(a.uc[Lc - 1], a.sc[Lc - 1], Pon.cbeta[Lc - 1], Pon.cgam[Lc - 1], gact.zc[Lc - 1], hdim)}, B);
+        for (int k = Lc - 1; k >= 1; --k) {
           add_launch(ops_grads, "q_bwd", 1,
                      {dense_bwd({{gact.zc[k], c.q_common[k], c.q_common[k], P + Pon.cw[k]}}, B, 0, c.q_common[k - 1],
-                                gact.zc[k - 1], c.q_common[k - 1], a.zc[k - 1])});
+                                gact.zc[k - 1], c.q_common[k - 1], relu_mask(a.zc[k - 1]))});
+          if (ln) add_ln(ops_grads, "q_ln_bwd", true, {ln_bwd(a.uc[k - 1], a.sc[k - 1], Pon.cbeta[k - 1], Pon.cgam[k - 1], gact.zc[k - 1], c.q_common[k - 1])}, B);
+        }
       }
     }
     // weight gradients (not here when the chained backward has formed them)
@@ -784,10 +889,17 @@ int grl_ctx::plan_q() {
     }
     std::vector<std::vector<IgemmProb>> sc1, sh1;
     std::vector<IgemmProb> so1;
-    fwd_stages(Pon, aact, afeat, ldf, NA, sc1, sh1, so1);
-    for (auto& v : sc1) add_launch(ops_act, "act_q", 0, v);
-    for (auto& v : sh1) add_launch(ops_act, "act_q", 0, v);
+    std::vector<std::vector<LnDesc>> lc1, lh1;
+    fwd_stages(Pon, aact, afeat, ldf, NA, sc1, sh1, so1, lc1, lh1);
+    for (size_t k = 0; k < sc1.size(); ++k) { add_launch(ops_act, "act_q", 0, sc1[k]); add_ln(ops_act, "act_ln", false, lc1[k], NA); }
+    for (size_t l = 0; l < sh1.size(); ++l) { add_launch(ops_act, "act_q", 0, sh1[l]); add_ln(ops_act, "act_ln", false, lh1[l], NA); }
     add_launch(ops_act, "act_q", 0, so1);
+    if (ln) {
+      int n_ln = 0;
+      for (auto* ops : {&ops_grads, &ops_act})
+        for (auto& o : *ops) n_ln += (o.tag == "q_ln_fwd" || o.tag == "q_ln_bwd" || o.tag == "act_ln") ? 1 : 0;
+      plan_note("grl plan: q layer_norm   per-layer launches + ln_relu_fwd/bwd (%d tensors in %d launches); no chains, no one-launch act\n", ln_tensors, n_ln);
+    }
     const float* adv = aact.adv; const float* vv = aact.v; float* qo = q_aout; const int rows = NA, Dq = D, nq = nb;
     // the last launch also writes the Q-values to coherent host memory and counts its workgroups there: grl_act polls the
     // counter instead of copying device -> host and synchronising the stream (GRL_TUNE act_poll=0 keeps that)
@@ -819,7 +931,7 @@ int grl_ctx::plan_q() {
       memset(q_io_host, 0, io_floats * 4);
       float* io_obs = q_io_host; float* io_explore = io_obs + (size_t)NA * c.obs_dim; float* io_bins = io_explore + (size_t)NA * D;
       for (int i = 0; i < NA * D; ++i) io_explore[i] = -1.f;
-      q_act_fused = sw.get(Sw::q_act) != 0 &&
+      q_act_fused = !ln && sw.get(Sw::q_act) != 0 &&
                     qa_shape_ok(c.obs_dim, D, nb, Lc, c.q_common, Lb, c.q_branch, Lv, c.q_value);
       plan_note("grl plan: q_act         epsilon-greedy act: %s\n",
                 q_act_fused ? "one launch (q_act.h)" : "launch list of the Q-value path + select kernel");

@@ -143,8 +143,9 @@ class _QModel(CheckpointMixin):
         raise NotImplementedError
 
     def setup_model(self):
-        if getattr(self.policy, "layer_norm", False) or self.policy_kwargs.get("layer_norm", False):
-            raise NotImplementedError("layer_norm policies are not implemented in the HIP engine")
+        # LnMlpPolicy or policy_kwargs={"layer_norm": True}: layer normalisation in front of every hidden layer's ReLU
+        # (grl_config.q_layer_norm, csrc/ln_kernels.h)
+        self.layer_norm = bool(getattr(self.policy, "layer_norm", False) or self.policy_kwargs.get("layer_norm", False))
         if getattr(self.policy, "feature_extraction", "mlp") == "cnn":
             raise NotImplementedError("%s on image observations is not implemented (the reference trains it on "
                                       "auto-encoder features)" % type(self).__name__)
@@ -167,7 +168,7 @@ class _QModel(CheckpointMixin):
                                   act_batch=max(1, self.n_envs), replay_capacity=self.buffer_size, normalize=0 if vn is None else _capi.norm_mode(vn), gamma=self.gamma,
                                   lr=lr, double_q=self.double_q, seed=engine_seed,
                                   prioritized=bool(self.prioritized_replay), per_alpha=self.prioritized_replay_alpha,
-                                  per_eps=self.prioritized_replay_eps, **kw)
+                                  per_eps=self.prioritized_replay_eps, layer_norm=self.layer_norm, **kw)
         self.engine = self._engine_factory(cfg, self.device)
         self.D, self.bins = D, bins
         self._init_weights()
@@ -182,7 +183,8 @@ class _QModel(CheckpointMixin):
         self._max_priority = 1.0
 
     def _init_weights(self):
-        """tf.contrib.layers.fully_connected defaults: Xavier-uniform weights, zero biases; target = copy."""
+        """tf.contrib.layers.fully_connected defaults: Xavier-uniform weights, zero biases; tf.contrib.layers.layer_norm
+        defaults: gamma one, beta zero; target = copy."""
         rng = np.random.default_rng(0 if self.seed is None else int(self.seed))
         P = {}
         for name, _, _, shape, _ in self.engine.table:
@@ -193,6 +195,8 @@ class _QModel(CheckpointMixin):
                 P[name] = rng.uniform(-lim, lim, shape).astype(np.float32)
             elif name.endswith("eps:0"):
                 P[name] = np.float32(self.exploration_initial_eps).reshape(())
+            elif name.endswith("/gamma:0"):
+                P[name] = np.ones(shape, np.float32)
             else:
                 P[name] = np.zeros(shape, np.float32)
         for name, *_ in self.engine.table:
@@ -398,6 +402,8 @@ class _QModel(CheckpointMixin):
 
     def _data(self):
         d = {k: getattr(self, k) for k in self._SAVED}
+        if getattr(self, "layer_norm", False):      # the zip rebuilds the same network whichever way it was asked for
+            d["policy_kwargs"] = dict(self.policy_kwargs, layer_norm=True)
         d["learning_rate"] = float(self.learning_rate(1.0)) if callable(self.learning_rate) else float(self.learning_rate)
         d.update(observation_space=self.observation_space, action_space=self.action_space, policy=self.policy,
                  n_envs=self.n_envs, _vectorize_action=True)

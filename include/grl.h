@@ -114,6 +114,12 @@ typedef struct grl_config {
      over the action branches instead of averaging them (default 0: mean, Tavakoli et al. 2018 eq. 6);
      q_trunk_scale above = 1 disables the 1/(D+1) rescaling of the gradient entering the shared trunk. */
   int32_t q_loss_sum_branches;
+  /* DQN / BDQ: 1 = layer normalisation in front of the ReLU of every HIDDEN layer of the Q-network (stable-baselines
+     `LnMlpPolicy` / policy_kwargs layer_norm=True: tf.contrib.layers.layer_norm, epsilon 1e-12, csrc/ln_kernels.h); the
+     parameter table then holds `LayerNorm[_k]/beta:0` and `LayerNorm[_k]/gamma:0` behind the layer's weights and biases.
+     Appended last: it occupies what used to be the struct's tail padding, so every earlier field and sizeof(grl_config)
+     stay where they were -- a caller that does not zero the struct now has to set it.  Must be 0 on SAC handles. */
+  int32_t q_layer_norm;
 } grl_config;
 
 /* byte sizes of the four caller-provided device arenas */
