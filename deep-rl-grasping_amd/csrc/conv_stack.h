@@ -24,6 +24,7 @@
 //     fmaf loop (see "Reduction order" below; scripts/conv_stack_bench.hip checks the bits against such a loop).
 #pragma once
 #include <stdint.h>
+#include "store_drain.h"
 
 namespace grl {
 
@@ -43,6 +44,8 @@ struct ConvStackArgs {
   ConvStackNet nets[CS_MAX_NETS];   // by value: the descriptors arrive with the kernel arguments (no dependent load of their own)
   int B;
   int n_nets;
+  int drain_a12;   // the a1 tiles and the a2 rows leave write-through (store_drain.h: whole 128-byte rows, read by later launches only;
+                   // a3's 4-byte strided store stays plain)
 #ifdef CS_STAMPS
   unsigned long long* stamps;
 #endif
@@ -244,7 +247,7 @@ __global__ __launch_bounds__(256, (C == 1 ? CS_WG_PER_CU : (C == 4 ? 3 : 2))) vo
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int row = 16 * mt + 8 * h + (l >> 3), ch = l & 7;
-          if (row < 225) *(cs_f4*)(a1g + (int64_t)row * net.ld1 + 4 * ch) = cs_row4(act1 + row * CS_P1, ch);
+          if (row < 225) st_quad_policy(a1g, row * net.ld1 + 4 * ch, cs_row4(act1 + row * CS_P1, ch), a.drain_a12);
         }
       }
     };
@@ -308,7 +311,7 @@ __global__ __launch_bounds__(256, (C == 1 ? CS_WG_PER_CU : (C == 4 ? 3 : 2))) vo
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             const int row = 16 * mt + (l >> 2), m = 4 * nt + (l & 3);
-            if (row < 225) *(cs_f4*)(a1g + (int64_t)row * net.ld1 + 4 * m) = cs_row4(act1 + row * CS_P1, m);
+            if (row < 225) st_quad_policy(a1g, row * net.ld1 + 4 * m, cs_row4(act1 + row * CS_P1, m), a.drain_a12);
           }
         }
       }
@@ -413,7 +416,7 @@ __global__ __launch_bounds__(256, (C == 1 ? CS_WG_PER_CU : (C == 4 ? 3 : 2))) vo
     float* dst = net.a2 + (int64_t)smp * 36 * 64;
     for (int e = t; e < 36 * 16; e += 256) {
       const int row = e >> 4, ch = e & 15;
-      *(cs_f4*)(dst + row * 64 + 4 * ch) = cs_row4(act2 + row * CS_P2, ch);
+      st_quad_policy(dst, row * 64 + 4 * ch, cs_row4(act2 + row * CS_P2, ch), a.drain_a12);
     }
   }
   CS_STAMP(6);

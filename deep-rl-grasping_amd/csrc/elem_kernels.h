@@ -12,6 +12,7 @@
 #endif
 #include <stdint.h>
 #include "../../include/grl.h"   // GRL_MAX_LAYERS
+#include "store_drain.h"
 
 namespace grl {
 
@@ -105,6 +106,8 @@ struct GatherArgs {
   // backward pass still reads, to the reduction launch that ends update t.
   // img_ctr = 1: draw with the counter DevScalars.rng_img (the riders of the head launch); set_img = 1: leave rng_step + 1 there
   int parts, img_ctr, set_img;
+  // riders of the head launch only (gather_images_rider): the image rows leave write-through (store_drain.h)
+  int drain;
 };
 #define GATHER_RIDE_ROWS 16       /* row instances per rider workgroup of the head launch (gather_images_rider) */
 #define GATHER_ROWS_U8 4          /* rows per workgroup of the grouped form, RGB-D ring with byte colours (GRL_TUNE gather_rows) */
@@ -408,19 +411,25 @@ __device__ __forceinline__ void gather_norm_rows_body(const GatherArgs& a, const
       rc.x = 1.0 / sd.x; rc.y = 1.0 / sd.y; rc.z = 1.0 / sd.z; rc.w = 1.0 / sd.w;     // IEEE divisions: correctly rounded reciprocals
     }
     const bool fast = BRANCH_FREE && norm_fast255(a.normalize, a.clip_obs, a.scale_div);      // (uniform: one branch around the loop, none inside)
+    // BRANCH_FREE is the riders' form: their rows may leave write-through (GatherArgs.drain, set by plan_sac.inl for the riders
+    // of a CNN plan only: those have no second observation copy x_obs2)
+    auto put = [&](long o, gn_f4 y) {
+      if (BRANCH_FREE && a.drain) st_quad_policy(which ? a.x_next : a.x_obs, o, y, 1);
+      else gather_store(a, which, o, y);
+    };
     if (fast) {
       gn_f4 y[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) y[r] = norm_elem_rcp4<true>(x[r], mu, sd, rc, a.clip_obs, 255.f);
 #pragma unroll
-      for (int r = 0; r < R; ++r) gather_store(a, which, (long)(b0 + r) * a.ldx + e4, y[r]);
+      for (int r = 0; r < R; ++r) put((long)(b0 + r) * a.ldx + e4, y[r]);
     } else
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       gn_f4 y;
       if (a.normalize) y = norm_elem_rcp4<false>(x[r], mu, sd, rc, a.clip_obs, a.scale_div);
       else y = norm_elem4<false>(x[r], mu, sd, 0, a.clip_obs, a.scale_div);
-      gather_store(a, which, (long)(b0 + r) * a.ldx + e4, y);
+      put((long)(b0 + r) * a.ldx + e4, y);
     }
   }
   if (bx == 0 && a.parts != 1) {
@@ -1296,23 +1305,11 @@ struct ReduceDesc {
 // System-scope WRITE-THROUGH stores (buffer store with sc0 | sc1 / a system-scope atomic store): what a kernel uses for data
 // that another GPU reads while kernels are running -- nothing stays dirty in an L2, a drained store has reached memory
 // (csrc/dp_kernels.h: the exchange step of the data-parallel update).
+// (st_sys_quad: store_drain.h)
 #ifdef GRL_HOSTEMU
-struct sys_f4 { float v[4]; };
-static inline void st_sys_quad(float* base, int64_t quad, const float (&v)[4]) { for (int k = 0; k < 4; ++k) base[4 * quad + k] = v[k]; }
 static inline void st_sys_f1(float* p, float v) { *p = v; }
 static inline float ld_sys_f1(const float* p) { return *p; }
 #else
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t sys_rsrc(const float* p) {
-  const uint64_t a = (uint64_t)p;     // (made provably wave-uniform: no waterfall loop around the buffer instructions)
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((int)(uint32_t)a), hi = __builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), 0, 0x7fffffff, 0x00020000);
-}
-enum { SYS_SCOPE = 1 | 16 };     // buffer-instruction cache policy: sc0 | sc1
-__device__ __forceinline__ void st_sys_quad(float* base, int64_t quad, const float (&v)[4]) {
-  typedef unsigned int sys_u4 __attribute__((ext_vector_type(4)));
-  typedef float sys_f4 __attribute__((ext_vector_type(4)));
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sys_u4, sys_f4{v[0], v[1], v[2], v[3]}), sys_rsrc(base), (int)(quad << 4), 0, SYS_SCOPE);
-}
 __device__ __forceinline__ void st_sys_f1(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 __device__ __forceinline__ float ld_sys_f1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 #endif

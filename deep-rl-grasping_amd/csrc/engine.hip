@@ -79,6 +79,7 @@ static inline int64_t rup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
   X(conv_stack, 1, INT, CREATE)               \
   X(conv_stack_bwd, 0, INT, CREATE)           \
   X(l0_split, 3, INT, CREATE)                 \
+  X(store_drain, SD_DEFAULT, INT, CREATE)     \
   X(wg_split, 0, TRIPLE, CREATE)              \
   X(sk_wgs, 512, INT, CREATE)                 \
   X(i2cfg_, -1, PER_TAG, CREATE)              \
@@ -429,6 +430,7 @@ struct grl_ctx {
   bool staged_ok = false;
   bool conv_stack = false;                // conv1 -> conv2 -> conv3 as one sample-local launch (conv_stack.h)
   bool conv_stack_bwd = false;            // ... and the backward-data of conv3 -> conv2
+  int store_drain = 0;                    // tensor groups of the SAC CNN plan stored write-through (store_drain.h: StoreDrain bits)
   bool loss_in_reduce = false;
   float grad_scale = 1.f;   // read by the apply op
 

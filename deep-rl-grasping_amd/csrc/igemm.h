@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #endif
 #include <stdint.h>
+#include "store_drain.h"
 
 namespace grl {
 
@@ -69,7 +70,10 @@ struct IgemmProb {
   float alg_frac;         // host only (profiling): share of the M*N*K MACs that are algorithmic -- the masked parity form of
                           // the conv backward-data multiplies zeros for taps outside the output; 0 means 1
 };
-enum { VF_P_TABS = 1u, VF_Q_TAB = 2u, VF_C_VEC = 4u, VF_CT4 = 8u };   // VF_CT4 (host): scatter-table offsets are multiples of 4   // VF_C_VEC is also read by the igemm2 epilogue
+// VF_C_DRAIN (set by the plan, per problem): the 16-byte stores of igemm2's wide epilogue leave write-through (store_drain.h) --
+// an output that only a LATER launch reads; never with `accumulate`.  A bit of vflags, which the epilogue reads anyway: a field
+// of its own would be one more scalar load in front of every tile's stores.
+enum { VF_P_TABS = 1u, VF_Q_TAB = 2u, VF_C_VEC = 4u, VF_CT4 = 8u, VF_C_DRAIN = 16u };   // VF_CT4 (host): scatter-table offsets are multiples of 4   // VF_C_VEC is also read by the igemm2 epilogue
 
 // Addressing modes are compile-time so the staging code has no branch around any load: every
 // load of a slab is issued back to back (masked lanes read offset 0 and select 0 afterwards) and the

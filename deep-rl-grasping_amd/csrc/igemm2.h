@@ -337,6 +337,7 @@ __device__ __forceinline__ void igemm2_tile(const IgemmProb* __restrict__ pb, co
   // ... and so are the scatter offsets of the wide epilogue (conv backward-data: output rows through c_tab_i): fetched
   // after the loop they sit in front of the ReLU-mask loads that need them -- two dependent round trips per tile
   const bool cvec = (pb->vflags & VF_C_VEC) != 0;
+  const int cdrain = (pb->vflags & VF_C_DRAIN) != 0 && !accumulate;
   constexpr int EP_NC4 = BN / 4, EP_RSTEP = 256 / EP_NC4, EP_NQ = BM / EP_RSTEP;
   int ct_pre[EP_NQ], mt_pre[EP_NQ];
 #pragma unroll
@@ -574,7 +575,7 @@ __device__ __forceinline__ void igemm2_tile(const IgemmProb* __restrict__ pb, co
       }
       v.x = mk[e].x > 0.f ? v.x : alpha * v.x; v.y = mk[e].y > 0.f ? v.y : alpha * v.y;
       v.z = mk[e].z > 0.f ? v.z : alpha * v.z; v.w = mk[e].w > 0.f ? v.w : alpha * v.w;
-      if (ok[e]) *(GRL_GLOBAL f32x4*)(cbase + off[e]) = v;
+      if (ok[e]) st_quad_policy((float*)cbase, off[e], v, cdrain);
     }
   };
 

@@ -197,6 +197,16 @@ int grl_ctx::plan_sac() {
       ft[l] = conv_fwd_tabs(cg[l], B);
     }
     const float* xin[3] = {x_obs, x_obs, x_next};
+    // tensor groups whose 16-byte stores leave write-through (store_drain.h; GRL_TUNE store_drain=<mask>, bits outside SD_ALL
+    // are ignored).  The buffer instruction takes 32-bit byte offsets: the largest buffers of the groups -- an image buffer, the
+    // a1 / g1 pair -- must stay below SD_MAX_BYTES, else every group keeps plain stores and the plan dump says why.
+    {
+      const int64_t largest = 4 * std::max<int64_t>((int64_t)B * img_elems, (int64_t)B * 225 * 64);
+      const int asked = sw.get(Sw::store_drain) & SD_ALL;
+      store_drain = largest < SD_MAX_BYTES ? asked : 0;
+      plan_note("grl plan: store_drain   mask %d (1 a1+a2, 2 a3 [per-layer route], 4 g1+g2, 8 weight-gradient slabs, 16 riders' images)%s\n", store_drain,
+                store_drain != asked ? "  [asked for more: a buffer of this batch reaches 2 GiB, all stores plain]" : "");
+    }
     // conv1 -> conv2 -> conv3 of the three networks: ONE sample-local launch (conv_stack.h; a workgroup owns a sample of a
     // network and keeps the activation chain in LDS) for 1 / 2 / 4 image channels; GRL_TUNE conv_stack=0 or any other channel
     // count: one implicit-GEMM launch per layer.  The target network's layer-1 / layer-2 activations are not stored.
@@ -212,6 +222,7 @@ int grl_ctx::plan_sac() {
         cn.a1 = n < 2 ? a1[n] : nullptr; cn.a2 = n < 2 ? a2[n] : nullptr; cn.a3 = a3[n]; cn.ld1 = ld1;
       }
       ca.B = B; ca.n_nets = 3;
+      ca.drain_a12 = (store_drain & SD_A12) != 0;
       const int Ci = C_img;
       Op op; op.tag = "conv_stack_fwd";
       op.flops = op.flops_exec = 2.0 * B * 3 * (225.0 * 32 * 64 * Ci + 36.0 * 64 * 512 + 16.0 * 64 * 576);
@@ -226,6 +237,7 @@ int grl_ctx::plan_sac() {
         const float* in = l == 0 ? xin[n] : (l == 1 ? a1[n] : a2[n]);
         float* out = l == 0 ? a1[n] : (l == 1 ? a2[n] : a3[n]);
         pr.push_back(conv_fwd(in, ft[l], cg[l], P + ex[n].w[l], P + ex[n].b[l], out, ACT_RELU, 0.f));
+        if (store_drain & (l == 2 ? SD_A3 : SD_A12)) pr.back().vflags |= VF_C_DRAIN;     // (the target network's a1 / a2 too: same launch)
       }
       add_launch(ops_grads, tags[l], 0, pr);
     }
@@ -649,6 +661,14 @@ int grl_ctx::plan_sac() {
       }
       wg_ones.clear();
     }
+    // the problems of a launch with VF_C_DRAIN set where GRL_TUNE store_drain names their group (outputs that a later launch
+    // reads; the staged data-parallel plan keeps its own, plain copies)
+    auto drained = [&](std::vector<IgemmProb> pr, int group) {
+      if (store_drain & group)
+        for (auto& p : pr)
+          if (!p.accumulate) p.vflags |= VF_C_DRAIN;
+      return pr;
+    };
     if (cnn && conv_stack_bwd) {
       add_launch(ops_grads, "fc_bwd", 1, bwd_pr[0]);
       ConvStackBwdArgs ba;
@@ -667,8 +687,8 @@ int grl_ctx::plan_sac() {
       add_launch(ops_grads, "fc_bwd", 1, bwd_pr[0]);
       std::vector<IgemmProb> riders = take_riders(wg_merged, rider_budget);
       if (!riders.empty()) add_launch(conv3_bwd_plain, "conv3_bwd", 1, bwd_pr[1]);
-      add_launch(ops_grads, "conv3_bwd", 1, bwd_pr[1], "wgrad_dense", 2, riders);
-      add_launch(ops_grads, "conv2_bwd", 1, bwd_pr[2]);
+      add_launch(ops_grads, "conv3_bwd", 1, drained(bwd_pr[1], SD_G12), "wgrad_dense", 2, drained(riders, SD_SLABS));
+      add_launch(ops_grads, "conv2_bwd", 1, drained(bwd_pr[2], SD_G12));
     }
     add_launch(wgrad_ops, "wgrad_dense", 2, wg_ones);
     add_launch(wgrad_ops, "wgrad_dense", 2, wg_plain);
@@ -677,6 +697,7 @@ int grl_ctx::plan_sac() {
       std::vector<IgemmProb> all;
       for (int l = 2; l >= 0; --l) all.insert(all.end(), wgc[l].begin(), wgc[l].end());
       all.insert(all.end(), wg_merged.begin(), wg_merged.end());
+      if (cnn) all = drained(all, SD_SLABS);
       add_launch(wgrad_ops, "wgrad_conv", 2, all);
       if (x_obs_b && cnn) {      // the same launch reading conv1's input from the second image buffer (flavour 1 of "gather_ride")
         bool patched = false;
@@ -871,6 +892,7 @@ int grl_ctx::plan_sac() {
               GatherArgs gi = g2;                        // images of update t+1 into the buffer flavour f does NOT read
               gi.parts = 1; gi.img_ctr = 1; gi.rng_ahead = 0; gi.quiet = 1;
               gi.rows = ride_rows;
+              gi.drain = (store_drain & SD_IMAGES) != 0 && !gi.x_obs2;
               if (!gather_ride_rows_built(gi.rows)) return fail(GRL_ERR_INVALID, "gather_ride: no kernel for this many rows per rider workgroup");
               gi.x_obs = f ? x_obs : x_obs_b;
               Op heads_ride[2];                          // [0] the call's first update, [1] later ones (see pf_heads)
