@@ -38,6 +38,8 @@
 #include "per_kernels.h"
 #include "ae_kernels.h"
 #include "q_apply_kernels.h"
+#define GRL_QW_TYPES_ONLY           // (the wide apply is instantiated in q_wide.hip)
+#include "q_wide_kernels.h"
 #include "ln_kernels.h"
 #include "dp_kernels.h"
 

@@ -101,6 +101,12 @@ int grl_ctx::plan_q() {
   tgt_off = n_params;
   add_net(scope + "/target_q_func/model", Ptg, false);
   vf_off = 0; n_polyak = 0; ent_off = 0;
+  // A handle is WIDE when a trainable variable outgrows the largest one of the vector-observation networks (an MLP over a
+  // flattened image): layer 0 of the chains is cut into partial sums and the apply runs tiled (q_wide_kernels.h).  Every
+  // other handle keeps its launch list.
+  bool wide = false;
+  for (auto& v : vars) wide = wide || (v.trainable && v.numel > QW_WIDE_MIN);
+  int q_l0_split = 0;           // partial sums of the q_l0 launch of a wide handle (0: no such launch, or not cut)
 
   // ---------------- arenas
   params = st.f32(n_params);
@@ -347,14 +353,27 @@ int grl_ctx::plan_q() {
     for (int l = 0; l < Lb; ++l) want_mfma = want_mfma && c.q_branch[l] <= QM_W;
     for (int l = 0; l < Lv; ++l) want_mfma = want_mfma && c.q_value[l] <= QM_W;
     const bool l0_chain = want_mfma && c.obs_dim <= 2 * QM_W && sw.get(Sw::q_l0_chain) != 0;
+    // wide handle: three to six problems of one tile each would walk K = obs_dim alone -- the reduction is cut (set_split) until
+    // the launch has at least 64 tiles, from B, H and K; the chains add the partial sums in index order before bias and
+    // activation (HtHead.u_split, as the SAC heads do)
+    auto l0_cut = [&](IgemmProb p, int H0, float*& u) {
+      if (wide) {
+        const int n_prob = 3 * (Lc > 0 ? 1 : D + 1);
+        const int base = n_prob * ((B + 63) / 64) * ((H0 + 63) / 64);
+        set_split(p, (64 + base - 1) / base);
+        q_l0_split = std::max(q_l0_split, p.split);
+      }
+      u = wk.f32((int64_t)B * H0 * p.split);
+      p.c = u;
+      return p;
+    };
     for (int n = 0; n < 3; ++n) {
       const QNetP& W = *Wn[n];
       const QNetAct& a = net[n];
       float* u_trunk = nullptr;
       if (Lc > 0 && !l0_chain) {   // layer 0 of the trunk: one GEMM (K = obs_dim), no bias / activation (applied by the chain)
-        u_trunk = wk.f32((int64_t)B * c.q_common[0]);
-        l0.push_back(dense_fwd(xin[n], ldf, c.obs_dim, nullptr, 0, 0, B, P + W.cw[0], c.q_common[0], nullptr, u_trunk,
-                               c.q_common[0], ACT_NONE));
+        l0.push_back(l0_cut(dense_fwd(xin[n], ldf, c.obs_dim, nullptr, 0, 0, B, P + W.cw[0], c.q_common[0], nullptr, nullptr,
+                                      c.q_common[0], ACT_NONE), c.q_common[0], u_trunk));
       }
       for (int tw = 0; tw <= D; ++tw) {
         const int Lt = tw < D ? Lb : Lv;
@@ -363,6 +382,7 @@ int grl_ctx::plan_q() {
         int li = 0;
         if (Lc > 0) {
           h.u = u_trunk; h.ldu = c.q_common[0]; h.b0 = P + W.cb[0]; h.H0 = c.q_common[0];
+          if (u_trunk && q_l0_split > 1) { h.u_split = q_l0_split; h.u_stride = (long)B * c.q_common[0]; }
           if (l0_chain) { h.xa = xin[n]; h.ld_xa = ldf; h.n_xa = c.obs_dim; h.w0a = P + W.cw[0]; }
           h.z0 = tw == 0 ? a.zc[0] : nullptr;             // the trunk is recomputed per tower, stored once
           h.hid[0] = c.q_common[0];
@@ -377,9 +397,9 @@ int grl_ctx::plan_q() {
           float* u = nullptr;
           if (l0_chain) { h.xa = xin[n]; h.ld_xa = ldf; h.n_xa = c.obs_dim; h.w0a = tower_w(W, tw, 0); }
           else {
-            u = wk.f32((int64_t)B * tower_hid(tw, 0));
-            l0.push_back(dense_fwd(xin[n], ldf, c.obs_dim, nullptr, 0, 0, B, tower_w(W, tw, 0), tower_hid(tw, 0), nullptr, u,
-                                   tower_hid(tw, 0), ACT_NONE));
+            l0.push_back(l0_cut(dense_fwd(xin[n], ldf, c.obs_dim, nullptr, 0, 0, B, tower_w(W, tw, 0), tower_hid(tw, 0), nullptr, nullptr,
+                                          tower_hid(tw, 0), ACT_NONE), tower_hid(tw, 0), u));
+            if (l0.back().split > 1) { h.u_split = l0.back().split; h.u_stride = (long)B * tower_hid(tw, 0); }
           }
           h.u = u; h.ldu = tower_hid(tw, 0); h.b0 = tower_b(W, tw, 0); h.H0 = tower_hid(tw, 0);
           h.z0 = tower_z(a, tw, 0); h.hid[0] = h.H0;
@@ -696,6 +716,29 @@ int grl_ctx::plan_q() {
     adam_base.grad_scale = 1.f; adam_base.eps = 1e-8f; adam_base.target = params + tgt_off;
     memset(&loss_args, 0, sizeof(loss_args));
   }
+  if (wide && c.q_grad_clip > 0.f) {
+    // wide handle: clip_by_norm (one workgroup per variable) + Adam become two launches over a tile table (q_wide_kernels.h).
+    // Data parallel: as below, the sum of the replicas is clipped at clip / grad_scale and Adam's 1 / W brings it back.
+    std::vector<VarSeg> segs;
+    for (auto& v : vars)
+      if (v.trainable) segs.push_back({v.off, v.numel});
+    const std::vector<QwTile> tl = qw_build_tiles(segs.data(), (int)segs.size());
+    const QwTile* d_tl = upload_vec(wk, tl);
+    const int n_tl = (int)tl.size();
+    float* part = wk.f32(n_tl);
+    float* g = grads; const float clip = c.q_grad_clip;
+    grl_ctx* self = this;
+    Op op; op.tag = "q_sumsq";
+    op.run = [g, d_tl, n_tl, part](hipStream_t s) { launch_q_sumsq(g, d_tl, n_tl, part, s); };
+    ops_apply.push_back(op);
+    Op oa; oa.tag = "q_clip_adam";
+    oa.run = [self, g, d_tl, n_tl, part, clip](hipStream_t s) {
+      launch_q_clip_adam(g, d_tl, n_tl, part, clip / self->grad_scale, self->adam_args(self->grad_scale, false), s);
+    };
+    ops_apply.push_back(oa);
+    plan_note("grl plan: q_wide        apply: q_sumsq + q_clip_adam, %d tiles of <= %d floats over %zu variables; q_l0: %d partial sums (B %d, K %d)\n",
+              n_tl, QW_TILE, segs.size(), std::max(1, q_l0_split), B, c.obs_dim);
+  } else {
   if (c.q_grad_clip > 0.f) {   // per-variable tf.clip_by_norm, after the data-parallel all-reduce point
     std::vector<VarSeg> segs;
     for (auto& v : vars)
@@ -721,6 +764,7 @@ int grl_ctx::plan_q() {
       hipLaunchKernelGGL(adam_polyak_kernel, dim3(blocks), dim3(256), 0, s, aa);
     };
     ops_apply.push_back(op);
+  }
   }
   {
     // Full updates: reduction + clip + Adam as one launch (q_reduce_clip_adam_kernel) when every trainable variable is

@@ -149,9 +149,13 @@ class _QModel(CheckpointMixin):
         if getattr(self.policy, "feature_extraction", "mlp") == "cnn":
             raise NotImplementedError("%s on image observations is not implemented (the reference trains it on "
                                       "auto-encoder features)" % type(self).__name__)
+        # An MLP policy takes a Box of any rank: the observation is flattened in C order (tf.layers.flatten over NHWC) and NOT
+        # divided by 255 -- stable-baselines 2.10's deepq FeedForwardPolicy scales only for feature_extraction == "cnn"
+        # (DESIGN.md 5).  The first kernel is [prod(shape), H]; every call below hands the engine C-contiguous float32 rows.
         obs_shape = tuple(self.observation_space.shape)
-        if len(obs_shape) != 1:
-            raise ValueError("vector observations expected, got %s" % (obs_shape,))
+        if len(obs_shape) < 1 or not sp.is_box(self.observation_space):
+            raise ValueError("Box observations expected, got %s" % (self.observation_space,))
+        self._obs_dim = int(np.prod(obs_shape))
         D, bins, common, branch, value = self._towers()
         vn = self._vec_normalize_env
         kw = {}
@@ -164,7 +168,7 @@ class _QModel(CheckpointMixin):
         if rt is not None:
             engine_seed += 7919 * rt.rank             # every replica draws its own replay indices
             self.device = rt.device
-        cfg = _capi.make_q_config(self.algo, obs_shape[0], D, bins, common, branch, value, batch_size=self._local_batch,
+        cfg = _capi.make_q_config(self.algo, self._obs_dim, D, bins, common, branch, value, batch_size=self._local_batch,
                                   act_batch=max(1, self.n_envs), replay_capacity=self.buffer_size, normalize=0 if vn is None else _capi.norm_mode(vn), gamma=self.gamma,
                                   lr=lr, double_q=self.double_q, seed=engine_seed,
                                   prioritized=bool(self.prioritized_replay), per_alpha=self.prioritized_replay_alpha,
@@ -214,7 +218,7 @@ class _QModel(CheckpointMixin):
         stream the single-env loop consumes -- and the greedy rows are chosen on the device, one call per act_batch rows
         (engine.act_bins; skipped when every row explores)."""
         raw, observed = getattr(self, "_act_device", (False, False))    # (the learn loop, statistics on the device)
-        obs = np.asarray(obs, np.float32).reshape(-1, self.observation_space.shape[0])
+        obs = np.asarray(obs, np.float32).reshape(-1, self._obs_dim)
         explore = np.full((obs.shape[0], self.D), -1, np.int64)
         if always_draw or eps > 0:
             for i in range(obs.shape[0]):

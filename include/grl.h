@@ -64,7 +64,9 @@ typedef struct grl_config {
   int32_t img_hw;         /* 64 (config/camera_info.yaml:1-2)                                   */
   int32_t obs_channels;   /* channels of the env observation: 2 depth, 5 RGB-D (robot.py:223-228) */
   int32_t n_direct;       /* direct features carried in the last channel (augmented only)       */
-  int32_t obs_dim;        /* vector observation size (MLP extractor only)                       */
+  int32_t obs_dim;        /* vector observation size (MLP extractor only).  DQN / BDQ handles: any size -- an image
+                             observation is handed over flattened in C order (64 * 64 * C values, NOT divided by 255);
+                             a handle whose first kernel exceeds 131 072 floats takes the wide route of plan_q.inl    */
   int32_t act_dim;        /* 5 full / 3 simplified (actuator.py:60-73)                           */
   int32_t n_layers;       /* len(config[algo]['layers'])                                        */
   int32_t layers[GRL_MAX_LAYERS];
