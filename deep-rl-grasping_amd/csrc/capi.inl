@@ -27,13 +27,8 @@ static int check_cfg(const grl_config* c) {
         c->q_n_value < 1 || c->q_n_value > GRL_MAX_LAYERS)
       return fail(GRL_ERR_INVALID, "tower depths out of range (branch and value towers need >= 1 hidden layer)");
     if (c->q_layer_norm != 0 && c->q_layer_norm != 1) return fail(GRL_ERR_INVALID, "q_layer_norm must be 0 or 1");
-    if (c->q_layer_norm) {
-      bool ok = true;
-      for (int k = 0; k < c->q_n_common; ++k) ok = ok && ln_npl(c->q_common[k]) > 0;
-      for (int l = 0; l < c->q_n_branch; ++l) ok = ok && ln_npl(c->q_branch[l]) > 0;
-      for (int l = 0; l < c->q_n_value; ++l) ok = ok && ln_npl(c->q_value[l]) > 0;
-      if (!ok) return fail(GRL_ERR_INVALID, "layer-normalised Q-networks support hidden widths up to " + std::to_string(64 * LN_MAX_NPL));
-    }
+    if (c->q_layer_norm && !q_hidden_widths_all(*c, [](int w) { return ln_npl(w) > 0; }))
+      return fail(GRL_ERR_INVALID, "layer-normalised Q-networks support hidden widths up to " + std::to_string(64 * LN_MAX_NPL));
     if (c->q_per && c->batch_size > 1024) return fail(GRL_ERR_INVALID, "prioritised replay supports batch_size <= 1024");
     if (c->q_per && c->replay_capacity > (int64_t)PER_BLK * PER_BLK)
       return fail(GRL_ERR_INVALID, "prioritised replay supports up to 1024 x 1024 transitions (two-level segment tree)");

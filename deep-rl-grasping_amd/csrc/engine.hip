@@ -424,8 +424,6 @@ struct grl_ctx {
   GatherArgs pf_ga;
   int pf_gx = 0;
   std::vector<Op> ops_grads_apply_per;   // DQN / BDQ with prioritised replay: ... and the priority write-back
-  Op q_fwd_tick_op, q_bwd_wb_op;
-  bool have_q_fwd_tick = false, have_q_bwd_wb = false;
   // data parallel, staged (grl_compute_grads_staged): stage 0 ends with the dense (fc + head) gradients final in the
   // bucket, stage 1 is the convolution backward + its weight gradients + the loss reductions
   std::vector<Op> ops_stage0, ops_stage1;

@@ -55,13 +55,21 @@ struct QActNorm {
   double clip_obs;
 };
 
-static inline bool qa_shape_ok(int obs_dim, int D, int nb, int Lc, const int* common, int Lb, const int* branch, int Lv, const int* value) {
-  bool ok = obs_dim >= 1 && obs_dim <= QA_MAXK && D >= 1 && D <= QA_MAXD && nb >= 1 && nb <= QM_W && Lb >= 1 && Lv >= 1 &&
-            Lc >= 0 && Lc + (Lb > Lv ? Lb : Lv) <= GRL_MAX_LAYERS;
-  for (int k = 0; k < Lc; ++k) ok = ok && common[k] >= 1 && common[k] <= QM_W;
-  for (int l = 0; l < Lb; ++l) ok = ok && branch[l] >= 1 && branch[l] <= QM_W;
-  for (int l = 0; l < Lv; ++l) ok = ok && value[l] >= 1 && value[l] <= QM_W;
-  return ok;
+// every hidden width of a DQN / BDQ network -- trunk, branch towers, value tower -- satisfies pred
+template <class Pred> static inline bool q_hidden_widths_all(const grl_config& c, Pred pred) {
+  const int* w[3] = {c.q_common, c.q_branch, c.q_value};
+  const int n[3] = {c.q_n_common, c.q_n_branch, c.q_n_value};
+  for (int s = 0; s < 3; ++s)
+    for (int l = 0; l < n[s]; ++l)
+      if (!pred(w[s][l])) return false;
+  return true;
+}
+
+static inline bool qa_shape_ok(const grl_config& c) {
+  const int Lc = c.q_n_common, Lb = c.q_n_branch, Lv = c.q_n_value;
+  return c.obs_dim >= 1 && c.obs_dim <= QA_MAXK && c.q_branches >= 1 && c.q_branches <= QA_MAXD && c.q_bins >= 1 && c.q_bins <= QM_W &&
+         Lb >= 1 && Lv >= 1 && Lc >= 0 && Lc + (Lb > Lv ? Lb : Lv) <= GRL_MAX_LAYERS &&
+         q_hidden_widths_all(c, [](int w) { return w >= 1 && w <= QM_W; });
 }
 
 #ifndef GRL_HEADS_TYPES_ONLY

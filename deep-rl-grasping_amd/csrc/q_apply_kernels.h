@@ -12,6 +12,7 @@ namespace grl {
 // clip_by_norm_kernel (strided partial sums, tree -- over 1024 instead of 256 threads) and adam_polyak_kernel: three launches at the launch floor
 // (4.8 + 8.6 + 4.8 us under graph replay) become one.
 #define GRL_QAPPLY_MAX 16384   /* floats of LDS for the summed gradient of one variable */
+enum { GRL_QAPPLY_THREADS = 1024 };   // threads of its block (NT below): a launch that carries per-row work of the minibatch needs B <= this
 // QNextArgs: the sampler of the NEXT update riding on this launch (prioritised multi-update calls whose trunk launch has already
 // written this update's priorities back and refreshed the block sums: q_chain.h, QChainArgs.per_wb): n_sample workgroups behind
 // everything else, workgroup k = per_sample_kernel's workgroup k (sum-tree walk, importance weight, the row's gather).

@@ -158,6 +158,25 @@ def test_plan_without_layer_norm_is_the_parent_commits(hostemu_lib, monkeypatch,
         assert capfd.readouterr().err == want, head
 
 
+def test_plans_tables_and_arena_sizes_are_the_parent_commits(hostemu_lib, monkeypatch, capfd):
+    """tests/golden/q_plan_parent_routes.json (tests/q_plan_routes_util.py): the plan dump, the variable table and the arena
+    sizes of every shape / layer-norm / wide case, two prioritised handles and the baseline shape with each route switch off,
+    captured from the commit before plan_q became a list of steps over one tower list."""
+    import q_plan_routes_util as ru
+    monkeypatch.setenv("GRL_PLAN_DUMP", "1")
+    gold = ru.load_golden(os.path.join(GOLD, "q_plan_parent_routes.json"))
+    cases = ru.route_cases()
+    assert [c[0] for c in cases] == list(gold)
+    for cid, tune, make in cases:
+        want = gold[cid]
+        assert want["tune"] == tune
+        monkeypatch.setenv("GRL_TUNE", tune) if tune else monkeypatch.delenv("GRL_TUNE", raising=False)
+        got = ru.snapshot(make(), lambda: capfd.readouterr().err, hostemu_lib)
+        assert got["plan"] == want["plan"], cid
+        assert got["table"] == want["table"], cid
+        assert got["sizes"] == want["sizes"], cid
+
+
 def test_state_checkpoint_round_trip_and_refusal(hostemu_lib, tmp_path):
     case = lu.make_ln_case("bdq_no_trunk", n_replay=60)
     a = lu.engine_setup(case, NumpyHostBackend(), hostemu_lib)
