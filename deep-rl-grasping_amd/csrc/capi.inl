@@ -8,8 +8,10 @@ static int check_cfg(const grl_config* c) {
   if (c->algo == GRL_ALGO_AE) {
     if (c->batch_size < 1 || c->batch_size > 4096) return fail(GRL_ERR_INVALID, "batch_size out of range");
     if (c->replay_capacity < 1) return fail(GRL_ERR_INVALID, "replay_capacity must be >= 1");
+    if (!cfg_ae_default(*c) && !ae_net_ok(ae_net_of(*c))) return fail(GRL_ERR_INVALID, ae_domain_text());
     return GRL_OK;
   }
+  if (!cfg_ae_default(*c)) return fail(GRL_ERR_INVALID, "the ae_* fields are defined for auto-encoder handles");
   if (c->extractor < 0 || c->extractor > 2) return fail(GRL_ERR_INVALID, "extractor must be 0..2");
   if (c->n_layers < 1 || c->n_layers > GRL_MAX_LAYERS) return fail(GRL_ERR_INVALID, "n_layers out of range");
   for (int l = 0; l < c->n_layers; ++l)
@@ -1141,14 +1143,15 @@ int grl_encode(grl_handle h, const float* depth, int n, float* out) {
   if (!h || !depth || !out || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (!h->enc_loaded) return fail(GRL_ERR_STATE, "grl_encoder_load has not been called");
   if (n > h->NA) return fail(GRL_ERR_INVALID, "n exceeds act_batch");
-  if (int e = pin_reserve(h, (size_t)n * 4096, (size_t)n * 100)) return e;
+  const size_t ed = (size_t)h->enc_dim;      // 100 for the shipped encoder; an auto-encoder handle's own encoding_dim
+  if (int e = pin_reserve(h, (size_t)n * 4096, (size_t)n * ed)) return e;
   memcpy(h->pin_in, depth, (size_t)n * 4096 * 4);
   HIPCHK(hipMemcpyAsync(h->ex_in, h->pin_in, (size_t)n * 4096 * 4, hipMemcpyHostToDevice, h->stream));
   if (int e = h->run_seq("encode", {&h->ops_enc})) return e;
-  HIPCHK(hipMemcpyAsync(h->pin_out, h->eout, (size_t)n * 100 * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(h->pin_out, h->eout, (size_t)n * ed * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
-  memcpy(out, h->pin_out, (size_t)n * 100 * 4);
+  memcpy(out, h->pin_out, (size_t)n * ed * 4);
   return GRL_OK;
 }
 

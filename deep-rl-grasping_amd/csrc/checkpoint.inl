@@ -22,17 +22,20 @@ static const struct { const char* name; size_t off, size; } k_cfg_fields[] = {
   GRL_CFG_FIELD(q_n_branch), GRL_CFG_FIELD(q_branch), GRL_CFG_FIELD(q_n_value), GRL_CFG_FIELD(q_value), GRL_CFG_FIELD(q_huber),
   GRL_CFG_FIELD(q_double), GRL_CFG_FIELD(q_grad_clip), GRL_CFG_FIELD(q_trunk_scale), GRL_CFG_FIELD(q_per), GRL_CFG_FIELD(q_per_alpha),
   GRL_CFG_FIELD(q_per_eps), GRL_CFG_FIELD(replay_rgb_u8), GRL_CFG_FIELD(q_per_stratified), GRL_CFG_FIELD(q_per_alpha64),
-  GRL_CFG_FIELD(q_loss_sum_branches), GRL_CFG_FIELD(q_layer_norm),
+  GRL_CFG_FIELD(q_loss_sum_branches), GRL_CFG_FIELD(q_layer_norm), GRL_CFG_FIELD(ae_kernel), GRL_CFG_FIELD(ae_filters),
+  GRL_CFG_FIELD(ae_encoding_dim), GRL_CFG_FIELD(ae_alpha),
 };
 #undef GRL_CFG_FIELD
 
 // FNV-1a over the bytes of every field in field order (padding between fields never enters).  q_layer_norm, appended after
 // blobs of this layout existed, enters only when set: a blob written before the field existed hashes as it did then (its
-// configuration bytes hold zeros there) and is still accepted by a handle without layer normalisation.
+// configuration bytes hold zeros there) and is still accepted by a handle without layer normalisation.  The ae_* fields
+// (the auto-encoder's network, appended later still) follow the same rule: all zero -- the shipped network, cfg_ae_default in plan_ae.inl -- they stay out.
 static uint64_t cfg_hash(const grl_config& c) {
   uint64_t hsh = 0xcbf29ce484222325ull;
   for (const auto& f : k_cfg_fields) {
     if (f.off == offsetof(grl_config, q_layer_norm) && c.q_layer_norm == 0) continue;
+    if (f.off >= offsetof(grl_config, ae_kernel) && cfg_ae_default(c)) continue;
     for (size_t k = 0; k < f.size; ++k) hsh = (hsh ^ ((const uint8_t*)&c)[f.off + k]) * 0x100000001b3ull;
   }
   return hsh;
@@ -91,11 +94,14 @@ int grl_state_import(grl_handle h, const void* host_buf, size_t n) {
   if (hd.version != grl_version())
     return fail(GRL_ERR_INVALID, "state blob written by library version " + std::to_string(hd.version) + ", this is " + std::to_string(grl_version()));
   if (hd.layout != GRL_STATE_LAYOUT) return fail(GRL_ERR_INVALID, "state blob has layout version " + std::to_string(hd.layout) + ", expected " + std::to_string(GRL_STATE_LAYOUT));
-  if (hd.config_bytes != (int32_t)sizeof(grl_config)) return fail(GRL_ERR_INVALID, "state blob holds a grl_config of another size");
-  const size_t fixed = sizeof(hd) + sizeof(grl_config) + sizeof(StateHost);
+  // (a blob written before the ae_* fields were appended holds the struct up to them: they read as zeros, the shipped network)
+  const size_t csz = (size_t)hd.config_bytes;
+  if (csz != sizeof(grl_config) && csz != offsetof(grl_config, ae_kernel)) return fail(GRL_ERR_INVALID, "state blob holds a grl_config of another size");
+  const size_t fixed = sizeof(hd) + csz + sizeof(StateHost);
   if (n < fixed || hd.total_bytes != n) return fail(GRL_ERR_INVALID, "state blob is truncated (" + std::to_string(n) + " of " + std::to_string(hd.total_bytes) + " bytes)");
   grl_config c;
-  memcpy(&c, p, sizeof(c)); p += sizeof(c);
+  memset(&c, 0, sizeof(c));
+  memcpy(&c, p, csz); p += csz;
   for (const auto& f : k_cfg_fields)
     if (memcmp((const char*)&c + f.off, (const char*)&h->cfg + f.off, f.size) != 0)
       return fail(GRL_ERR_INVALID, std::string("state blob was written for another configuration: grl_config.") + f.name + " differs");

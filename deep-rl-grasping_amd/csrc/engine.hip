@@ -37,6 +37,8 @@
 #include "elem_kernels.h"
 #include "per_kernels.h"
 #include "ae_kernels.h"
+#include "ae_general.h"
+#include "ae_geom.h"
 #include "q_apply_kernels.h"
 #define GRL_QW_TYPES_ONLY           // (the wide apply is instantiated in q_wide.hip)
 #include "q_wide_kernels.h"
@@ -98,6 +100,7 @@ static inline int64_t rup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
   X(per_pf, 1, INT, CREATE)                   \
   X(q_pf, 1, INT, CREATE)                     \
   X(q_act, 1, INT, CREATE)                    \
+  X(ae_general, 0, INT, CREATE)               \
   X(graph_updates, 16, INT, CALL)             \
   X(dp_coarse, 0, INT, DP_INIT)               \
   X(dp_timeout_ms, 120000, INT, DP_CONNECT)   \
@@ -709,7 +712,7 @@ struct grl_ctx {
           uint64_t bits = 0;
           for (int kh = 0; kh < g.KH; ++kh)
             for (int kw = 0; kw < g.KW; ++kw)
-              if (ih0 + kh >= 0 && ih0 + kh < g.H && iw0 + kw >= 0 && iw0 + kw < g.W)
+              if (ih0 + kh >= 0 && ih0 + kh < g.H && iw0 + kw >= 0 && iw0 + kw < g.W && kh * g.KW + kw < 64)
                 bits |= 1ull << (kh * g.KW + kw);
           vm[m] = bits;
         }
@@ -1498,6 +1501,8 @@ struct grl_ctx {
   int plan_sac();
   int plan_q();        // DQN / BDQ (MLP towers, dueling, double-Q)
   int plan_ae();       // depth auto-encoder training (encoders.py:40-50,70-136)
+  int plan_ae_general(const AeNet& net);   // ... of any supported network but the shipped one (GRL_TUNE ae_general=1: that one too)
+  int enc_dim = 100;   // floats per image grl_encode returns (auto-encoder handles: their encoding_dim)
   float* ae_x = nullptr;            // [B, 4096] minibatch of depth images (staged per step)
   float* ae_out = nullptr;          // [B, 4096] reconstruction of that minibatch
   std::vector<Op> ops_ae_fwd;       // forward half of ops_ae (grl_ae_reconstruct)

@@ -4,8 +4,26 @@
 // Depth auto-encoder training: encoders.py:90-124 network, :127 MSE, :130 Adam,
 // config/encoder.yaml (7/5/3 kernels, 32 filters, stride 2, encoding 100, lr 2e-4, batch 128).
 // Parameters are the 16 Keras tensors in model.h5 order; one step = forward, MSE, backward, Keras-Adam.
+//
+// Two routes, decided once at the top of plan_ae(): the TUNED one below is written for the shipped network (and taken by it alone);
+// plan_ae_general() at the end of this file builds the same step from geometry for every other network of the supported domain
+// (ae_geom.h), or for the shipped one under GRL_TUNE ae_general=1 (A/B measurements, tests).
+static bool cfg_ae_default(const grl_config& c) {      // all ae_* fields zero: the shipped network
+  return !c.ae_kernel[0] && !c.ae_kernel[1] && !c.ae_kernel[2] && !c.ae_filters[0] && !c.ae_filters[1] && !c.ae_filters[2] &&
+         !c.ae_encoding_dim && c.ae_alpha == 0.f;
+}
+static AeNet ae_net_of(const grl_config& c) {
+  if (cfg_ae_default(c)) return ae_shipped_net();
+  return AeNet{{c.ae_kernel[0], c.ae_kernel[1], c.ae_kernel[2]}, {c.ae_filters[0], c.ae_filters[1], c.ae_filters[2]}, c.ae_encoding_dim,
+               c.ae_alpha};
+}
+
 int grl_ctx::plan_ae() {
   const grl_config& c = cfg;
+  {
+    const AeNet net = ae_net_of(c);
+    if (!net.shipped() || sw.get(Sw::ae_general)) return plan_ae_general(net);
+  }
   cnn = false;
   B = c.batch_size; NA = std::max(1, c.act_batch); A = 1; L = 0;
   img_elems = 4096; F = 100; Fc = 0; ldf = 100; C_img = 1; hw = 64;
@@ -405,6 +423,343 @@ int grl_ctx::plan_ae() {
   dbg["z"] = {z, (int64_t)B * 100};
   dbg["e3"] = {e3, (int64_t)B * 2048};
   dbg["d5"] = {d5, (int64_t)B * 32 * 32 * 32};
+  dbg["grads"] = {grads, n_train};
+  dbg["adam_m"] = {adam_m, n_train};
+  dbg["adam_v"] = {adam_v, n_train};
+  return GRL_OK;
+}
+
+// --------------------------------------------------------------------------------------------------
+// The GENERAL route: the same training step, forward-only path and encode path for any network of ae_geom.h's domain, built
+// from geometry.  Every convolution is a 'valid' one over its input kept in a zero-bordered buffer (TensorFlow 'SAME' borders,
+// asymmetric for even kernels), so no launch needs per-tap validity masks -- a 9 x 9 kernel has more taps than a mask word
+// has bits.  Launches go through add_launch: igemm2 where a problem's tables allow 16-byte runs, the scalar-gather
+// igemm_kernel otherwise (named in the plan dump).  The output convolution keeps the tuned route's restructuring -- tap GEMM
+// over the pixels of d5, k^2-tap gather-sum (+ MSE), backward-data and weight gradient over the four sub-positions of the
+// up-sampling -- with tables instead of the 8-tap row trick (ae_general.h, ae_geom.h: AeOutTabs).  Not tuned for speed.
+int grl_ctx::plan_ae_general(const AeNet& net) {
+  const grl_config& c = cfg;
+  if (!ae_net_ok(net)) return fail(GRL_ERR_INVALID, ae_domain_text());
+  cnn = false;
+  B = c.batch_size; NA = std::max(1, c.act_batch); A = 1; L = 0;
+  const int D = net.dim, f0 = net.f[0], f1 = net.f[1], f2 = net.f[2], k0 = net.k[0], flat = 64 * f2;
+  img_elems = 4096; F = D; Fc = 0; ldf = D; C_img = 1; hw = 64; enc_dim = D;
+  const float LA = net.alpha;
+  const AeGeom G = ae_geometry(net);
+  plan_note("grl plan: ae general   k=%d/%d/%d f=%d/%d/%d dim=%d alpha=%g\n", net.k[0], net.k[1], net.k[2], f0, f1, f2, D, (double)LA);
+  // ---------------- parameter layout (Keras creation order, as in plan_ae)
+  int64_t ew[3], eb[3], dw[3], db[3];
+  for (int l = 0; l < 3; ++l) {
+    const std::string nm = "encoder/conv2d_" + std::to_string(l + 1);
+    ew[l] = add_var(nm + "/kernel", {G.enc[l].k, G.enc[l].k, G.enc[l].C, G.enc[l].F}, true);
+    eb[l] = add_var(nm + "/bias", {G.enc[l].F}, true);
+  }
+  const int64_t edw = add_var("encoder/dense_1/kernel", {flat, D}, true), edb = add_var("encoder/dense_1/bias", {D}, true);
+  const int64_t ddw = add_var("decoder/dense_2/kernel", {D, flat}, true), ddb = add_var("decoder/dense_2/bias", {flat}, true);
+  for (int l = 0; l < 3; ++l) {
+    const std::string nm = "decoder/conv2d_" + std::to_string(l + 4);
+    dw[l] = add_var(nm + "/kernel", {G.dec[l].k, G.dec[l].k, G.dec[l].C, G.dec[l].F}, true);
+    db[l] = add_var(nm + "/bias", {G.dec[l].F}, true);
+  }
+  n_train = n_params; tgt_off = n_params; vf_off = 0; n_polyak = 0; ent_off = 0;
+  // ---------------- arenas
+  params = st.f32(n_params);
+  adam_m = st.f32(n_train);
+  adam_v = st.f32(n_train);
+  sc = (DevScalars*)st.take(sizeof(DevScalars));
+  s_mean = (double*)st.take(8); s_std = (double*)st.take(8); s_dmean = (double*)st.take(8); s_dstd = (double*)st.take(8);
+  s_ret = (double*)st.take(8);
+  grads = gr.f32(n_train);
+  rp_obs = rp_next = rp_dobs = rp_dnext = rp_act = rp_rew = rp_done = rp.f32(4);   // no replay on this path
+  stg_n = std::max(NA, 64);
+  stg_obs = stg_next = stg_act = stg_rew = stg_done = wk.f32(4);
+  idx_buf = (int64_t*)wk.take(8); eps_buf = wk.f32(4);
+  for (int n = 0; n < 3; ++n) feat[n] = wk.f32(4);
+  const float* P = params;
+  auto T = [&](int Bn, int h, int ch) { return wk.f32((int64_t)Bn * h * h * ch); };
+  auto TP = [&](int Bn, const AeConv& cv) {            // zero-bordered input buffer of a convolution (border written once)
+    const int64_t n = cv.bordered_elems(Bn);
+    float* b = wk.f32(n);
+    zero_once.push_back({b, (size_t)n * 4});
+    return b;
+  };
+  auto TZ = [&](int Bn, int h, int ch) {               // a gradient image whose launch may leave pixels unwritten: kept zero
+    float* b = T(Bn, h, ch);
+    zero_once.push_back({b, (size_t)Bn * h * h * ch * 4});
+    return b;
+  };
+  auto valid_geom = [](const AeConv& cv) { return ConvGeom{cv.Hp(), cv.Hp(), cv.C, cv.k, cv.k, cv.S, 0, cv.OH, cv.OH, cv.F}; };
+  auto same_geom = [](const AeConv& cv) { return ConvGeom{cv.H, cv.H, cv.C, cv.k, cv.k, cv.S, cv.lo, cv.OH, cv.OH, cv.F}; };
+  auto elem = [&](std::vector<Op>& ops, const char* tag, std::function<void(hipStream_t)> f) {
+    Op op; op.tag = tag; op.run = std::move(f);
+    ops.push_back(op);
+  };
+  std::string scalar;                                   // launches that took the scalar-gather kernel
+  auto launch = [&](std::vector<Op>& ops, const std::string& tag, int variant, std::vector<IgemmProb> probs, const std::string& what) {
+    if (probs.empty()) return;
+    add_launch(ops, tag, variant, probs);
+    if (!launches.back()->v2 && !what.empty()) scalar += " " + what;
+  };
+  auto up = [&](const float* h, float* u, int H, const AeConv& cv) {
+    const int Bn = B, C = cv.C, lo = cv.lo, hi = cv.hi;
+    elem(ops_ae, "ae_upsample", [=](hipStream_t s) {
+      const long quads = (long)Bn * 2 * H * 2 * H * (C / 4);
+      hipLaunchKernelGGL(upsample2_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, h, u, Bn, H, H, C, lo, hi);
+    });
+  };
+  auto up_bwd = [&](const float* gu, const float* h, float* gh, int H, int C) {
+    const int Bn = B;
+    elem(ops_ae, "ae_upsample_bwd", [=](hipStream_t s) {
+      const long n = (long)Bn * H * H * C;
+      hipLaunchKernelGGL(upsample2_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, gu, h, gh, Bn, H, H, C, LA);
+    });
+  };
+  // ---------------- activations (NHWC) and gradients
+  ae_x = T(B, 64, 1);
+  float *x_p = TP(B, G.enc[0]), *e1_p = TP(B, G.enc[1]), *e2_p = TP(B, G.enc[2]);
+  float *e3 = T(B, 8, f2), *z = wk.f32((int64_t)B * D), *dh = T(B, 8, f2);
+  float *u4 = TP(B, G.dec[0]), *d4 = T(B, 16, f1), *u5 = TP(B, G.dec[1]), *d5 = T(B, 32, f0), *out = T(B, 64, 1);
+  float *g_d5 = T(B, 32, f0), *g_u5 = TZ(B, 32, f1), *g_d4 = T(B, 16, f1), *g_u4 = TZ(B, 16, f2), *g_dh = T(B, 8, f2);
+  float *g_z = wk.f32((int64_t)B * D), *g_e3 = T(B, 8, f2), *g_e2 = TZ(B, 16, f1), *g_e1 = TZ(B, 32, f0);
+  const AeOutTabs ot = ae_out_tabs(B, k0);
+  const int64_t gpad_n = (int64_t)B * ot.Gp * ot.Gp;
+  float* g_pad = wk.f32(gpad_n);
+  zero_once.push_back({g_pad, (size_t)gpad_n * 4});
+  const int n_w6 = k0 * k0 * f0;
+  float* W6x4 = wk.f32((int64_t)4 * n_w6);
+  ConvGeom gev[3], gdv[2];
+  ConvFwdTabs fte[3], ftd[2];
+  for (int l = 0; l < 3; ++l) { gev[l] = valid_geom(G.enc[l]); fte[l] = conv_fwd_tabs(gev[l], B); }
+  for (int l = 0; l < 2; ++l) { gdv[l] = valid_geom(G.dec[l]); ftd[l] = conv_fwd_tabs(gdv[l], B); }
+  // =============================================================== forward
+  {
+    const float* W6 = P + dw[2];
+    const int n_prep = (n_w6 + 255) / 256, lo = G.enc[0].lo, Hp = G.enc[0].Hp();
+    const long total = (long)B * 4096;
+    const float* xin = ae_x;
+    elem(ops_ae, "ae_kernel_prep", [=](hipStream_t s) {
+      hipLaunchKernelGGL(aeg_prep_kernel, dim3((unsigned)(n_prep + (total + 255) / 256)), dim3(256), 0, s, W6, W6x4, n_w6, n_prep, xin, x_p,
+                         total, lo, Hp);
+    });
+  }
+  // encoder convolutions: l = 0, 1 write the zero-bordered input of the next one (output row table), l = 2 the plain e3
+  auto encoder = [&](std::vector<Op>& ops, const char* tag, int Bn, const ConvFwdTabs* ft, float* const in[3], float* const o[3], bool note) {
+    for (int l = 0; l < 3; ++l) {
+      IgemmProb p = conv_fwd(in[l], ft[l], gev[l], P + ew[l], P + eb[l], o[l], ACT_LEAKY, LA);
+      if (l < 2) {
+        const AeConv& nx = G.enc[l + 1];
+        p.c_tab_i = upload_vec(wk, ae_bordered_rows(Bn, nx.H, nx.lo, nx.hi, nx.C));
+        p.vflags |= VF_CT4;
+      }
+      launch(ops, tag, 0, {p}, note ? "conv2d_" + std::to_string(l + 1) : "");
+    }
+  };
+  {
+    float* const in[3] = {x_p, e1_p, e2_p};
+    float* const o[3] = {e1_p, e2_p, e3};
+    encoder(ops_ae, "ae_enc_conv", B, fte, in, o, true);
+  }
+  {
+    IgemmProb p = dense_fwd(e3, flat, flat, nullptr, 0, 0, B, P + edw, D, P + edb, z, D, ACT_LEAKY);
+    p.act_alpha = LA;
+    launch(ops_ae, "ae_dense", 0, {p}, "");
+    IgemmProb q = dense_fwd(z, D, D, nullptr, 0, 0, B, P + ddw, flat, P + ddb, dh, flat, ACT_LEAKY);
+    q.act_alpha = LA;
+    launch(ops_ae, "ae_dense", 0, {q}, "");
+  }
+  up(dh, u4, 8, G.dec[0]);
+  launch(ops_ae, "ae_dec_conv", 0, {conv_fwd(u4, ftd[0], gdv[0], P + dw[0], P + db[0], d4, ACT_LEAKY, LA)}, "conv2d_4");
+  up(d4, u5, 16, G.dec[1]);
+  launch(ops_ae, "ae_dec_conv", 0, {conv_fwd(u5, ftd[1], gdv[1], P + dw[1], P + db[1], d5, ACT_LEAKY, LA)}, "conv2d_5");
+  // output convolution: T[tap, q] = W6[tap, :] . d5[q, :] (M = k0^2), then the k0^2-tap gather-sum
+  const long ldT = (long)B * 1024;
+  float* Tt = wk.f32((int64_t)k0 * k0 * ldT);
+  launch(ops_ae, "ae_out_conv", 1, {dense_bwd({{P + dw[2], f0, f0, d5}}, k0 * k0, 0, (int)ldT, Tt, (int)ldT, nullptr)}, "");
+  const long npix = (long)B * 4096;
+  const int n_part = (int)((npix + 255) / 256);
+  const int olo = G.dec[2].lo, ohi = G.dec[2].hi;
+  {
+    const float* b6 = P + db[2];
+    ae_out = out;
+    ops_ae_fwd = ops_ae;
+    elem(ops_ae_fwd, "ae_out_tapsum", [=](hipStream_t s) {
+      hipLaunchKernelGGL(aeg_tapsum_kernel, dim3((unsigned)n_part), dim3(256), 0, s, (const float*)Tt, ldT, b6, out, npix, k0, olo);
+    });
+  }
+  // =============================================================== loss
+  {
+    float* part = wk.f32(n_part);
+    float* partial_g = wk.f32(n_part);
+    AegTapMseArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    ta.T = Tt; ta.ldT = ldT; ta.bias = P + db[2]; ta.n_pix = npix; ta.k = k0; ta.lo = olo; ta.hi = ohi; ta.Gp = ot.Gp;
+    ta.out = out; ta.x = ae_x; ta.gpad = g_pad; ta.partial = part; ta.partial_g = partial_g;
+    const float lr = c.lr;
+    DevScalars* scp = sc;
+    float* gb6 = grads + db[2];
+    elem(ops_ae, "ae_out_tapsum_mse", [=](hipStream_t s) {
+      hipLaunchKernelGGL(aeg_tapsum_mse_kernel, dim3(n_part), dim3(256), 0, s, ta);
+      hipLaunchKernelGGL(ae_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)part, (const float*)partial_g, n_part, npix, lr, scp, gb6);
+    });
+  }
+  // =============================================================== backward
+  std::vector<IgemmProb> wgc, wgd;
+  auto split_of = [](int M, int N, int K) {             // reduction splits: ~512 rows each, slabs of one problem within 16 MB
+    const int64_t cap = std::max<int64_t>(1, ((int64_t)4 << 20) / ((int64_t)M * N));
+    return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(64, cap), K / 512));
+  };
+  auto cw = [&](const float* x, const ConvFwdTabs& t, const ConvGeom& g, const float* gy, int64_t w_off, int64_t b_off) {
+    IgemmProb p = conv_wgrad(x, t, g, gy, nullptr, split_of(g.K() + 1, g.Cout, t.M));
+    p.c = wk.f32(p.slab_stride * p.split);
+    add_wgrad(wgc, p, w_off, 0, g.K(), b_off);
+  };
+  // backward-data of a convolution into the plain [B, H, H, C] gradient image dx.  exact: one problem per set of existing taps
+  // (stride 1: up to k x k sets; no masks); otherwise the parity form with validity masks (stride 2: at most 5 x 5 tap positions).
+  // bordered_mask: the activations whose LeakyReLU gradient applies, in their zero-bordered form (row table of their own)
+  auto cb = [&](const char* tag, const float* gy, const AeConv& cv, const float* w, float* dx, const float* bordered_mask, bool exact,
+                const std::string& what) {
+    const ConvGeom g = same_geom(cv);
+    std::vector<IgemmProb> pr;
+    std::vector<int32_t> untouched;
+    for (auto& cl : exact ? conv_bwd_tabs_exact(g, B, &untouched) : conv_bwd_tabs(g, B)) {
+      IgemmProb p = conv_bwd(gy, cl, g, w, dx, bordered_mask);
+      p.act_alpha = LA;
+      if (bordered_mask) {
+        std::vector<int32_t> mt(cl.ct_host.size());
+        const int Hp = cv.Hp();
+        for (size_t i = 0; i < mt.size(); ++i) {
+          const int ct = cl.ct_host[i];
+          if (ct < 0) { mt[i] = 0; continue; }
+          const int pix = ct / g.C, n = pix / (g.H * g.W), y = (pix / g.W) % g.H, x = pix % g.W;
+          mt[i] = ((n * Hp + y + cv.lo) * Hp + x + cv.lo) * g.C;
+        }
+        p.m_tab_i = upload_vec(wk, mt);
+      }
+      pr.push_back(p);
+    }
+    launch(ops_ae, tag, 1, pr, what);
+  };
+  {
+    // output convolution, weight gradient: dW[tap, c] = sum over the sub-positions s of a 2 x 2 block and the pixels q of d5 of
+    // gpad[pix(q) + off(s, tap)] d5[q, c] -- four GEMMs (M = k0^2, N = F0, K = pixels of d5), their slabs summed as one list
+    const int32_t* d_pix = upload_vec(wk, ot.pix);
+    std::vector<IgemmProb> four;
+    float* slabs = nullptr;
+    int per = 0;
+    int64_t sstride = 0;
+    for (int sp = 0; sp < 4; ++sp) {
+      IgemmProb p = blank();
+      p.M = k0 * k0; p.N = f0; p.K = B * 1024;
+      p.p_base[0] = g_pad; p.p_tab_i = upload_vec(wk, ot.wg_i[sp]); p.p_tab_r = d_pix; single_part(p);
+      p.q_base[0] = d5; p.q_ld_r[0] = f0; p.q_ld_j[0] = 1;
+      p.ldc = f0;
+      set_split(p, split_of(p.M, p.N, p.K));
+      if (sp == 0) { per = p.split; sstride = p.slab_stride; slabs = wk.f32(sstride * per * 4); }
+      p.c = slabs + (int64_t)sp * per * sstride;
+      four.push_back(p);
+    }
+    ReduceDesc r;
+    memset(&r, 0, sizeof(r));
+    r.src = slabs; r.splits = 4 * per; r.slab_stride = sstride;
+    r.dst = grads + dw[2]; r.n = k0 * k0 * f0;
+    reduces.push_back(r);
+    launch(ops_ae, "ae_out_wgrad", 0, four, "conv2d_6/wgrad");
+  }
+  {
+    // backward-data of the output convolution and of the up-sampling in front of it, as one product:
+    //   g_d5[q, c] = LeakyReLU'(d5[q, c]) sum_{s, tap} gpad[pix(q) + off(s, tap)] W6[tap, c]       (K = 4 k0^2, Q = W6x4)
+    IgemmProb p = blank();
+    p.M = B * 1024; p.N = f0; p.K = 4 * k0 * k0;
+    p.p_base[0] = g_pad; p.p_tab_i = upload_vec(wk, ot.pix); p.p_tab_r = upload_vec(wk, ot.bwd_r); single_part(p);
+    p.q_base[0] = W6x4; p.q_ld_r[0] = f0; p.q_ld_j[0] = 1;
+    p.c = g_d5; p.ldc = f0;
+    p.relu_mask = d5; p.act_alpha = LA;
+    set_split(p, 1);
+    launch(ops_ae, "ae_out_conv_bwd", 0, {p}, "conv2d_6/bwd");
+  }
+  cw(u5, ftd[1], gdv[1], g_d5, dw[1], db[1]);
+  cb("ae_dec_conv_bwd", g_d5, G.dec[1], P + dw[1], g_u5, nullptr, true, "conv2d_5/bwd");
+  up_bwd(g_u5, d4, g_d4, 16, f1);
+  cw(u4, ftd[0], gdv[0], g_d4, dw[0], db[0]);
+  cb("ae_dec_conv_bwd", g_d4, G.dec[0], P + dw[0], g_u4, nullptr, true, "conv2d_4/bwd");
+  up_bwd(g_u4, dh, g_dh, 8, f2);
+  {
+    IgemmProb p = dense_wgrad(z, D, D, true, g_dh, flat, flat, B, nullptr, 1);
+    p.c = wk.f32(p.slab_stride * p.split);
+    add_wgrad(wgd, p, ddw, 0, D, ddb);
+    IgemmProb b = dense_bwd({{g_dh, flat, flat, P + ddw}}, B, 0, D, g_z, D, z);
+    b.act_alpha = LA;
+    launch(ops_ae, "ae_dense_bwd", 1, {b}, "");
+    IgemmProb p2 = dense_wgrad(e3, flat, flat, true, g_z, D, D, B, nullptr, 1);
+    p2.c = wk.f32(p2.slab_stride * p2.split);
+    add_wgrad(wgd, p2, edw, 0, flat, edb);
+    IgemmProb b2 = dense_bwd({{g_z, D, D, P + edw}}, B, 0, flat, g_e3, flat, e3);
+    b2.act_alpha = LA;
+    launch(ops_ae, "ae_dense_bwd", 1, {b2}, "");
+  }
+  cw(e2_p, fte[2], gev[2], g_e3, ew[2], eb[2]);
+  cb("ae_enc_conv_bwd", g_e3, G.enc[2], P + ew[2], g_e2, e2_p, false, "conv2d_3/bwd");
+  cw(e1_p, fte[1], gev[1], g_e2, ew[1], eb[1]);
+  cb("ae_enc_conv_bwd", g_e2, G.enc[1], P + ew[1], g_e1, e1_p, false, "conv2d_2/bwd");
+  cw(x_p, fte[0], gev[0], g_e1, ew[0], eb[0]);
+  {
+    std::vector<IgemmProb> ok_c, rest;
+    for (auto& p : wgc) (v2_prob_ok(p, 2) && (p.K % 4) == 0 ? ok_c : rest).push_back(p);
+    launch(ops_ae, "ae_wgrad_conv", 2, ok_c, "");
+    launch(ops_ae, "ae_wgrad_small", 2, rest, "wgrad");
+    launch(ops_ae, "ae_wgrad_dense", 2, wgd, "");
+  }
+  {
+    std::vector<int2> rt = reduce_tiles();
+    d_reduces = upload_vec(wk, reduces);
+    int2* d_rt = upload_vec(wk, rt);
+    const int ntiles = (int)rt.size();
+    ReduceDesc* dr = d_reduces;
+    LossArgs none;
+    memset(&none, 0, sizeof(none));
+    elem(ops_ae, "reduce_slabs", [=](hipStream_t s) {
+      hipLaunchKernelGGL(reduce_slabs_kernel, dim3(ntiles), dim3(256), 0, s, dr, d_rt, ntiles, none, 0, AdamArgs{}, 0);
+    });
+  }
+  {
+    grl_ctx* self = this;
+    elem(ops_ae, "adam", [self](hipStream_t s) {
+      const AdamArgs aa = self->adam_args(1.f, false, 1e-7f);   // Keras epsilon
+      const int blocks = (int)std::min<int64_t>(2048, (self->n_train + 255) / 256);
+      hipLaunchKernelGGL(adam_polyak_kernel, dim3(blocks), dim3(256), 0, s, aa);
+    });
+  }
+  // =============================================================== encode path (batch NA) on the trained weights
+  {
+    ex_in = wk.f32((int64_t)NA * 4096);
+    float *ex_p = TP(NA, G.enc[0]), *c1_p = TP(NA, G.enc[1]), *c2_p = TP(NA, G.enc[2]);
+    ec1 = c1_p; ec2 = c2_p;
+    ec3 = T(NA, 8, f2); eout = wk.f32((int64_t)NA * D);
+    {
+      const long total = (long)NA * 4096;
+      const int lo = G.enc[0].lo, Hp = G.enc[0].Hp();
+      const float* xin = ex_in;
+      elem(ops_enc, "enc_pad", [=](hipStream_t s) {
+        hipLaunchKernelGGL(aeg_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)nullptr, (float*)nullptr, 0, 0,
+                           xin, ex_p, total, lo, Hp);
+      });
+    }
+    ConvFwdTabs ft[3];
+    for (int l = 0; l < 3; ++l) ft[l] = conv_fwd_tabs(gev[l], NA);
+    float* const in[3] = {ex_p, c1_p, c2_p};
+    float* const o[3] = {c1_p, c2_p, ec3};
+    encoder(ops_enc, "enc_conv", NA, ft, in, o, false);
+    IgemmProb p = dense_fwd(ec3, flat, flat, nullptr, 0, 0, NA, P + edw, D, P + edb, eout, D, ACT_LEAKY);
+    p.act_alpha = LA;
+    launch(ops_enc, "enc_dense", 0, {p}, "");
+    for (int k = 0; k < 8; ++k) enc_w[k] = nullptr;
+    enc_loaded = true;
+  }
+  if (!scalar.empty()) plan_note("grl plan: ae general   scalar-gather kernel:%s\n", scalar.c_str());
+  dbg["out"] = {out, (int64_t)B * 4096};
+  dbg["z"] = {z, (int64_t)B * D};
+  dbg["e3"] = {e3, (int64_t)B * flat};
+  dbg["d5"] = {d5, (int64_t)B * 32 * 32 * f0};
   dbg["grads"] = {grads, n_train};
   dbg["adam_m"] = {adam_m, n_train};
   dbg["adam_v"] = {adam_v, n_train};

@@ -27,6 +27,7 @@ class GrlConfig(C.Structure):
         ("q_per", C.c_int32), ("q_per_alpha", C.c_float), ("q_per_eps", C.c_float),
         ("replay_rgb_u8", C.c_int32), ("q_per_stratified", C.c_int32), ("q_per_alpha64", C.c_double),
         ("q_loss_sum_branches", C.c_int32), ("q_layer_norm", C.c_int32),
+        ("ae_kernel", C.c_int32 * 3), ("ae_filters", C.c_int32 * 3), ("ae_encoding_dim", C.c_int32), ("ae_alpha", C.c_float),
     ]
 
 
@@ -205,11 +206,22 @@ def param_table(lib, handle):
     return out
 
 
-def make_ae_config(batch_size=128, lr=2e-4, act_batch=16):
-    """Depth auto-encoder training handle (config/encoder.yaml: batch 128, lr 2e-4)."""
+AE_SHIPPED_NET = ((7, 5, 3), (32, 32, 32), 100, 0.1)      # config/encoder.yaml: kernel sizes, filters, encoding_dim, alpha
+
+
+def make_ae_config(batch_size=128, lr=2e-4, act_batch=16, net=None):
+    """Depth auto-encoder training handle (config/encoder.yaml: batch 128, lr 2e-4).  net = (kernel sizes, filters,
+    encoding_dim, alpha) of a three-layer stride-2 encoder; None or the shipped values leave the ae_* fields zero (the shipped
+    network: tuned launch plan, configuration hash of earlier checkpoints)."""
     cfg = make_config("mlp", obs_dim=4096, act_dim=1, layers=(1,), batch_size=batch_size, act_batch=act_batch,
                       replay_capacity=1, normalize=False, lr=lr)
     cfg.algo = 3
+    if net is not None:
+        ks, fs, dim, alpha = net
+        if (tuple(ks), tuple(fs), dim, alpha) != AE_SHIPPED_NET:
+            for i in range(3):
+                cfg.ae_kernel[i], cfg.ae_filters[i] = int(ks[i]), int(fs[i])
+            cfg.ae_encoding_dim, cfg.ae_alpha = int(dim), float(alpha)
     return cfg
 
 

@@ -1,8 +1,9 @@
 """Depth auto-encoder on the HIP engine: the call surface of
 /root/reference/manipulation_main/gripperEnv/encoders.py (`SimpleAutoEncoder(config)`, `.train(inputs,
 targets, batch_size, epochs, model_dir)` :40-50, `.test` :52-53, `.predict` :55-57, `.encode` :59-61,
-`.load_weights(model_dir)` :26-30, `.encoding_shape` :63-65) for the network of :70-136 and
-config/encoder.yaml.  Training (forward, MSE, backward, Keras-Adam) runs in libgrl.so (GRL_ALGO_AE);
+`.load_weights(model_dir)` :26-30, `.encoding_shape` :63-65) for the network of :70-136 as
+config/encoder.yaml describes it (three stride-2 layers; `net_of_config` states the supported sizes).
+Training (forward, MSE, backward, Keras-Adam) runs in libgrl.so (GRL_ALGO_AE);
 this file owns the epoch loop Keras' `Model.fit` provides in the reference: shuffling, the 10 %
 validation split, CSV history, best-weights checkpoint and EarlyStopping(patience=25).
 
@@ -28,11 +29,40 @@ PARAM_NAMES = ["encoder/conv2d_1/kernel", "encoder/conv2d_1/bias", "encoder/conv
                "decoder/conv2d_5/kernel", "decoder/conv2d_5/bias", "decoder/conv2d_6/kernel", "decoder/conv2d_6/bias"]
 
 
-def glorot_uniform_params(seed=0):
+SHIPPED_NET = _capi.AE_SHIPPED_NET
+DOMAIN = ("the HIP engine implements auto-encoders of three encoder layers with strides 2 on a 64x64x1 image: kernel_size 1..9, "
+          "filters a multiple of 4 in 4..64, encoding_dim 1..1024, 0 <= alpha < 1 (the reference's shipped network, "
+          "config/encoder.yaml, among them)")
+
+
+def net_of_config(config):
+    """(kernel sizes, filters, encoding_dim, alpha) of an encoder.yaml dictionary (encoders.py:85-87); NotImplementedError
+    outside the supported domain."""
+    net = list(config.get("network", []))
+    dim, alpha = config.get("encoding_dim", 100), config.get("alpha", 0.1)
+    if len(net) != 3 or any(l.get("strides", 1) != 2 for l in net):
+        raise NotImplementedError(DOMAIN)
+    ks, fs = tuple(l["kernel_size"] for l in net), tuple(l["filters"] for l in net)
+    ok = all(isinstance(k, (int, np.integer)) and 1 <= k <= 9 for k in ks) and \
+        all(isinstance(f, (int, np.integer)) and 4 <= f <= 64 and f % 4 == 0 for f in fs) and \
+        isinstance(dim, (int, np.integer)) and 1 <= dim <= 1024 and 0.0 <= float(alpha) < 1.0
+    if not ok:
+        raise NotImplementedError(DOMAIN)
+    return tuple(int(k) for k in ks), tuple(int(f) for f in fs), int(dim), float(alpha)
+
+
+def param_shapes(net=None):
+    """Shapes of the 16 Keras tensors (PARAM_NAMES order) of a network (encoders.py:94-124)."""
+    (k0, k1, k2), (f0, f1, f2), dim, _ = net or SHIPPED_NET
+    flat = 64 * f2
+    return [(k0, k0, 1, f0), (f0,), (k1, k1, f0, f1), (f1,), (k2, k2, f1, f2), (f2,), (flat, dim), (dim,),
+            (dim, flat), (flat,), (k2, k2, f2, f1), (f1,), (k1, k1, f1, f0), (f0,), (k0, k0, f0, 1), (1,)]
+
+
+def glorot_uniform_params(seed=0, net=None):
     """Keras defaults (encoders.py builds every layer with them): glorot_uniform kernels, zero biases."""
     rng = np.random.default_rng(seed)
-    shapes = [(7, 7, 1, 32), (32,), (5, 5, 32, 32), (32,), (3, 3, 32, 32), (32,), (2048, 100), (100,),
-              (100, 2048), (2048,), (3, 3, 32, 32), (32,), (5, 5, 32, 32), (32,), (7, 7, 32, 1), (1,)]
+    shapes = param_shapes(net)
     P = {}
     for name, shp in zip(PARAM_NAMES, shapes):
         if name.endswith("bias"):
@@ -47,8 +77,10 @@ def glorot_uniform_params(seed=0):
 class AeEngine(SacEngine):
     """Handle of a GRL_ALGO_AE engine: parameters = the 16 Keras tensors, one call = n minibatch updates."""
 
-    def __init__(self, batch_size=128, lr=2e-4, act_batch=16, backend=None, lib_path=None, device="cuda:0"):
-        super().__init__(_capi.make_ae_config(batch_size, lr, act_batch), backend=backend, lib_path=lib_path, device=device)
+    def __init__(self, batch_size=128, lr=2e-4, act_batch=16, backend=None, lib_path=None, device="cuda:0", net=None):
+        super().__init__(_capi.make_ae_config(batch_size, lr, act_batch, net=net), backend=backend, lib_path=lib_path, device=device)
+        self.net = net or SHIPPED_NET
+        self.encoding_dim = int(self.net[2])
 
     def train_batches(self, imgs):
         """imgs [n_steps*B, 64, 64, 1] float32 (host): n_steps updates; returns the loss of the last one."""
@@ -114,17 +146,13 @@ class SimpleAutoEncoder:
         return super().__new__(cls)
 
     def __init__(self, config, backend=None, lib_path=None, device="cuda:0", seed=0):
-        net = config.get("network", [])
-        want = [(32, 7, 2), (32, 5, 2), (32, 3, 2)]
-        got = [(l["filters"], l["kernel_size"], l["strides"]) for l in net]
-        if got != want or config.get("encoding_dim", 100) != 100 or config.get("alpha", 0.1) != 0.1:
-            raise NotImplementedError("the HIP engine implements the reference's shipped network (config/encoder.yaml)")
+        self.net = net_of_config(config)
         self.config = config
         self.act_batch = 16                # observations one grl_encode call takes (`ensure_act_batch`)
         self._mk = lambda bs: AeEngine(bs, float(config.get("learning_rate", 2e-4)), act_batch=self.act_batch, backend=backend,
-                                       lib_path=lib_path, device=device)
+                                       lib_path=lib_path, device=device, net=self.net)
         self.engine = None
-        self._params = glorot_uniform_params(seed)
+        self._params = glorot_uniform_params(seed, self.net)
         self._bs = None
         self.model_dir = None              # where `load_weights` read from
         _LIVE.add(self)
@@ -155,8 +183,13 @@ class SimpleAutoEncoder:
         return self.engine.get_parameters() if self.engine is not None else dict(self._params)
 
     def set_weights(self, params):
+        new = {k: np.asarray(params[k], np.float32) for k in PARAM_NAMES}
+        for k, shp in zip(PARAM_NAMES, param_shapes(self.net)):      # the first tensor that does not fit the configured network
+            if tuple(new[k].shape) != shp:
+                raise ValueError("weights do not match the configured network: %s has shape %s, the configuration gives %s"
+                                 % (k, tuple(new[k].shape), shp))
         self.model_dir = None
-        self._params = {k: np.asarray(params[k], np.float32) for k in PARAM_NAMES}
+        self._params = new
         if self.engine is not None:
             self.engine.set_parameters(self._params)
 
@@ -243,7 +276,7 @@ class SimpleAutoEncoder:
 
     @property
     def encoding_shape(self):
-        return (100,)
+        return (self.net[2],)
 
 
 class DeferredEncoder:
@@ -262,6 +295,10 @@ class DeferredEncoder:
 
     def __init__(self, config=None):
         self.config = dict(config) if config else None
+        # what the parent's batched encoder will hand out per image for this configuration (`VecBatchedEncoder` sizes its
+        # observation space from the parent's `SimpleAutoEncoder.encoding_shape`, the same number); an unsupported
+        # configuration fails here, in the worker, as it would in `SimpleAutoEncoder`
+        self.encoded_shape = (net_of_config(self.config)[2],) if self.config else (SHIPPED_NET[2],)
         self.model_dir = None
         self._record = {"config": self.config, "model_dir": None}
         _DEFERRED.append(self._record)

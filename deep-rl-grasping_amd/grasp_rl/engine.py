@@ -644,10 +644,12 @@ class SacEngine:
         nums = (C.c_int64 * 8)(*[a.size for a in arrs])
         check(self.lib, self.lib.grl_encoder_load(self.h, ptrs, nums, 8))
 
+    encoding_dim = 100       # floats per image `encode` returns (auto-encoder handles: their configured encoding_dim)
+
     def encode(self, depth):
         depth = np.ascontiguousarray(depth, dtype=np.float32).reshape(-1, 64, 64, 1)
         n = depth.shape[0]
-        out = np.empty((n, 100), np.float32)
+        out = np.empty((n, self.encoding_dim), np.float32)
         check(self.lib, self.lib.grl_encode(self.h, depth.ctypes.data, n, out.ctypes.data))
         return out
 

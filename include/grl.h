@@ -122,6 +122,17 @@ typedef struct grl_config {
      Appended last: it occupies what used to be the struct's tail padding, so every earlier field and sizeof(grl_config)
      stay where they were -- a caller that does not zero the struct now has to set it.  Must be 0 on SAC handles. */
   int32_t q_layer_norm;
+  /* Auto-encoder handles (algo 3): the network of encoders.py:85-124 as config/encoder.yaml describes it -- three encoder
+     layers of stride 2 on a 64x64x1 image with `ae_kernel[l]` (1..9, TensorFlow 'SAME' borders) and `ae_filters[l]` (a multiple
+     of 4 in 4..64), a bottleneck of `ae_encoding_dim` (1..1024) and LeakyReLU slope `ae_alpha` (0 <= alpha < 1); the decoder
+     mirrors it.  ALL of them zero: the shipped network (7/5/3, 32/32/32, 100, 0.1), which runs the tuned launch plan; any
+     other supported network runs the general one.  Otherwise every field is taken as written.  Appended
+     last: earlier fields keep their offsets, sizeof(grl_config) grows by 32 bytes (a caller built against the earlier header has
+     to be rebuilt; grl_state_import still takes blobs that hold the shorter struct).  Must all be 0 on handles of another algo. */
+  int32_t ae_kernel[3];
+  int32_t ae_filters[3];
+  int32_t ae_encoding_dim;
+  float ae_alpha;
 } grl_config;
 
 /* byte sizes of the four caller-provided device arenas */
