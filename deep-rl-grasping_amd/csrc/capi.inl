@@ -3,6 +3,14 @@
 // ==================================================================================================
 // C ABI
 // ==================================================================================================
+// PPO handles (plan_ppo.inl) hold a rollout, not a replay ring, and have one update form: the entry points of the other
+// algorithms stop here, before anything moves
+#define NOT_ON_PPO(h, what)                                                                                                       \
+  do {                                                                                                                            \
+    if ((h) && (h)->cfg.algo == GRL_ALGO_PPO)                                                                                     \
+      return fail(GRL_ERR_STATE, what " is not defined on a PPO handle (PPO handles: grl_ppo_step / _rewards / _finish / _train, grl_act)"); \
+  } while (0)
+
 static int check_cfg(const grl_config* c) {
   if (!c) return fail(GRL_ERR_INVALID, "null config");
   if (c->algo == GRL_ALGO_AE) {
@@ -19,7 +27,20 @@ static int check_cfg(const grl_config* c) {
   if (c->batch_size < 1 || c->batch_size > 65536) return fail(GRL_ERR_INVALID, "batch_size out of range");
   if (c->act_dim < 1 || c->act_dim > 64) return fail(GRL_ERR_INVALID, "act_dim out of range");
   if (c->replay_capacity < 1) return fail(GRL_ERR_INVALID, "replay_capacity must be >= 1");
-  if (c->algo < 0 || c->algo > 3) return fail(GRL_ERR_INVALID, "algo must be 0..3");
+  if (c->algo < 0 || c->algo > 4) return fail(GRL_ERR_INVALID, "algo must be 0..4");
+  if (c->algo == GRL_ALGO_PPO) {
+    if (c->extractor != GRL_EXTRACTOR_MLP) return fail(GRL_ERR_INVALID, "PPO runs on flattened observations (MLP extractor)");
+    if (c->obs_dim < 1 || c->obs_dim > 64 * 64 * 5) return fail(GRL_ERR_INVALID, "PPO: obs_dim must be 1..20480");
+    for (int l = 0; l < c->n_layers; ++l)
+      if (c->layers[l] > 1024) return fail(GRL_ERR_INVALID, "PPO: tower widths must be 1..1024");
+    if (c->normalize != 0) return fail(GRL_ERR_INVALID, "PPO: normalize must be 0 (VecNormalize stays on the host)");
+    if (c->act_batch < 1) return fail(GRL_ERR_INVALID, "PPO: act_batch must equal n_envs");
+    if (c->q_branches || c->q_bins || c->q_n_common || c->q_n_branch || c->q_n_value || c->q_huber || c->q_double || c->q_grad_clip != 0.f ||
+        c->q_trunk_scale != 0.f || c->q_per || c->q_per_alpha != 0.f || c->q_per_eps != 0.f || c->q_per_stratified || c->q_per_alpha64 != 0.0 ||
+        c->q_loss_sum_branches || c->q_layer_norm || c->replay_rgb_u8)
+      return fail(GRL_ERR_INVALID, "PPO: every q_* field and replay_rgb_u8 must be 0");
+    return GRL_OK;
+  }
   if (c->algo != GRL_ALGO_SAC) {
     if (c->extractor != GRL_EXTRACTOR_MLP) return fail(GRL_ERR_INVALID, "DQN/BDQ run on vector observations (MLP extractor)");
     if (c->q_branches < 1 || c->q_branches > 16 || c->q_branches != c->act_dim)
@@ -60,11 +81,29 @@ extern "C" {
 const char* grl_last_error(void) { return g_err.c_str(); }
 int grl_version(void) { return 1; }
 
-int grl_query_sizes(const grl_config* cfg, grl_sizes* out) {
-  if (int e = check_cfg(cfg)) return e;
+static int check_ppo(const grl_config* c, const grl_ppo_config* p) {
+  if (int e = check_cfg(c)) return e;
+  if (c->algo != GRL_ALGO_PPO) return fail(GRL_ERR_INVALID, "grl_ppo_query_sizes / grl_ppo_create take a grl_config with algo = GRL_ALGO_PPO");
+  if (!p) return fail(GRL_ERR_INVALID, "null PPO config");
+  if (p->n_envs < 1 || p->n_steps < 1 || (int64_t)p->n_envs * p->n_steps > (1 << 22)) return fail(GRL_ERR_INVALID, "PPO: n_envs, n_steps must be >= 1 and n_envs * n_steps <= 4194304");
+  const int64_t R = (int64_t)p->n_envs * p->n_steps;
+  if (c->act_batch != p->n_envs) return fail(GRL_ERR_INVALID, "PPO: act_batch must equal n_envs");
+  if (c->replay_capacity != R) return fail(GRL_ERR_INVALID, "PPO: replay_capacity must equal n_envs * n_steps");
+  if (R % c->batch_size) return fail(GRL_ERR_INVALID, "PPO: batch_size (the minibatch rows) must divide n_envs * n_steps");
+  if (p->n_vf_layers < 1 || p->n_vf_layers > GRL_MAX_LAYERS) return fail(GRL_ERR_INVALID, "PPO: n_vf_layers out of range");
+  for (int l = 0; l < p->n_vf_layers; ++l)
+    if (p->vf_layers[l] < 1 || p->vf_layers[l] > 1024) return fail(GRL_ERR_INVALID, "PPO: tower widths must be 1..1024");
+  if (!(p->lam >= 0.f && p->lam <= 1.f)) return fail(GRL_ERR_INVALID, "PPO: lam must be in [0, 1]");
+  if (!(p->clip_range >= 0.f)) return fail(GRL_ERR_INVALID, "PPO: clip_range must be >= 0");
+  if (!(p->adam_eps > 0.f)) return fail(GRL_ERR_INVALID, "PPO: adam_eps must be > 0");
+  return GRL_OK;
+}
+
+static int query_sizes(const grl_config* cfg, const grl_ppo_config* ppo, grl_sizes* out) {
   if (!out) return fail(GRL_ERR_INVALID, "null out");
   grl_ctx ctx;
   ctx.cfg = *cfg;
+  if (ppo) ctx.pcfg = *ppo;
   ctx.dry = true;
   if (int e = ctx.plan()) return e;
   out->state_bytes = ctx.st.off + 256;
@@ -74,6 +113,16 @@ int grl_query_sizes(const grl_config* cfg, grl_sizes* out) {
   out->n_params = ctx.n_params;
   out->n_trainable = ctx.n_train;
   return GRL_OK;
+}
+
+int grl_query_sizes(const grl_config* cfg, grl_sizes* out) {
+  if (int e = check_cfg(cfg)) return e;
+  if (cfg->algo == GRL_ALGO_PPO) return fail(GRL_ERR_INVALID, "a PPO handle needs a grl_ppo_config: use grl_ppo_query_sizes / grl_ppo_create");
+  return query_sizes(cfg, nullptr, out);
+}
+int grl_ppo_query_sizes(const grl_config* cfg, const grl_ppo_config* ppo, grl_sizes* out) {
+  if (int e = check_ppo(cfg, ppo)) return e;
+  return query_sizes(cfg, ppo, out);
 }
 
 // Prioritised replay with an empty ring: all leaves 0, PerState at its starting values.  The block sums / minima (per.bsum,
@@ -89,12 +138,12 @@ static hipError_t per_start(grl_ctx* h) {
   return hipMemcpy(h->per.st, &ps, sizeof(ps), hipMemcpyHostToDevice);
 }
 
-int grl_create(const grl_config* cfg, const grl_buffers* bufs, grl_handle* out) {
-  if (int e = check_cfg(cfg)) return e;
+static int create_handle(const grl_config* cfg, const grl_ppo_config* ppo, const grl_buffers* bufs, grl_handle* out) {
   if (!bufs || !out || !bufs->state || !bufs->grads || !bufs->work || !bufs->replay)
     return fail(GRL_ERR_INVALID, "null buffers");
   grl_ctx* h = new grl_ctx();
   h->cfg = *cfg;
+  if (ppo) h->pcfg = *ppo;
   h->st.base = (char*)bufs->state; h->gr.base = (char*)bufs->grads;
   h->wk.base = (char*)bufs->work; h->rp.base = (char*)bufs->replay;
   if (int e = h->plan()) { delete h; return e; }
@@ -126,8 +175,22 @@ int grl_create(const grl_config* cfg, const grl_buffers* bufs, grl_handle* out) 
     e = per_start(h);
     if (e != hipSuccess) { delete h; return fail(GRL_ERR_HIP, std::string("per init: ") + hipGetErrorString(e)); }
   }
+  if (h->ppo_dev) {
+    e = hipMemset(h->ppo_dev, 0, sizeof(PpoDev));
+    if (e != hipSuccess) { delete h; return fail(GRL_ERR_HIP, std::string("ppo init: ") + hipGetErrorString(e)); }
+  }
   *out = h;
   return GRL_OK;
+}
+
+int grl_create(const grl_config* cfg, const grl_buffers* bufs, grl_handle* out) {
+  if (int e = check_cfg(cfg)) return e;
+  if (cfg->algo == GRL_ALGO_PPO) return fail(GRL_ERR_INVALID, "a PPO handle needs a grl_ppo_config: use grl_ppo_query_sizes / grl_ppo_create");
+  return create_handle(cfg, nullptr, bufs, out);
+}
+int grl_ppo_create(const grl_config* cfg, const grl_ppo_config* ppo, const grl_buffers* bufs, grl_handle* out) {
+  if (int e = check_ppo(cfg, ppo)) return e;
+  return create_handle(cfg, ppo, bufs, out);
 }
 
 int grl_destroy(grl_handle h) {
@@ -179,6 +242,7 @@ int grl_set_learning_rate(grl_handle h, float lr) {
 }
 
 int grl_set_obs_stats(grl_handle h, const double* mean, const double* var, double ret_var) {
+  NOT_ON_PPO(h, "grl_set_obs_stats");
   if (!h || !mean || !var) return fail(GRL_ERR_INVALID, "null argument");
   const grl_config& c = h->cfg;
   const double eps = c.norm_eps;
@@ -250,6 +314,7 @@ static int copy_from_caller(grl_handle h, void* dst, const void* src, size_t byt
 }
 
 int grl_set_ret_var(grl_handle h, double ret_var) {
+  NOT_ON_PPO(h, "grl_set_ret_var");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   const double sd = std::sqrt(ret_var + (double)h->cfg.norm_eps);
   HIPCHK(hipMemcpyAsync(h->s_ret, &sd, 8, hipMemcpyHostToDevice, h->stream));   // (pageable source: staged before returning)
@@ -257,6 +322,7 @@ int grl_set_ret_var(grl_handle h, double ret_var) {
 }
 
 int grl_set_running_stats(grl_handle h, const double* mean, const double* var, double count) {
+  NOT_ON_PPO(h, "grl_set_running_stats");
   if (!h || !mean || !var) return fail(GRL_ERR_INVALID, "null argument");
   if (!h->n_mean) return fail(GRL_ERR_STATE, "this handle keeps no running statistics");
   // (rare: once per attach / load; pageable sources are staged before hipMemcpyAsync returns)
@@ -301,6 +367,7 @@ static int norm_update_from(grl_handle h, const float* dev_obs, int n) {
 }
 
 int grl_norm_update(grl_handle h, const float* obs, int n) {
+  NOT_ON_PPO(h, "grl_norm_update");
   if (!h || !obs || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (!h->n_mean) return fail(GRL_ERR_STATE, "this handle keeps no running statistics");
   if (n > h->stg_n) return fail(GRL_ERR_INVALID, "more observations than one env step of act_batch environments");
@@ -310,6 +377,7 @@ int grl_norm_update(grl_handle h, const float* obs, int n) {
 }
 
 int grl_get_obs_stats(grl_handle h, double* mean, double* var, double* count) {
+  NOT_ON_PPO(h, "grl_get_obs_stats");
   if (!h || !mean || !var || !count) return fail(GRL_ERR_INVALID, "null argument");
   if (!h->n_mean) return fail(GRL_ERR_STATE, "this handle keeps no running statistics");
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -347,6 +415,7 @@ static int replay_add_dev(grl_handle h, const float* obs, const float* act, cons
 
 int grl_replay_add_device(grl_handle h, const float* obs, const float* act, const float* rew,
                           const float* next_obs, const float* done, int n) {
+  NOT_ON_PPO(h, "grl_replay_add_device");
   if (!h || !obs || !act || !rew || !next_obs || !done || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (n > h->cfg.replay_capacity) return fail(GRL_ERR_INVALID, "n exceeds replay capacity");
   return replay_add_dev(h, obs, act, rew, next_obs, done, n);
@@ -372,6 +441,7 @@ static int pin_reserve(grl_handle h, size_t in_floats, size_t out_floats) {
 
 int grl_replay_add(grl_handle h, const float* obs, const float* act, const float* rew, const float* next_obs,
                    const float* done, int n) {
+  NOT_ON_PPO(h, "grl_replay_add");
   if (!h || !obs || !act || !rew || !next_obs || !done || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
   const int64_t oe = h->cnn ? (int64_t)h->hw * h->hw * h->cfg.obs_channels : h->cfg.obs_dim;
   // (pageable copies: for these sizes -- 64 KB per transition -- an extra host copy into pinned staging costs
@@ -421,6 +491,7 @@ static int ob_stage_release(grl_handle h) {
 }
 
 int grl_observe(grl_handle h, const float* obs, int n, int flags) {
+  NOT_ON_PPO(h, "grl_observe");
   if (!h || !obs || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (!h->ob_latest) return fail(GRL_ERR_STATE, "this handle keeps no observed observations (SAC / DQN / BDQ handles do)");
   if (n > h->stg_n) return fail(GRL_ERR_INVALID, "more observations than one env step of act_batch environments");
@@ -442,6 +513,7 @@ int grl_observe(grl_handle h, const float* obs, int n, int flags) {
 
 int grl_replay_add_observed(grl_handle h, const float* act, const float* rew, const float* done, int n,
                             const int32_t* term_rows, const float* term_obs, int n_term) {
+  NOT_ON_PPO(h, "grl_replay_add_observed");
   if (!h || !act || !rew || !done || n < 1 || n_term < 0 || n_term > n) return fail(GRL_ERR_INVALID, "bad argument");
   if (n_term > 0 && (!term_rows || !term_obs)) return fail(GRL_ERR_INVALID, "terminal rows without their observations");
   if (!h->ob_latest) return fail(GRL_ERR_STATE, "this handle keeps no observed observations (SAC / DQN / BDQ handles do)");
@@ -471,7 +543,10 @@ int grl_replay_add_observed(grl_handle h, const float* act, const float* rew, co
   return e;
 }
 
-int64_t grl_replay_size(grl_handle h) { return h ? h->rp_size : -1; }
+int64_t grl_replay_size(grl_handle h) {
+  NOT_ON_PPO(h, "grl_replay_size");
+  return h ? h->rp_size : -1;
+}
 
 static int stage_noise(grl_handle h, const int64_t* idx, const float* eps, int step) {
   HIPCHK(hipMemcpyAsync(h->idx_buf, idx + (int64_t)step * h->B, (size_t)h->B * 8, hipMemcpyDeviceToDevice, h->stream));
@@ -481,6 +556,7 @@ static int stage_noise(grl_handle h, const int64_t* idx, const float* eps, int s
 }
 
 int grl_compute_grads(grl_handle h, const int64_t* idx, const float* eps) {
+  NOT_ON_PPO(h, "grl_compute_grads");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if ((idx == nullptr) != (eps == nullptr)) return fail(GRL_ERR_INVALID, "idx and eps must both be given or both be NULL");
   if (h->rp_size < 1) return fail(GRL_ERR_STATE, "replay buffer is empty");
@@ -495,6 +571,7 @@ int grl_compute_grads(grl_handle h, const int64_t* idx, const float* eps) {
 }
 
 int grl_compute_grads_staged(grl_handle h, int stage, const int64_t* idx, const float* eps) {
+  NOT_ON_PPO(h, "grl_compute_grads_staged");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if (stage != 0 && stage != 1) return fail(GRL_ERR_INVALID, "stage must be 0 or 1");
   if (!h->staged_ok) {          // plans without a staged form: everything in stage 0, one bucket (grl_grad_ranges)
@@ -519,6 +596,7 @@ int grl_compute_grads_staged(grl_handle h, int stage, const int64_t* idx, const 
 }
 
 int grl_grad_ranges(grl_handle h, int bucket, int cap, int64_t* offsets, int64_t* numels) {
+  NOT_ON_PPO(h, "grl_grad_ranges");
   if (!h || !offsets || !numels) return fail(GRL_ERR_INVALID, "null argument");
   if (bucket != 0 && bucket != 1) return fail(GRL_ERR_INVALID, "bucket must be 0 or 1");
   std::vector<std::pair<int64_t, int64_t>> r;
@@ -538,6 +616,7 @@ int grl_grad_ranges(grl_handle h, int bucket, int cap, int64_t* offsets, int64_t
 }
 
 int grl_apply_grads(grl_handle h, float grad_scale) {
+  NOT_ON_PPO(h, "grl_apply_grads");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if (grad_scale != h->apply_graph_scale) {   // the scale is baked into the captured kernel arguments
     auto it = h->graphs.find("apply");
@@ -551,6 +630,7 @@ int grl_apply_grads(grl_handle h, float grad_scale) {
 }
 
 int grl_train_step(grl_handle h, int n_steps, const int64_t* idx, const float* eps) {
+  NOT_ON_PPO(h, "grl_train_step");
   if (!h || n_steps < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (h->cfg.algo == GRL_ALGO_AE) return fail(GRL_ERR_STATE, "auto-encoder handles train with grl_ae_train_step");
   if ((idx == nullptr) != (eps == nullptr)) return fail(GRL_ERR_INVALID, "idx and eps must both be given or both be NULL");
@@ -573,6 +653,7 @@ int grl_train_step(grl_handle h, int n_steps, const int64_t* idx, const float* e
 }
 
 int grl_train_step_per(grl_handle h, int n_steps, double beta, const double* u) {
+  NOT_ON_PPO(h, "grl_train_step_per");
   if (!h || n_steps < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (!h->per_on) return fail(GRL_ERR_STATE, "prioritised replay is not enabled (grl_config.q_per)");
   if (h->rp_size < 1) return fail(GRL_ERR_STATE, "replay buffer is empty");
@@ -619,6 +700,7 @@ int grl_train_step_per(grl_handle h, int n_steps, double beta, const double* u) 
 }
 
 int grl_ae_train_step(grl_handle h, const float* imgs, int n_steps) {
+  NOT_ON_PPO(h, "grl_ae_train_step");
   if (!h || !imgs || n_steps < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (h->cfg.algo != GRL_ALGO_AE) return fail(GRL_ERR_STATE, "not an auto-encoder handle (grl_config.algo)");
   const size_t per = (size_t)h->B * 4096;
@@ -631,6 +713,7 @@ int grl_ae_train_step(grl_handle h, const float* imgs, int n_steps) {
 }
 
 int grl_ae_reconstruct(grl_handle h, const float* imgs, float* out) {
+  NOT_ON_PPO(h, "grl_ae_reconstruct");
   if (!h || !imgs || !out) return fail(GRL_ERR_INVALID, "null argument");
   if (h->cfg.algo != GRL_ALGO_AE) return fail(GRL_ERR_STATE, "not an auto-encoder handle (grl_config.algo)");
   const size_t per = (size_t)h->B * 4096;
@@ -698,9 +781,138 @@ static int act_greedy(grl_handle h, const float* obs, int n, const float* explor
   return GRL_OK;
 }
 
+
+// ---------------------------------------------------------------------------------------------- PPO2 (plan_ppo.inl)
+// what one env step sends, packed into page-locked staging and copied once: observations [NA, ldo] (rows padded, padding zero) |
+// done [NA] | eps [NA, A] | rewards [NA] (the layout of grl_ctx::ppo_in)
+static int ppo_send(grl_handle h, const float* obs, const float* done, const float* eps, int n) {
+  const int NA = h->NA, ldo = h->ppo_ldo, od = h->cfg.obs_dim, A = h->A;
+  const size_t n_in = (size_t)NA * (ldo + 1 + A);
+  if (int e = pin_reserve(h, (size_t)NA * (ldo + 2 + A), (size_t)NA * (A + 2))) return e;
+  // (the previous call synchronised the stream behind its copy: the staging buffer is free)
+  memset(h->pin_in, 0, n_in * 4);
+  for (int r = 0; r < n; ++r) memcpy(h->pin_in + (size_t)r * ldo, obs + (size_t)r * od, (size_t)od * 4);
+  if (done) memcpy(h->pin_in + (size_t)NA * ldo, done, (size_t)n * 4);
+  if (eps) memcpy(h->pin_in + (size_t)NA * (ldo + 1), eps, (size_t)n * A * 4);
+  HIPCHK(hipMemcpyAsync(h->ppo_in, h->pin_in, n_in * 4, hipMemcpyHostToDevice, h->stream));
+  return GRL_OK;
+}
+// ... and what it returns: action [NA, A] | value [NA] | neglogp [NA]; synchronises
+static int ppo_receive(grl_handle h, int n, float* out_act, float* out_val, float* out_nlp) {
+  const int NA = h->NA, A = h->A;
+  HIPCHK(hipMemcpyAsync(h->pin_out, h->ppo_out, (size_t)NA * (A + 2) * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipGetLastError());
+  if (out_act) memcpy(out_act, h->pin_out, (size_t)n * A * 4);
+  if (out_val) memcpy(out_val, h->pin_out + (size_t)NA * A, (size_t)n * 4);
+  if (out_nlp) memcpy(out_nlp, h->pin_out + (size_t)NA * (A + 1), (size_t)n * 4);
+  return GRL_OK;
+}
+#define PPO_ONLY(h, what)                                                                                        \
+  do {                                                                                                           \
+    if (!(h)) return fail(GRL_ERR_INVALID, "null handle");                                                       \
+    if ((h)->cfg.algo != GRL_ALGO_PPO) return fail(GRL_ERR_STATE, what " is defined for PPO handles (grl_ppo_create)"); \
+  } while (0)
+
+static int ppo_act(grl_handle h, const float* obs, int n, int flags, const float* eps, float* out) {
+  if (flags & ~GRL_ACT_DETERMINISTIC) return fail(GRL_ERR_STATE, "a PPO handle acts on the observations handed to it: GRL_ACT_RAW_OBS / GRL_ACT_OBSERVED / GRL_ACT_GREEDY are not defined on it");
+  if (!obs) return fail(GRL_ERR_INVALID, "bad argument");
+  if (n > h->NA) return fail(GRL_ERR_INVALID, "n exceeds act_batch");
+  const int v = (flags & GRL_ACT_DETERMINISTIC) ? 0 : (eps ? 1 : 2);
+  if (int e = ppo_send(h, obs, nullptr, v == 1 ? eps : nullptr, n)) return e;
+  static const char* key[3] = {"ppo_act_det", "ppo_act_eps", "ppo_act_rng"};
+  if (int e = h->run_seq(key[v], {&h->ops_ppo_act[v]})) return e;
+  return ppo_receive(h, n, out, nullptr, nullptr);
+}
+
+int grl_ppo_step(grl_handle h, const float* obs, const float* done, const float* eps, float* out_act, float* out_val, float* out_nlp) {
+  PPO_ONLY(h, "grl_ppo_step");
+  if (!obs || !done || !out_act || !out_val || !out_nlp) return fail(GRL_ERR_INVALID, "null argument");
+  if (h->ppo_stepped >= h->pcfg.n_steps) return fail(GRL_ERR_STATE, "the rollout is full: grl_ppo_finish and grl_ppo_train empty it");
+  if (h->ppo_stepped != h->ppo_closed) return fail(GRL_ERR_STATE, "the previous slot is still open: grl_ppo_rewards closes it");
+  if (int e = ppo_send(h, obs, done, eps, h->NA)) return e;
+  if (int e = h->run_seq(eps ? "ppo_step_eps" : "ppo_step_rng", {&h->ops_ppo_step[eps ? 0 : 1]})) return e;
+  if (int e = ppo_receive(h, h->NA, out_act, out_val, out_nlp)) return e;
+  h->ppo_stepped += 1;
+  h->ppo_finished = false;
+  return GRL_OK;
+}
+
+int grl_ppo_rewards(grl_handle h, const float* rew, int n) {
+  PPO_ONLY(h, "grl_ppo_rewards");
+  if (!rew || n != h->NA) return fail(GRL_ERR_INVALID, "grl_ppo_rewards takes n_envs rewards");
+  if (h->ppo_stepped != h->ppo_closed + 1) return fail(GRL_ERR_STATE, "no open slot: grl_ppo_step opens one");
+  if (int e = copy_from_caller(h, h->ppo_in + (size_t)h->NA * (h->ppo_ldo + 1 + h->A), rew, (size_t)n * 4)) return e;
+  if (int e = h->run_seq("ppo_rewards", {&h->ops_ppo_rew})) return e;
+  HIPCHK(hipGetLastError());
+  h->ppo_closed += 1;
+  return GRL_OK;
+}
+
+int grl_ppo_finish(grl_handle h, const float* last_obs, const float* last_done) {
+  PPO_ONLY(h, "grl_ppo_finish");
+  if (!last_obs || !last_done) return fail(GRL_ERR_INVALID, "null argument");
+  if (h->ppo_closed != h->pcfg.n_steps) return fail(GRL_ERR_STATE, "the rollout is not full: n_steps slots must be closed before grl_ppo_finish");
+  if (int e = ppo_send(h, last_obs, last_done, nullptr, h->NA)) return e;
+  if (int e = h->run_seq("ppo_finish", {&h->ops_ppo_finish})) return e;
+  // (the staging buffer of ppo_send is reused by the next call: wait for its copy, as every per-step call does)
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipGetLastError());
+  h->ppo_finished = true;
+  return GRL_OK;
+}
+
+int grl_ppo_train(grl_handle h, const int32_t* perm, int noptepochs) {
+  PPO_ONLY(h, "grl_ppo_train");
+  if (!perm || noptepochs < 1 || noptepochs > GRL_PPO_MAX_EPOCHS)
+    return fail(GRL_ERR_INVALID, "grl_ppo_train takes 1.." + std::to_string(GRL_PPO_MAX_EPOCHS) + " permutations");
+  if (!h->ppo_finished) return fail(GRL_ERR_STATE, "no finished rollout: grl_ppo_finish forms the advantages grl_ppo_train reads");
+  const int64_t R = (int64_t)h->pcfg.n_envs * h->pcfg.n_steps;
+  {
+    std::vector<uint8_t> seen((size_t)R);
+    for (int e = 0; e < noptepochs; ++e) {
+      std::fill(seen.begin(), seen.end(), 0);
+      for (int64_t i = 0; i < R; ++i) {
+        const int32_t v = perm[(int64_t)e * R + i];
+        if (v < 0 || v >= R || seen[(size_t)v]) return fail(GRL_ERR_INVALID, "perm row " + std::to_string(e) + " is no permutation of 0.." + std::to_string(R - 1));
+        seen[(size_t)v] = 1;
+      }
+    }
+  }
+  if (int e = copy_from_caller(h, h->ppo_perm, perm, (size_t)noptepochs * R * 4)) return e;
+  HIPCHK(hipMemsetAsync(&h->ppo_dev->cursor, 0, 4, h->stream));
+  const int n_updates = noptepochs * (int)(R / h->cfg.batch_size);
+  if (int e = h->run_repeated("ppo_update", {&h->ops_ppo_update}, n_updates)) return e;
+  HIPCHK(hipMemsetAsync(&h->ppo_dev->slot, 0, 4, h->stream));      // the rollout is empty again
+  HIPCHK(hipGetLastError());
+  h->ppo_updates = n_updates;
+  h->ppo_stepped = h->ppo_closed = 0;
+  h->ppo_finished = false;
+  return GRL_OK;
+}
+
+int grl_ppo_get_metrics(grl_handle h, float* out, int cap) {
+  PPO_ONLY(h, "grl_ppo_get_metrics");
+  if (!out) return fail(GRL_ERR_INVALID, "null argument");
+  const int nu = h->ppo_updates, nb = h->ppo_nblk, mb = h->cfg.batch_size;
+  if (cap < nu * PPO_DIAG) return fail(GRL_ERR_INVALID, "metrics buffer too small");
+  std::vector<float> part((size_t)std::max(1, nu * nb * PPO_DIAG));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (nu) HIPCHK(hipMemcpy(part.data(), h->ppo_diag, (size_t)nu * nb * PPO_DIAG * 4, hipMemcpyDeviceToHost));
+  for (int u = 0; u < nu; ++u) {
+    float s[PPO_DIAG] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < nb; ++b)      // the per-block sums of the loss launch, in index order
+      for (int k = 0; k < PPO_DIAG; ++k) s[k] += part[((size_t)u * nb + b) * PPO_DIAG + k];
+    float* o = out + (size_t)u * PPO_DIAG;
+    o[0] = s[0] / (float)mb; o[1] = 0.5f * (s[1] / (float)mb); o[2] = s[2]; o[3] = 0.5f * (s[3] / (float)mb); o[4] = s[4] / (float)mb;
+  }
+  return nu;
+}
+
 int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps, float* out) {
   if (!h || !out || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (flags & ~(GRL_ACT_DETERMINISTIC | GRL_ACT_RAW_OBS | GRL_ACT_OBSERVED | GRL_ACT_GREEDY)) return fail(GRL_ERR_INVALID, "unknown flag bits");
+  if (h->cfg.algo == GRL_ALGO_PPO) return ppo_act(h, obs, n, flags, eps, out);
   const int deterministic = flags & GRL_ACT_DETERMINISTIC;
   const bool raw = (flags & GRL_ACT_RAW_OBS) != 0;        // raw observations: VecNormalize applied on the device (grl_norm_update statistics)
   const bool observed = (flags & GRL_ACT_OBSERVED) != 0;  // act on what grl_observe uploaded: no second upload
@@ -748,6 +960,7 @@ static size_t dp_arr_bytes(int64_t n) { return (size_t)rup(n * 4, 256); }
 static size_t dp_mom_bytes(int64_t elems) { return (size_t)rup((2 * elems + 4) * 4, 256); }
 
 int grl_allreduce_init(grl_handle h, int rank, int world, void* handle_out) {
+  NOT_ON_PPO(h, "grl_allreduce_init");
   if (!h || !handle_out) return fail(GRL_ERR_INVALID, "null argument");
   if (h->cfg.algo == GRL_ALGO_AE) return fail(GRL_ERR_STATE, "the exchange step is defined for SAC / DQN / BDQ handles");
   if (world < 1 || world > DP_MAX_WORLD || rank < 0 || rank >= world) return fail(GRL_ERR_INVALID, "bad rank / world size");
@@ -895,6 +1108,7 @@ static void close_with_exchange(grl_ctx* h, const DpArgs& d, const CallPlan& src
 }
 
 int grl_allreduce_connect(grl_handle h, const void* handles) {
+  NOT_ON_PPO(h, "grl_allreduce_connect");
   if (!h || !handles) return fail(GRL_ERR_INVALID, "null argument");
   if (!h->dp_buf) return fail(GRL_ERR_STATE, "call grl_allreduce_init first");
   if (h->dp_on) return fail(GRL_ERR_STATE, "already connected");
@@ -1019,6 +1233,7 @@ int grl_allreduce_connect(grl_handle h, const void* handles) {
 }
 
 int grl_allreduce_disconnect(grl_handle h) {
+  NOT_ON_PPO(h, "grl_allreduce_disconnect");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if (!h->dp_buf && !h->dp_flags) return GRL_OK;          // never initialised (or already released): nothing to do
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1040,6 +1255,7 @@ int grl_allreduce_disconnect(grl_handle h) {
 }
 
 int grl_allreduce_set_overlap(grl_handle h, int on) {
+  NOT_ON_PPO(h, "grl_allreduce_set_overlap");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if (!h->dp_on) return fail(GRL_ERR_STATE, "call grl_allreduce_init / grl_allreduce_connect first");
   if (on && h->ops_dp_overlap.empty()) return fail(GRL_ERR_STATE, "this configuration has no staged plan: the exchange cannot be overlapped");
@@ -1048,6 +1264,7 @@ int grl_allreduce_set_overlap(grl_handle h, int on) {
 }
 
 int grl_allreduce_set_mode(grl_handle h, int mode) {
+  NOT_ON_PPO(h, "grl_allreduce_set_mode");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if (!h->dp_on) return fail(GRL_ERR_STATE, "call grl_allreduce_init / grl_allreduce_connect first");
   if (mode < 0 || mode > 2) return fail(GRL_ERR_INVALID, "mode: 0 auto, 1 two-shot, 2 one-shot");
@@ -1057,6 +1274,7 @@ int grl_allreduce_set_mode(grl_handle h, int mode) {
 }
 
 int grl_allreduce_set_timeout(grl_handle h, int ms) {
+  NOT_ON_PPO(h, "grl_allreduce_set_timeout");
   if (!h || ms < 0) return fail(GRL_ERR_INVALID, "bad argument");
   if (!h->dp_err_host) return fail(GRL_ERR_STATE, "call grl_allreduce_init first");
   __atomic_store_n(h->dp_err_host + 1, (uint32_t)ms, __ATOMIC_RELEASE);     // read by the waiting kernels (dp_wait_all)
@@ -1064,6 +1282,7 @@ int grl_allreduce_set_timeout(grl_handle h, int ms) {
 }
 
 int grl_train_step_allreduce(grl_handle h, int n_steps, const int64_t* idx, const float* eps) {
+  NOT_ON_PPO(h, "grl_train_step_allreduce");
   if (!h || n_steps < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (!h->dp_on) return fail(GRL_ERR_STATE, "call grl_allreduce_init / grl_allreduce_connect first");
   if ((idx == nullptr) != (eps == nullptr)) return fail(GRL_ERR_INVALID, "idx and eps must both be given or both be NULL");
@@ -1099,6 +1318,7 @@ int grl_train_step_allreduce(grl_handle h, int n_steps, const int64_t* idx, cons
 }
 
 int grl_allreduce_status(grl_handle h, int64_t* exchanges, int* error) {
+  NOT_ON_PPO(h, "grl_allreduce_status");
   if (!h || !h->dp_flags) return fail(GRL_ERR_STATE, "no exchange buffer");
   HIPCHK(hipStreamSynchronize(h->stream));
   DpCtl c[DP_CHANNELS];
@@ -1120,6 +1340,7 @@ int grl_allreduce_status(grl_handle h, int64_t* exchanges, int* error) {
 }
 
 int grl_q_update_target(grl_handle h) {
+  NOT_ON_PPO(h, "grl_q_update_target");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if (h->cfg.algo == GRL_ALGO_SAC) return fail(GRL_ERR_STATE, "SAC has no hard target update");
   HIPCHK(hipMemcpyAsync(h->params + h->tgt_off, h->params + h->q_online_off, (size_t)h->q_online_n * 4,
@@ -1128,6 +1349,7 @@ int grl_q_update_target(grl_handle h) {
 }
 
 int grl_encoder_load(grl_handle h, const float* const* w, const int64_t* numels, int n_arrays) {
+  NOT_ON_PPO(h, "grl_encoder_load");
   if (!h || !w || !numels || n_arrays != 8) return fail(GRL_ERR_INVALID, "expected 8 weight arrays");
   if (h->cfg.algo != GRL_ALGO_SAC) return fail(GRL_ERR_STATE, "grl_encoder_load is for SAC handles (auto-encoder handles encode with their own parameters)");
   const int64_t wn[8] = {7 * 7 * 32, 32, 5 * 5 * 32 * 32, 32, 3 * 3 * 32 * 32, 32, 2048 * 100, 100};
@@ -1140,6 +1362,7 @@ int grl_encoder_load(grl_handle h, const float* const* w, const int64_t* numels,
 }
 
 int grl_encode(grl_handle h, const float* depth, int n, float* out) {
+  NOT_ON_PPO(h, "grl_encode");
   if (!h || !depth || !out || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (!h->enc_loaded) return fail(GRL_ERR_STATE, "grl_encoder_load has not been called");
   if (n > h->NA) return fail(GRL_ERR_INVALID, "n exceeds act_batch");
@@ -1168,6 +1391,15 @@ int64_t grl_debug_fetch(grl_handle h, const char* name, float* out, int64_t cap)
 
 int64_t grl_debug_store(grl_handle h, const char* name, const float* in, int64_t n) {
   if (!h || !name || !in) return fail(GRL_ERR_INVALID, "null argument");
+  if (h->cfg.algo == GRL_ALGO_PPO && !strcmp(name, "ppo_slots")) {      // a rollout placed through the names below: how far it has got
+    if (n != 3) return fail(GRL_ERR_INVALID, "ppo_slots takes three values: slots written, slots closed, finished");
+    const int32_t st = (int32_t)in[0], cl = (int32_t)in[1];
+    if (cl < 0 || cl > h->pcfg.n_steps || st < cl || st > cl + 1 || st > h->pcfg.n_steps) return fail(GRL_ERR_INVALID, "ppo_slots out of range");
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(GRL_ERR_HIP, "sync failed");
+    if (hipMemcpy(&h->ppo_dev->slot, &cl, 4, hipMemcpyHostToDevice) != hipSuccess) return fail(GRL_ERR_HIP, "copy failed");
+    h->ppo_stepped = st; h->ppo_closed = cl; h->ppo_finished = in[2] != 0.f && cl == h->pcfg.n_steps;
+    return n;
+  }
   auto it = h->dbg.find(name);
   if (it == h->dbg.end()) return fail(GRL_ERR_INVALID, std::string("unknown tensor ") + name);
   if (n > it->second.second) return fail(GRL_ERR_INVALID, std::string("too many values for ") + name);

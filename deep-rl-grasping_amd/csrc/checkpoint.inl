@@ -52,12 +52,14 @@ static size_t state_bytes_now(const grl_ctx* h) {
 }
 
 int grl_state_size(grl_handle h, size_t* bytes) {
+  NOT_ON_PPO(h, "grl_state_size");
   if (!h || !bytes) return fail(GRL_ERR_INVALID, "null argument");
   *bytes = state_bytes_now(h);
   return GRL_OK;
 }
 
 int64_t grl_state_export(grl_handle h, void* host_buf, size_t cap) {
+  NOT_ON_PPO(h, "grl_state_export");
   if (!h || !host_buf) return fail(GRL_ERR_INVALID, "null argument");
   const size_t total = state_bytes_now(h);
   if (cap < total) return fail(GRL_ERR_INVALID, "state buffer too small: " + std::to_string(total) + " bytes needed");
@@ -85,6 +87,7 @@ int64_t grl_state_export(grl_handle h, void* host_buf, size_t cap) {
 }
 
 int grl_state_import(grl_handle h, const void* host_buf, size_t n) {
+  NOT_ON_PPO(h, "grl_state_import");
   if (!h || !host_buf) return fail(GRL_ERR_INVALID, "null argument");
   const char* p = (const char*)host_buf;
   grl_state_header hd;
@@ -137,6 +140,7 @@ int grl_state_import(grl_handle h, const void* host_buf, size_t n) {
 }
 
 int grl_replay_segments(grl_handle h, int cap, grl_segment* out) {
+  NOT_ON_PPO(h, "grl_replay_segments");
   if (!h || (cap > 0 && !out)) return fail(GRL_ERR_INVALID, "null argument");
   std::vector<grl_segment> s;
   if (h->cfg.algo != GRL_ALGO_AE) {

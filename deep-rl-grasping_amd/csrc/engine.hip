@@ -1,7 +1,8 @@
 // engine.hip -- host side of libgrl.so: grl_ctx (parameter layout, addressing tables, problem builders, launch and
 // graph machinery); the launch plans and the C ABI of include/grl.h are included parts of this translation unit:
 //   plan_sac.inl (SAC update, act, encoder forward)   plan_q.inl (DQN / BDQ, prioritised replay)
-//   plan_ae.inl  (auto-encoder training)              capi.inl  (extern "C" entry points)
+//   plan_ae.inl  (auto-encoder training)              plan_ppo.inl (PPO2: rollout, GAE, clipped update)
+//   capi.inl     (extern "C" entry points)
 // The element-wise, replay, prioritised-sampling and exchange kernels are compiled here; the GEMM and head kernels in
 // gemm_fwd.hip / gemm_bwd.hip / gemm_wgrad.hip / heads.hip behind the launchers of launch.h.
 //
@@ -44,6 +45,8 @@
 #include "q_wide_kernels.h"
 #include "ln_kernels.h"
 #include "dp_kernels.h"
+#define GRL_PPO_TYPES_ONLY          // (the PPO kernels are instantiated in ppo.hip)
+#include "ppo_kernels.h"
 
 namespace grl {
 
@@ -100,6 +103,7 @@ static inline int64_t rup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
   X(per_pf, 1, INT, CREATE)                   \
   X(q_pf, 1, INT, CREATE)                     \
   X(q_act, 1, INT, CREATE)                    \
+  X(ppo_act, 1, INT, CREATE)                  \
   X(ae_general, 0, INT, CREATE)               \
   X(graph_updates, 16, INT, CALL)             \
   X(dp_coarse, 0, INT, DP_INIT)               \
@@ -1501,6 +1505,19 @@ struct grl_ctx {
   int plan_sac();
   int plan_q();        // DQN / BDQ (MLP towers, dueling, double-Q)
   int plan_ae();       // depth auto-encoder training (encoders.py:40-50,70-136)
+  int plan_ppo();      // PPO2 (actor-critic MlpPolicy, Box actions): rollout store, GAE, clipped update
+  // PPO2 state (plan_ppo.inl): the second configuration block, the device words, the rollout in the replay arena, what one env
+  // step sends and returns, the permutations and per-block diagnostics of a training call, and how far the rollout has got
+  grl_ppo_config pcfg = {};
+  PpoDev* ppo_dev = nullptr;
+  float *pr_obs = nullptr, *pr_act = nullptr, *pr_val = nullptr, *pr_nlp = nullptr, *pr_rew = nullptr, *pr_done = nullptr;
+  float *pr_adv = nullptr, *pr_ret = nullptr, *pr_lastv = nullptr, *pr_lastdone = nullptr;
+  float *ppo_in = nullptr, *ppo_out = nullptr, *ppo_diag = nullptr;
+  int32_t* ppo_perm = nullptr;
+  int ppo_ldo = 0, ppo_nblk = 0;
+  int ppo_stepped = 0, ppo_closed = 0, ppo_updates = 0;     // slots written / closed by rewards; updates of the last training call
+  bool ppo_finished = false;                                // advantages and returns of the full rollout are on the device
+  std::vector<Op> ops_ppo_step[2], ops_ppo_finish, ops_ppo_act[3], ops_ppo_rew, ops_ppo_update;   // [eps handed over | Philox]; act: mean | eps | Philox
   int plan_ae_general(const AeNet& net);   // ... of any supported network but the shipped one (GRL_TUNE ae_general=1: that one too)
   int enc_dim = 100;   // floats per image grl_encode returns (auto-encoder handles: their encoding_dim)
   float* ae_x = nullptr;            // [B, 4096] minibatch of depth images (staged per step)
@@ -1541,7 +1558,7 @@ static ConvGeom cnn_geom(int l, int C_img) {
 
 // --------------------------------------------------------------------------------------------------
 int grl_ctx::plan() {
-  const int e = cfg.algo == GRL_ALGO_SAC ? plan_sac() : (cfg.algo == GRL_ALGO_AE ? plan_ae() : plan_q());
+  const int e = cfg.algo == GRL_ALGO_SAC ? plan_sac() : (cfg.algo == GRL_ALGO_AE ? plan_ae() : (cfg.algo == GRL_ALGO_PPO ? plan_ppo() : plan_q()));
   sw.note();
   return e;
 }
@@ -1549,6 +1566,7 @@ int grl_ctx::plan() {
 #include "plan_sac.inl"
 #include "plan_q.inl"
 #include "plan_ae.inl"
+#include "plan_ppo.inl"
 
 int grl_ctx::run_ops(std::vector<Op>& ops) {
   if (!prof) {

@@ -31,6 +31,20 @@ class GrlConfig(C.Structure):
     ]
 
 
+class GrlPpoConfig(C.Structure):
+    """include/grl.h: grl_ppo_config -- what a PPO handle needs beside its GrlConfig."""
+    _fields_ = [
+        ("n_envs", C.c_int32), ("n_steps", C.c_int32),
+        ("n_vf_layers", C.c_int32), ("vf_layers", C.c_int32 * GRL_MAX_LAYERS),
+        ("lam", C.c_float), ("clip_range", C.c_float), ("clip_range_vf", C.c_float),
+        ("ent_coef", C.c_float), ("vf_coef", C.c_float), ("max_grad_norm", C.c_float),
+        ("adam_eps", C.c_float),
+    ]
+
+
+PPO_MAX_EPOCHS = 64      # GRL_PPO_MAX_EPOCHS
+
+
 class GrlSizes(C.Structure):
     _fields_ = [("state_bytes", C.c_size_t), ("grads_bytes", C.c_size_t), ("work_bytes", C.c_size_t),
                 ("replay_bytes", C.c_size_t), ("n_params", C.c_int64), ("n_trainable", C.c_int64)]
@@ -58,6 +72,8 @@ EXPORTS = [
     "grl_allreduce_init", "grl_allreduce_connect", "grl_train_step_allreduce", "grl_allreduce_status", "grl_allreduce_set_overlap", "grl_allreduce_set_mode", "grl_allreduce_set_timeout",
     "grl_allreduce_disconnect",
     "grl_state_size", "grl_state_export", "grl_state_import", "grl_replay_segments",
+    "grl_ppo_query_sizes", "grl_ppo_create", "grl_ppo_step", "grl_ppo_rewards", "grl_ppo_finish", "grl_ppo_train",
+    "grl_ppo_get_metrics",
 ]
 
 
@@ -146,6 +162,13 @@ def load_library(path=None):
     lib.grl_state_export.restype = i64
     lib.grl_state_import.argtypes = [vp, vp, C.c_size_t]
     lib.grl_replay_segments.argtypes = [vp, i32, C.POINTER(GrlSegment)]
+    lib.grl_ppo_query_sizes.argtypes = [C.POINTER(GrlConfig), C.POINTER(GrlPpoConfig), C.POINTER(GrlSizes)]
+    lib.grl_ppo_create.argtypes = [C.POINTER(GrlConfig), C.POINTER(GrlPpoConfig), C.POINTER(GrlBuffers), C.POINTER(vp)]
+    lib.grl_ppo_step.argtypes = [vp, f32p, f32p, f32p, f32p, f32p, f32p]
+    lib.grl_ppo_rewards.argtypes = [vp, f32p, i32]
+    lib.grl_ppo_finish.argtypes = [vp, f32p, f32p]
+    lib.grl_ppo_train.argtypes = [vp, vp, i32]
+    lib.grl_ppo_get_metrics.argtypes = [vp, f32p, i32]
     return lib
 
 
@@ -255,3 +278,31 @@ def make_q_config(algo, obs_dim, n_branches, n_bins, common=(), branch_hidden=(6
     cfg.q_per_alpha64, cfg.q_per_stratified = float(per_alpha), (1 if per_stratified else 0)
     cfg.q_layer_norm = 1 if layer_norm else 0
     return cfg
+
+
+def make_ppo_config(obs_dim, act_dim, n_envs=1, n_steps=128, nminibatches=4, pi_layers=(64, 64), vf_layers=(64, 64), gamma=0.99,
+                    lam=0.95, lr=2.5e-4, ent_coef=0.01, vf_coef=0.5, max_grad_norm=0.5, cliprange=0.2, cliprange_vf=None,
+                    adam_eps=1e-5, seed=0):
+    """(GrlConfig, GrlPpoConfig) of a PPO2 handle (stable-baselines 2.10.1 PPO2 + actor-critic MlpPolicy, Box actions).
+    cliprange_vf None: the policy's cliprange; negative: no value clipping.  max_grad_norm None or <= 0: no clipping."""
+    n_batch = int(n_envs) * int(n_steps)
+    if n_batch % int(nminibatches):
+        raise GrlError("The number of minibatches (`nminibatches`) is not a factor of the total number of samples "
+                       "collected per rollout (`n_batch`), some samples won't be used.")
+    if len(vf_layers) > GRL_MAX_LAYERS:
+        raise GrlError("at most %d hidden layers are supported" % GRL_MAX_LAYERS)
+    cfg = make_config("mlp", obs_dim=int(obs_dim), act_dim=int(act_dim), layers=tuple(pi_layers), batch_size=n_batch // int(nminibatches),
+                      act_batch=int(n_envs), replay_capacity=n_batch, normalize=False, gamma=gamma, lr=lr, seed=seed)
+    cfg.algo = 4
+    cfg.tau = cfg.clip_obs = cfg.clip_reward = cfg.norm_eps = cfg.target_entropy = 0.0
+    ppo = GrlPpoConfig()
+    ppo.n_envs, ppo.n_steps = int(n_envs), int(n_steps)
+    ppo.n_vf_layers = len(vf_layers)
+    for i, h in enumerate(vf_layers):
+        ppo.vf_layers[i] = int(h)
+    ppo.lam, ppo.clip_range = lam, cliprange
+    ppo.clip_range_vf = cliprange if cliprange_vf is None else cliprange_vf
+    ppo.ent_coef, ppo.vf_coef = ent_coef, vf_coef
+    ppo.max_grad_norm = 0.0 if max_grad_norm is None else max_grad_norm
+    ppo.adam_eps = adam_eps
+    return cfg, ppo

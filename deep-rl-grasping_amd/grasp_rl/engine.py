@@ -218,7 +218,7 @@ class SacEngine:
         self.be = backend if backend is not None else TorchCudaBackend(device)
         self.cfg = cfg
         sizes = _capi.GrlSizes()
-        check(self.lib, self.lib.grl_query_sizes(C.byref(cfg), C.byref(sizes)))
+        check(self.lib, self._query_sizes(cfg, sizes))
         self.sizes = sizes
         self.state = self.be.alloc_f32(sizes.state_bytes)
         self.grads = self.be.alloc_f32(sizes.grads_bytes)
@@ -227,7 +227,7 @@ class SacEngine:
         bufs = _capi.GrlBuffers(self.be.ptr(self.state), self.be.ptr(self.grads), self.be.ptr(self.work),
                                 self.be.ptr(self.replay))
         h = C.c_void_p()
-        check(self.lib, self.lib.grl_create(C.byref(cfg), C.byref(bufs), C.byref(h)))
+        check(self.lib, self._create(cfg, bufs, h))
         self.h = h
         check(self.lib, self.lib.grl_set_stream(self.h, C.c_void_p(self.be.stream_ptr())))
         self.table = _capi.param_table(self.lib, self.h)
@@ -235,6 +235,13 @@ class SacEngine:
         self.B, self.A = cfg.batch_size, cfg.act_dim
         self.observe_rows = int(cfg.act_batch)      # one env step that `observe` + `act(observed=True)` cover in one call
         self._keep = []
+
+    # the two calls that differ between handle kinds (PpoEngine: grl_ppo_query_sizes / grl_ppo_create)
+    def _query_sizes(self, cfg, sizes):
+        return self.lib.grl_query_sizes(C.byref(cfg), C.byref(sizes))
+
+    def _create(self, cfg, bufs, h):
+        return self.lib.grl_create(C.byref(cfg), C.byref(bufs), C.byref(h))
 
     def close(self):
         if getattr(self, "h", None):
@@ -769,3 +776,82 @@ class QEngine(SacEngine):
 
     def priorities(self):
         return self.fetch("priority", (self.B,))
+
+
+class PpoEngine(SacEngine):
+    """PPO2 handle (``_capi.make_ppo_config``): the rollout lives on the device; ``step`` / ``rewards`` fill a slot per env step,
+    ``finish`` forms the last values and GAE, ``train`` runs noptepochs * nminibatches updates over the permutations handed to
+    it.  Parameters, ``set_learning_rate``, ``reset_optimizer``, ``fetch`` / ``store`` and profiling as on every handle."""
+
+    def __init__(self, cfg, ppo, backend=None, lib_path=None, device="cuda:0"):
+        self.ppo = ppo
+        super().__init__(cfg, backend=backend, lib_path=lib_path, device=device)
+        self.n_envs, self.n_steps, self.obs_dim = ppo.n_envs, ppo.n_steps, cfg.obs_dim
+        self.R = self.n_envs * self.n_steps
+        self.ldo = (self.obs_dim + 3) // 4 * 4
+        self.n_minibatches = self.R // cfg.batch_size
+
+    def _query_sizes(self, cfg, sizes):
+        return self.lib.grl_ppo_query_sizes(C.byref(cfg), C.byref(self.ppo), C.byref(sizes))
+
+    def _create(self, cfg, bufs, h):
+        return self.lib.grl_ppo_create(C.byref(cfg), C.byref(self.ppo), C.byref(bufs), C.byref(h))
+
+    def step(self, obs, done, eps=None):
+        """model.step on the n_envs observations: (actions [n, A] unclipped, values [n], neglogps [n]); recorded in the open slot."""
+        n, A = self.n_envs, self.A
+        obs = np.ascontiguousarray(obs, dtype=np.float32).reshape(n, self.obs_dim)
+        done = np.ascontiguousarray(done, dtype=np.float32).reshape(n)
+        pe = None
+        if eps is not None:
+            eps = np.ascontiguousarray(eps, dtype=np.float32).reshape(n, A)
+            pe = eps.ctypes.data
+        act, val, nlp = np.empty((n, A), np.float32), np.empty(n, np.float32), np.empty(n, np.float32)
+        check(self.lib, self.lib.grl_ppo_step(self.h, obs.ctypes.data, done.ctypes.data, pe, act.ctypes.data, val.ctypes.data,
+                                              nlp.ctypes.data))
+        return act, val, nlp
+
+    def rewards(self, rew):
+        rew = np.ascontiguousarray(rew, dtype=np.float32).reshape(self.n_envs)
+        check(self.lib, self.lib.grl_ppo_rewards(self.h, rew.ctypes.data, self.n_envs))
+
+    def finish(self, last_obs, last_done):
+        last_obs = np.ascontiguousarray(last_obs, dtype=np.float32).reshape(self.n_envs, self.obs_dim)
+        last_done = np.ascontiguousarray(last_done, dtype=np.float32).reshape(self.n_envs)
+        check(self.lib, self.lib.grl_ppo_finish(self.h, last_obs.ctypes.data, last_done.ctypes.data))
+
+    def train(self, perm):
+        """perm [noptepochs, R] int32: one permutation of the rollout rows per epoch."""
+        perm = np.ascontiguousarray(perm, dtype=np.int32).reshape(-1, self.R)
+        check(self.lib, self.lib.grl_ppo_train(self.h, perm.ctypes.data, perm.shape[0]))
+
+    def metrics(self):
+        """[n_updates, 5] of the last ``train``: policy loss, value loss, entropy, approxkl, clipfrac."""
+        out = np.empty((_capi.PPO_MAX_EPOCHS * max(1, self.n_minibatches), 5), np.float32)
+        n = check(self.lib, self.lib.grl_ppo_get_metrics(self.h, out.ctypes.data, out.size))
+        return out[:n].copy()
+
+    def act(self, obs, deterministic=True, eps=None):
+        """model.predict-style action (unclipped) of n <= n_envs observations; eps None with deterministic=False: device draw."""
+        obs = np.ascontiguousarray(obs, dtype=np.float32).reshape(-1, self.obs_dim)
+        n = obs.shape[0]
+        out = np.empty((n, self.A), np.float32)
+        pe = None
+        if not deterministic and eps is not None:
+            eps = np.ascontiguousarray(eps, dtype=np.float32).reshape(n, self.A)
+            pe = eps.ctypes.data
+        check(self.lib, self.lib.grl_act(self.h, obs.ctypes.data, n, 1 if deterministic else 0, pe, out.ctypes.data))
+        return out
+
+    def reset_rollout(self):
+        """Empty the rollout (slot 0 is next), whatever state a stopped run left it in."""
+        self.store("ppo_slots", [0, 0, 0])
+
+    def place_rollout(self, obs, act, val, nlp, rew, done):
+        """Parity tests: a whole rollout through grl_debug_store.  Arrays are [n_envs, n_steps, ...] (row = env * n_steps + t)."""
+        o = np.zeros((self.R, self.ldo), np.float32)
+        o[:, :self.obs_dim] = np.asarray(obs, np.float32).reshape(self.R, self.obs_dim)
+        for name, arr in (("ppo_obs", o), ("ppo_act", act), ("ppo_old_v", val), ("ppo_old_nlp", nlp), ("ppo_rew", rew),
+                          ("ppo_done", done)):
+            self.store(name, arr)
+        self.store("ppo_slots", [self.n_steps, self.n_steps, 0])

@@ -33,3 +33,18 @@ def init_parameters(table, seed=0):
         if name.startswith("target/"):
             out[name] = out["model" + name[len("target"):]].copy()
     return OrderedDict((n, out[n]) for n, *_ in table)
+
+
+def init_ppo_parameters(table, seed=0):
+    """The actor-critic MlpPolicy of stable-baselines 2.10.1 (common/policies.py mlp_extractor + linear, distributions.py
+    proba_distribution_from_latent): orthogonal with gain sqrt(2) for the hidden layers `model/pi_fc*` / `model/vf_fc*`, 0.01 for
+    the `pi` and `q` outputs, 1 for `vf`; zero biases and logstd."""
+    rng = np.random.default_rng(seed)
+    out = OrderedDict()
+    for name, _, _, shape, _ in table:
+        if name.endswith("/w:0"):
+            gain = {"model/pi/w:0": 0.01, "model/q/w:0": 0.01, "model/vf/w:0": 1.0}.get(name, np.sqrt(2.0))
+            out[name] = _ortho(tuple(shape), gain, rng)
+        else:
+            out[name] = np.zeros(shape, np.float32)
+    return out

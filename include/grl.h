@@ -58,6 +58,7 @@ extern "C" {
 #define GRL_ALGO_DQN 1   /* sb.DQN  sb_helper.py:159-165 */
 #define GRL_ALGO_BDQ 2   /* sb.BDQ  sb_helper.py:210-224 */
 #define GRL_ALGO_AE 3    /* depth auto-encoder training: gripperEnv/encoders.py:40-50,70-136, config/encoder.yaml */
+#define GRL_ALGO_PPO 4   /* sb.PPO2 sb_helper.py:137-154; created through grl_ppo_create (grl_ppo_config below) */
 
 typedef struct grl_config {
   int32_t extractor;      /* GRL_EXTRACTOR_*                                                    */
@@ -82,7 +83,7 @@ typedef struct grl_config {
   uint64_t seed;          /* device RNG (replay indices, policy noise) when none are supplied   */
   /* ---- DQN / BDQ (algo != GRL_ALGO_SAC): vector observations, extractor must be GRL_EXTRACTOR_MLP,
      act_dim = q_branches (the replay stores one bin index per action dimension)              */
-  int32_t algo;           /* GRL_ALGO_*                                                         */
+  int32_t algo;           /* GRL_ALGO_* (GRL_ALGO_PPO: see grl_ppo_config for what the fields above mean there)   */
   int32_t q_branches;     /* 1 for DQN; action dimensions for BDQ                               */
   int32_t q_bins;         /* discrete actions (DQN) / num_actions_pad per dimension (BDQ)       */
   int32_t q_n_common;  int32_t q_common[GRL_MAX_LAYERS];   /* BDQ layers[0] (shared trunk)     */
@@ -360,6 +361,51 @@ int grl_ae_reconstruct(grl_handle h, const float* imgs, float* out);
 int grl_encoder_load(grl_handle h, const float* const* weights, const int64_t* numels, int n_arrays);
 /* host: depth [n,64,64,1] float32 -> out [n,100]; n <= act_batch.  Synchronises the stream. */
 int grl_encode(grl_handle h, const float* depth, int n, float* out_feat);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+   PPO2 (GRL_ALGO_PPO): stable-baselines 2.10.1 PPO2 with the actor-critic MlpPolicy on a Box action space, as
+   sb_helper.py:137-154 builds it.  The handle is described by a grl_config AND a grl_ppo_config and is created through the two
+   calls below (grl_query_sizes / grl_create return GRL_ERR_INVALID for algo 4 and name them).  In the grl_config of such a handle
+   extractor is GRL_EXTRACTOR_MLP; obs_dim (observations of any rank flattened in C order, not divided by 255), act_dim and seed
+   mean what they say; n_layers / layers[] describe the pi tower (tanh, widths 1..1024); batch_size is the minibatch row count;
+   act_batch equals n_envs; replay_capacity is R = n_envs * n_steps; normalize is 0; gamma and lr mean what they say; every q_*,
+   ae_* and replay_rgb_u8 field is 0.  The four arenas keep their roles; the rollout lives in the replay arena.
+   Parameters (grl_param_info), TF creation order: model/pi_fc<l>/{w,b}:0 and model/vf_fc<l>/{w,b}:0 with the layer index
+   outermost, model/vf/{w,b}:0, model/pi/{w,b}:0, model/pi/logstd:0 [1, A], model/q/{w,b}:0 (initialised, never read, not trainable). */
+typedef struct grl_ppo_config {
+  int32_t n_envs, n_steps;                 /* R = n_envs * n_steps rollout rows; grl_config.batch_size must divide R */
+  int32_t n_vf_layers; int32_t vf_layers[GRL_MAX_LAYERS];
+  float lam, clip_range, clip_range_vf;    /* clip_range_vf < 0: no value clipping */
+  float ent_coef, vf_coef, max_grad_norm;  /* max_grad_norm <= 0: no clipping */
+  float adam_eps;                          /* 1e-5 */
+} grl_ppo_config;
+int grl_ppo_query_sizes(const grl_config* cfg, const grl_ppo_config* ppo, grl_sizes* out);
+int grl_ppo_create(const grl_config* cfg, const grl_ppo_config* ppo, const grl_buffers* bufs, grl_handle* out);
+
+/* model.step: n == n_envs rows. obs [n, obs_dim], done [n] (flags from before the step), eps_or_null [n, A] are host pointers
+   (NULL: device Philox from cfg.seed). Writes obs / action / value / neglogp / done into slot t of the rollout on the device
+   and copies action (unclipped), value, neglogp to the host outputs; synchronises. GRL_ERR_STATE when the rollout is full or the
+   previous slot has not been closed by grl_ppo_rewards. */
+int grl_ppo_step(grl_handle h, const float* obs, const float* done, const float* eps_or_null,
+                 float* out_act, float* out_val, float* out_nlp);
+int grl_ppo_rewards(grl_handle h, const float* rew, int n);                     /* closes slot t; stream-ordered */
+/* model.value(last obs) + GAE over the full rollout -> adv, ret on the device; GRL_ERR_STATE unless n_steps slots are closed */
+int grl_ppo_finish(grl_handle h, const float* last_obs, const float* last_done);
+/* noptepochs * (R / batch_size) updates. perm: host int32 [noptepochs, R], each row a permutation of 0..R-1 (checked:
+   GRL_ERR_INVALID names the first row that is none); 1 <= noptepochs <= GRL_PPO_MAX_EPOCHS. Needs a finished rollout
+   (GRL_ERR_STATE otherwise) and empties it. Stream-ordered, no synchronisation. */
+#define GRL_PPO_MAX_EPOCHS 64
+int grl_ppo_train(grl_handle h, const int32_t* perm, int noptepochs);
+/* host, synchronises: the five diagnostics (policy loss, value loss, entropy, approxkl, clipfrac) of every update of the last
+   grl_ppo_train call, [n_updates, 5]; returns n_updates, GRL_ERR_INVALID when cap (in floats) is too small */
+int grl_ppo_get_metrics(grl_handle h, float* out, int cap);
+/* On a PPO handle grl_act (n <= act_batch rows; GRL_ACT_DETERMINISTIC: the mean, else a sample -- eps_or_null NULL draws on the
+   device; unclipped; records nothing; the other flags are GRL_ERR_STATE), grl_param_count / _info, grl_reset_optimizer,
+   grl_set_learning_rate, grl_set_stream, grl_profile_* and grl_debug_fetch / _store work; the debug names are "ppo_obs" [R, ld],
+   "ppo_act", "ppo_old_v", "ppo_old_nlp", "ppo_rew", "ppo_done", "ppo_adv", "ppo_ret" (rollout, row = env * n_steps + t),
+   "ppo_last_v", "ppo_last_done", "ppo_mean", "ppo_v" (the last minibatch), "ppo_slots" (grl_debug_store only, three values: slots written,
+   slots closed, finished -- says how far a rollout placed through the other names has got), "grads", "adam_m", "adam_v".  Every other entry point returns
+   GRL_ERR_STATE on a PPO handle before anything moves. */
 
 /* debugging / parity: copy a named internal activation of the last update to the host.
    Names: "x_obs","x_next","feat_pi","feat_vf","feat_tgt","mu","log_std","pi","logp","qf1","qf2",
