@@ -1088,23 +1088,18 @@ static Op dp_apply_oneshot_op(grl_ctx* self, const DpArgs& da) {
   return op;
 }
 
-// The sequences of a multi-update call ending in the exchange: every part of `src` with its last launch (reduction + Adam)
-// replaced by the publishing reduction K1 -- carrying the riders of the next update (`lk`, `g2`, `gx`) except in the call's last
-// update -- and the rest of the exchange `tail` appended.  short_call_graph is the caller's choice, not copied from `src`
-static void close_with_exchange(grl_ctx* h, const DpArgs& d, const CallPlan& src, CallPlan& dst, const LossArgs& lk,
-                                const GatherArgs* g2, int gx, const std::vector<Op>& tail, bool short_call_graph) {
-  dst.clear();
-  dst.alternate = src.alternate;
+// The sequences of a multi-update SAC call ending in the exchange (`ride`: the "gather_ride" form of the call, else "prefetch"):
+// every update assembled by sac_update_ops (plan_sac.inl) and closed by the publishing reduction K1 -- carrying the riders of
+// the next update except in the call's last one -- and the rest of the exchange `tail`.  short_call_graph is the caller's choice
+static void close_with_exchange(grl_ctx* h, const DpArgs& d, bool ride, CallPlan& dst, const std::vector<Op>& tail, bool short_call_graph) {
+  const grl_ctx::SacKit::Riders& r = h->sac_kit.riders[ride];
+  sac_call_plan(*h, dst, ride, [&](int v) {
+    std::vector<Op> close{v == 2 ? dp_k1_op(h, h->red_all, d, h->loss_args, nullptr, 0, "reduce_publish")
+                                 : dp_k1_op(h, h->red_all, d, r.lk, &r.g2, r.gx, "reduce_publish")};
+    close.insert(close.end(), tail.begin() + 1, tail.end());
+    return close;
+  });
   dst.short_call_graph = short_call_graph;
-  for (int v = 0; v < 3; ++v)
-    for (int f = 0; f < (v > 0 && src.alternate ? 2 : 1); ++f) {
-      const std::vector<Op>& from = src.part(v, f);
-      std::vector<Op>& to = dst.part(v, f);
-      to.assign(from.begin(), from.end() - 1);
-      to.push_back(v == 2 ? dp_k1_op(h, h->red_all, d, h->loss_args, nullptr, 0, "reduce_publish")
-                          : dp_k1_op(h, h->red_all, d, lk, g2, gx, "reduce_publish"));
-      to.insert(to.end(), tail.begin() + 1, tail.end());
-    }
 }
 
 int grl_allreduce_connect(grl_handle h, const void* handles) {
@@ -1113,10 +1108,15 @@ int grl_allreduce_connect(grl_handle h, const void* handles) {
   if (!h->dp_buf) return fail(GRL_ERR_STATE, "call grl_allreduce_init first");
   if (h->dp_on) return fail(GRL_ERR_STATE, "already connected");
   const bool qh = h->cfg.algo != GRL_ALGO_SAC;
-  // (DQN / BDQ: the batch means of the loss launch follow the reduction as a launch of their own in the split plan)
+  // the gradient computation without the reduction that ends it (SAC: the recorded closing slot; DQN / BDQ: the batch means of
+  // the loss launch follow the reduction as a launch of their own in the split plan)
   size_t n_body = h->ops_grads.size();
-  while (n_body > 0 && h->ops_grads[n_body - 1].tag == "q_finish") --n_body;
-  if (n_body == 0 || h->ops_grads[n_body - 1].tag != "reduce_slabs" || !h->red_all.tiles)
+  bool ends_in_reduction = !qh && h->sac_kit.close + 1 == (int)n_body;
+  if (qh) {
+    while (n_body > 0 && h->ops_grads[n_body - 1].tag == "q_finish") --n_body;
+    ends_in_reduction = n_body > 0 && h->ops_grads[n_body - 1].tag == "reduce_slabs";
+  }
+  if (!ends_in_reduction || !h->red_all.tiles)
     return fail(GRL_ERR_STATE, "this plan does not end in the slab reduction the exchange publishes from");
   char* flags[DP_MAX_WORLD];
   char* data[DP_MAX_WORLD];
@@ -1177,8 +1177,8 @@ int grl_allreduce_connect(grl_handle h, const void* handles) {
     // (pf_dp keeps short_call_graph off: see plan_q "per_pf")
     h->pf_dp[one].clear();
     h->ride_dp[one].clear();
-    if (h->pf.ok()) close_with_exchange(h, d, h->pf, h->pf_dp[one], h->pf_lk, &h->pf_g2, h->pf_gx, tail, false);
-    if (h->ride.ok()) close_with_exchange(h, d, h->ride, h->ride_dp[one], h->ride_lk, &h->ride_g2, 1, tail, true);
+    if (h->pf.ok()) close_with_exchange(h, d, false, h->pf_dp[one], tail, false);
+    if (h->ride.ok()) close_with_exchange(h, d, true, h->ride_dp[one], tail, true);
   }
   // ---- the overlapped update (grl_allreduce_set_overlap): the staged plan (grl_compute_grads_staged) with both exchanges in
   // the graph.  After heads_dfeat a SIDE LANE forms the dense layers' weight gradients, reduces them (publishing) and
@@ -1197,10 +1197,7 @@ int grl_allreduce_connect(grl_handle h, const void* handles) {
     bool ok = dense.size() <= DP_MAX_RANGES && conv.size() <= DP_MAX_RANGES;
     for (auto& r : dense) ok = ok && r.first % 4 == 0 && r.second % 4 == 0;
     for (auto& r : conv) ok = ok && r.first % 4 == 0 && r.second % 4 == 0;
-    int cut = -1;
-    for (size_t k = 0; k < h->ops_stage0.size(); ++k)
-      if (h->ops_stage0[k].tag == "heads_dfeat") cut = (int)k;
-    ok = ok && h->ops_stage0.back().tag == "reduce_dense" && h->ops_stage1.back().tag == "reduce_conv";
+    const int cut = h->sac_kit.dfeat;       // (the stages copy ops_grads up to here; each ends in its own reduction)
     if (ok && cut >= 0) {
       DpArgs d0 = dp_channel(h, 0, dense, flags, data);
       const DpArgs d1 = dp_channel(h, 1, conv, flags, data);
@@ -1222,6 +1219,14 @@ int grl_allreduce_connect(grl_handle h, const void* handles) {
       L.push_back(dp_wait_op(d1, 1));
       L.push_back(dp_apply_op(h, d0, d1));       // (joins the side lane)
     }
+  }
+  if (!qh) {
+    plan_seq("ops_dp", h->ops_dp); plan_seq("ops_dp1", h->ops_dp1);
+    for (int one = 0; one < 2; ++one) {
+      plan_seq("pf_dp[" + std::to_string(one) + "]", h->pf_dp[one]);
+      plan_seq("ride_dp[" + std::to_string(one) + "]", h->ride_dp[one]);
+    }
+    plan_seq("ops_dp_overlap", h->ops_dp_overlap);
   }
   // ---- the running-statistics merge (grl_norm_update on a connected handle): channel 2, moment blocks behind the three arrays
   memset(&h->dp_norm, 0, sizeof(h->dp_norm));

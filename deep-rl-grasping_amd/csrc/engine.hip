@@ -286,6 +286,20 @@ struct CallPlan {
   void clear() { *this = CallPlan(); }
 };
 
+// "grl plan: seq <list name>  <tag> <tag> ..." -- the launch order of one op list of the SAC plan / the SAC half of connect
+// (GRL_PLAN_DUMP; an empty list prints nothing), and of every non-empty part of a call plan
+static void plan_seq(const std::string& name, const std::vector<Op>& ops) {
+  if (ops.empty()) return;
+  std::string line = "grl plan: seq " + name + " ";
+  for (const Op& o : ops) line += " " + o.tag;
+  plan_note("%s\n", line.c_str());
+}
+static void plan_seq(const std::string& name, const CallPlan& p) {
+  static const char* const part[3] = {".first", ".mid", ".last"};
+  for (int v = 0; v < 3; ++v)
+    for (int f = 0; f < (v > 0 && p.alternate ? 2 : 1); ++f) plan_seq(name + part[v] + (p.alternate && v > 0 ? std::to_string(f) : ""), p.part(v, f));
+}
+
 struct ProfAcc {
   double ms = 0;
   int64_t n = 0;
@@ -364,24 +378,10 @@ struct grl_ctx {
   int64_t* idx_buf;
   float* eps_buf;
   float *x_obs, *x_next;
-  float *a1[3], *a2[3], *a3[3], *feat[3];
+  float* feat[3];
   float *act, *rew, *done;
-  HeadAct hPI, hVF, hQF1, hQF2, hTGT, hQF1PI, hQF2PI;
-  float *pi_a, *logp, *ent;
-  float *d_qf1, *d_qf2, *d_v, *d_qf1pi;
-  HeadGrad gPI, gVF, gQF1, gQF2, gQF1PI;
-  float *da_pi, *dmu, *dls;
-  float *dfeat[2], *g3[2], *g2[2], *g1[2];
-  int ld1 = 64;   // pixel stride of a1 / g1: the two trained networks side by side
-  float* act_p = nullptr;            // [B, Ap] row-padded copy of the minibatch actions (Ap = rup(A, 4))
-  int Ap = 0, ld_d = 1, ld_dm = 0;   // strides of the packed output-gradient buffers (fused heads)
-  bool fused_heads = false;          // heads_kernels.h path (row-local chains) instead of per-layer GEMMs
-  bool heads_mfma = false;           // heads_mfma.h: forward + backward of all heads as ONE launch on 16x16x4 MFMAs
-  float *u_l0[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // layer-0 feature partials: pi, vf, qf1, qf2, target
-  int l0_split = 1;
-  float* g0cat = nullptr;            // [B, 3*H0]: layer-0 gradients of vf | qf1 | qf2
   // act path
-  float *ax, *aa1, *aa2, *aa3, *afeat, *a_eps, *a_out;
+  float *afeat, *a_eps, *a_out;
   float* act_io_host = nullptr;   // SAC: a_eps | a_out live in page-locked host memory (plan_sac.inl)
   float* q_act_host = nullptr;         // DQN / BDQ: the Q-values of the act path in coherent host memory (plan_q.inl)
   // DQN / BDQ, grl_act(GRL_ACT_GREEDY): observations [NA, obs_dim] | overrides [NA, D] | bins [NA, D] in coherent host memory
@@ -392,7 +392,6 @@ struct grl_ctx {
   std::vector<Op> ops_act_greedy[4];   // [(observed by grl_observe) << 1 | (raw: VecNormalize applied on the device)], as ops_act_in
   unsigned* act_done_host = nullptr;   // SAC: completion counter of the act path's last launch (coherent host memory), polled by grl_act
   unsigned act_done_wgs = 0, act_done_seen = 0;    // increments per call (0: no counter, synchronise the stream); expected value
-  HeadAct ahPI;
   // encoder path
   float *enc_w[8];
   bool enc_loaded = false;
@@ -404,7 +403,7 @@ struct grl_ctx {
   std::vector<ReduceDesc> reduces;
   ReduceDesc* d_reduces = nullptr;
 
-  std::vector<Op> ops_rng, ops_gather, ops_grads, ops_apply, ops_act, ops_act_det, ops_act_sto, ops_enc, wgrad_ops;   // ops_rng: gather with device RNG; ops_gather: gather of explicit indices
+  std::vector<Op> ops_rng, ops_gather, ops_grads, ops_apply, ops_act, ops_act_det, ops_act_sto, ops_enc;   // ops_rng: gather with device RNG; ops_gather: gather of explicit indices
   LossArgs loss_args;              // SAC: batch reductions appended to the reduce_slabs launch (fused heads)
   std::vector<Op> ops_grads_apply; // SAC: ops_grads with Adam + Polyak fused into the slab-reduction launch (full updates)
   // Calls of several updates on the device RNG (CallPlan).  SAC "prefetch": the next minibatch is gathered inside the last launch
@@ -418,27 +417,25 @@ struct grl_ctx {
   CallPlan q_pf, per_pf;
   // data parallel: pf / ride ending in the exchange (built at connect): [0] two-shot, [1] one-shot
   CallPlan pf_dp[2], ride_dp[2];
-  float* x_obs_b = nullptr;
-  Op wgrad_conv_alt;                    // the merged weight-gradient launch with conv1's operand in x_obs_b
-  bool have_wgrad_conv_alt = false;
-  ConvStackArgs ride_conv_args;         // arguments of the forward stack as planned (reading x_obs)
-  const HeadsFusedArgs* ride_heads_args = nullptr;   // [3] argument blocks of the head launch (plain, first, later updates)
-  int ride_heads_shape = 0, ride_heads_nblk = 0;
-  LossArgs ride_lk;                     // loss arguments / extras gather the riding reductions carry (data-parallel connect)
-  GatherArgs ride_g2;
-  Op pf_heads[2];
+  // What the updates of a multi-update SAC call are assembled from (plan_sac.inl: sac_update_ops builds every part of pf / ride
+  // and, at connect, of pf_dp / ride_dp from it).  Slots are positions in ops_grads / ops_grads_apply, recorded when the launch
+  // is planned (-1: this plan has no such launch); a launch's tag names it for the profiler, never for the plan.
+  struct SacKit {
+    int stack = -1, heads = -1, dfeat = -1, wgrad_conv = -1, close = -1;   // forward stack, head launch, heads_dfeat, merged weight gradients, closing reduction
+    Op gather[2];               // the call's opening gather: plain / leaving rng_img behind for the image riders (set_img)
+    Op heads_open[2];           // the head launch opening the update: of the call's first update / of a later one (RNG counter += 1)
+    Op heads_ride[2][2];        // [flavour] ... carrying the image gather of the next update into the buffer the flavour does not read
+    Op stack_b, wgrad_conv_b;   // forward stack / merged weight-gradient launch reading the second image buffer (flavour 1)
+    // what the closing launch of a first / middle update carries for the next one: [0] "prefetch" (the whole gather),
+    // [1] "gather_ride" (the per-row extras)
+    struct Riders { LossArgs lk; GatherArgs g2; int gx = 0; } riders[2];
+  } sac_kit;
   float* ae_gp4 = nullptr;               // auto-encoder step: the output gradient's four sub-position planes (plan_ae, MseArgs.gp4)
-  GatherArgs pf_ga;
-  int pf_gx = 0;
   std::vector<Op> ops_grads_apply_per;   // DQN / BDQ with prioritised replay: ... and the priority write-back
   // data parallel, staged (grl_compute_grads_staged): stage 0 ends with the dense (fc + head) gradients final in the
   // bucket, stage 1 is the convolution backward + its weight gradients + the loss reductions
   std::vector<Op> ops_stage0, ops_stage1;
   bool staged_ok = false;
-  bool conv_stack = false;                // conv1 -> conv2 -> conv3 as one sample-local launch (conv_stack.h)
-  bool conv_stack_bwd = false;            // ... and the backward-data of conv3 -> conv2
-  int store_drain = 0;                    // tensor groups of the SAC CNN plan stored write-through (store_drain.h: StoreDrain bits)
-  bool loss_in_reduce = false;
   float grad_scale = 1.f;   // read by the apply op
 
   // data parallel without a host round trip per update (grl_allreduce_*, csrc/dp_kernels.h)
@@ -454,8 +451,6 @@ struct grl_ctx {
   AdamArgs adam_base;
   std::vector<Op> ops_dp;                // two-shot: reduce + publish | reduce-scatter | pull + Adam + Polyak (replaces the last op of ops_grads)
   std::vector<Op> ops_dp1;               // one-shot: reduce + publish | sum of all ranks + Adam + Polyak
-  LossArgs pf_lk;                        // loss arguments / gather of the NEXT update as the prefetching reductions carry them (plan_sac)
-  GatherArgs pf_g2;
   std::vector<Op> dp_body;               // ops_grads without its final reduction (the exchange's first kernel forms the sums)
   std::vector<Op> dp_body_per;           // DQN / BDQ with prioritised replay: the same without the gather (the sampler gathers its rows)
   int dp_mode = 0;                       // 0 auto (one-shot for world <= 2), 1 two-shot, 2 one-shot
