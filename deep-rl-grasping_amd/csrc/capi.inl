@@ -9,9 +9,11 @@
   do {                                                                                                                            \
     if ((h) && (h)->cfg.algo == GRL_ALGO_PPO)                                                                                     \
       return fail(GRL_ERR_STATE, what " is not defined on a PPO handle (PPO handles: grl_ppo_step / _rewards / _finish / _train, grl_act)"); \
+    if ((h) && (h)->cfg.algo == GRL_ALGO_TRPO)                                                                                    \
+      return fail(GRL_ERR_STATE, what " is not defined on a TRPO handle (TRPO handles: grl_ppo_step / _rewards / _finish, grl_trpo_update, grl_act)"); \
   } while (0)
 
-static int check_cfg(const grl_config* c) {
+static int check_cfg(const grl_config* c, bool trpo_call = false) {
   if (!c) return fail(GRL_ERR_INVALID, "null config");
   if (c->algo == GRL_ALGO_AE) {
     if (c->batch_size < 1 || c->batch_size > 4096) return fail(GRL_ERR_INVALID, "batch_size out of range");
@@ -27,8 +29,11 @@ static int check_cfg(const grl_config* c) {
   if (c->batch_size < 1 || c->batch_size > 65536) return fail(GRL_ERR_INVALID, "batch_size out of range");
   if (c->act_dim < 1 || c->act_dim > 64) return fail(GRL_ERR_INVALID, "act_dim out of range");
   if (c->replay_capacity < 1) return fail(GRL_ERR_INVALID, "replay_capacity must be >= 1");
-  if (c->algo < 0 || c->algo > 4) return fail(GRL_ERR_INVALID, "algo must be 0..4");
-  if (c->algo == GRL_ALGO_PPO) {
+  if (c->algo < 0 || c->algo > 4) {
+    if (!(trpo_call && c->algo == GRL_ALGO_TRPO))
+      return fail(GRL_ERR_INVALID, "algo must be 0..4 (5, GRL_ALGO_TRPO, needs a grl_trpo_config: grl_trpo_query_sizes / grl_trpo_create)");
+  }
+  if (c->algo == GRL_ALGO_PPO || c->algo == GRL_ALGO_TRPO) {      // (a TRPO handle's grl_config is read as a PPO handle's)
     if (c->extractor != GRL_EXTRACTOR_MLP) return fail(GRL_ERR_INVALID, "PPO runs on flattened observations (MLP extractor)");
     if (c->obs_dim < 1 || c->obs_dim > 64 * 64 * 5) return fail(GRL_ERR_INVALID, "PPO: obs_dim must be 1..20480");
     for (int l = 0; l < c->n_layers; ++l)
@@ -99,11 +104,33 @@ static int check_ppo(const grl_config* c, const grl_ppo_config* p) {
   return GRL_OK;
 }
 
-static int query_sizes(const grl_config* cfg, const grl_ppo_config* ppo, grl_sizes* out) {
+static int check_trpo(const grl_config* c, const grl_trpo_config* p) {
+  if (int e = check_cfg(c, true)) return e;
+  if (c->algo != GRL_ALGO_TRPO) return fail(GRL_ERR_INVALID, "grl_trpo_query_sizes / grl_trpo_create take a grl_config with algo = GRL_ALGO_TRPO");
+  if (!p) return fail(GRL_ERR_INVALID, "null TRPO config");
+  if (p->n_steps < 1 || p->n_steps > 65536) return fail(GRL_ERR_INVALID, "TRPO: n_steps must be 1..65536");
+  if (c->act_batch != 1) return fail(GRL_ERR_INVALID, "TRPO: act_batch must be 1 (one environment)");
+  if (c->replay_capacity != p->n_steps) return fail(GRL_ERR_INVALID, "TRPO: replay_capacity must equal n_steps");
+  if (p->vf_batch < 1 || c->batch_size != p->vf_batch) return fail(GRL_ERR_INVALID, "TRPO: batch_size must equal vf_batch >= 1");
+  if (p->n_vf_layers < 1 || p->n_vf_layers > GRL_MAX_LAYERS) return fail(GRL_ERR_INVALID, "TRPO: n_vf_layers out of range");
+  for (int l = 0; l < p->n_vf_layers; ++l)
+    if (p->vf_layers[l] < 1 || p->vf_layers[l] > 1024) return fail(GRL_ERR_INVALID, "TRPO: tower widths must be 1..1024");
+  if (p->cg_iters < 1 || p->cg_iters > GRL_TRPO_MAX_CG) return fail(GRL_ERR_INVALID, "TRPO: cg_iters must be 1..64");
+  if (p->ls_steps < 1 || p->ls_steps > GRL_TRPO_MAX_LS) return fail(GRL_ERR_INVALID, "TRPO: ls_steps must be 1..16");
+  if (p->fvp_stride < 1) return fail(GRL_ERR_INVALID, "TRPO: fvp_stride must be >= 1");
+  if (!(p->lam >= 0.f && p->lam <= 1.f)) return fail(GRL_ERR_INVALID, "TRPO: lam must be in [0, 1]");
+  if (!(p->max_kl > 0.f)) return fail(GRL_ERR_INVALID, "TRPO: max_kl must be > 0");
+  if (!(p->cg_damping >= 0.f)) return fail(GRL_ERR_INVALID, "TRPO: cg_damping must be >= 0");
+  if (!(p->adam_eps > 0.f)) return fail(GRL_ERR_INVALID, "TRPO: adam_eps must be > 0");
+  return GRL_OK;
+}
+
+static int query_sizes(const grl_config* cfg, const grl_ppo_config* ppo, grl_sizes* out, const grl_trpo_config* trpo = nullptr) {
   if (!out) return fail(GRL_ERR_INVALID, "null out");
   grl_ctx ctx;
   ctx.cfg = *cfg;
   if (ppo) ctx.pcfg = *ppo;
+  if (trpo) ctx.tcfg = *trpo;
   ctx.dry = true;
   if (int e = ctx.plan()) return e;
   out->state_bytes = ctx.st.off + 256;
@@ -124,6 +151,10 @@ int grl_ppo_query_sizes(const grl_config* cfg, const grl_ppo_config* ppo, grl_si
   if (int e = check_ppo(cfg, ppo)) return e;
   return query_sizes(cfg, ppo, out);
 }
+int grl_trpo_query_sizes(const grl_config* cfg, const grl_trpo_config* trpo, grl_sizes* out) {
+  if (int e = check_trpo(cfg, trpo)) return e;
+  return query_sizes(cfg, nullptr, out, trpo);
+}
 
 // Prioritised replay with an empty ring: all leaves 0, PerState at its starting values.  The block sums / minima (per.bsum,
 // per.bmin) need no reset: the first update of every prioritised call rebuilds ALL of them from the leaves below the ring's fill
@@ -138,12 +169,14 @@ static hipError_t per_start(grl_ctx* h) {
   return hipMemcpy(h->per.st, &ps, sizeof(ps), hipMemcpyHostToDevice);
 }
 
-static int create_handle(const grl_config* cfg, const grl_ppo_config* ppo, const grl_buffers* bufs, grl_handle* out) {
+static int create_handle(const grl_config* cfg, const grl_ppo_config* ppo, const grl_buffers* bufs, grl_handle* out,
+                         const grl_trpo_config* trpo = nullptr) {
   if (!bufs || !out || !bufs->state || !bufs->grads || !bufs->work || !bufs->replay)
     return fail(GRL_ERR_INVALID, "null buffers");
   grl_ctx* h = new grl_ctx();
   h->cfg = *cfg;
   if (ppo) h->pcfg = *ppo;
+  if (trpo) h->tcfg = *trpo;
   h->st.base = (char*)bufs->state; h->gr.base = (char*)bufs->grads;
   h->wk.base = (char*)bufs->work; h->rp.base = (char*)bufs->replay;
   if (int e = h->plan()) { delete h; return e; }
@@ -179,6 +212,10 @@ static int create_handle(const grl_config* cfg, const grl_ppo_config* ppo, const
     e = hipMemset(h->ppo_dev, 0, sizeof(PpoDev));
     if (e != hipSuccess) { delete h; return fail(GRL_ERR_HIP, std::string("ppo init: ") + hipGetErrorString(e)); }
   }
+  if (h->trpo_dev) {
+    e = hipMemset(h->trpo_dev, 0, sizeof(TrpoDev));
+    if (e != hipSuccess) { delete h; return fail(GRL_ERR_HIP, std::string("trpo init: ") + hipGetErrorString(e)); }
+  }
   *out = h;
   return GRL_OK;
 }
@@ -191,6 +228,10 @@ int grl_create(const grl_config* cfg, const grl_buffers* bufs, grl_handle* out) 
 int grl_ppo_create(const grl_config* cfg, const grl_ppo_config* ppo, const grl_buffers* bufs, grl_handle* out) {
   if (int e = check_ppo(cfg, ppo)) return e;
   return create_handle(cfg, ppo, bufs, out);
+}
+int grl_trpo_create(const grl_config* cfg, const grl_trpo_config* trpo, const grl_buffers* bufs, grl_handle* out) {
+  if (int e = check_trpo(cfg, trpo)) return e;
+  return create_handle(cfg, nullptr, bufs, out, trpo);
 }
 
 int grl_destroy(grl_handle h) {
@@ -813,6 +854,18 @@ static int ppo_receive(grl_handle h, int n, float* out_act, float* out_val, floa
     if (!(h)) return fail(GRL_ERR_INVALID, "null handle");                                                       \
     if ((h)->cfg.algo != GRL_ALGO_PPO) return fail(GRL_ERR_STATE, what " is defined for PPO handles (grl_ppo_create)"); \
   } while (0)
+// the rollout calls serve both kinds of handle that keep one (a TRPO handle: one environment)
+#define ROLLOUT_ONLY(h, what)                                                                                    \
+  do {                                                                                                           \
+    if (!(h)) return fail(GRL_ERR_INVALID, "null handle");                                                       \
+    if ((h)->cfg.algo != GRL_ALGO_PPO && (h)->cfg.algo != GRL_ALGO_TRPO)                                         \
+      return fail(GRL_ERR_STATE, what " is defined for PPO and TRPO handles (grl_ppo_create, grl_trpo_create)");  \
+  } while (0)
+#define TRPO_ONLY(h, what)                                                                                       \
+  do {                                                                                                           \
+    if (!(h)) return fail(GRL_ERR_INVALID, "null handle");                                                       \
+    if ((h)->cfg.algo != GRL_ALGO_TRPO) return fail(GRL_ERR_STATE, what " is defined for TRPO handles (grl_trpo_create)"); \
+  } while (0)
 
 static int ppo_act(grl_handle h, const float* obs, int n, int flags, const float* eps, float* out) {
   if (flags & ~GRL_ACT_DETERMINISTIC) return fail(GRL_ERR_STATE, "a PPO handle acts on the observations handed to it: GRL_ACT_RAW_OBS / GRL_ACT_OBSERVED / GRL_ACT_GREEDY are not defined on it");
@@ -826,7 +879,7 @@ static int ppo_act(grl_handle h, const float* obs, int n, int flags, const float
 }
 
 int grl_ppo_step(grl_handle h, const float* obs, const float* done, const float* eps, float* out_act, float* out_val, float* out_nlp) {
-  PPO_ONLY(h, "grl_ppo_step");
+  ROLLOUT_ONLY(h, "grl_ppo_step");
   if (!obs || !done || !out_act || !out_val || !out_nlp) return fail(GRL_ERR_INVALID, "null argument");
   if (h->ppo_stepped >= h->pcfg.n_steps) return fail(GRL_ERR_STATE, "the rollout is full: grl_ppo_finish and grl_ppo_train empty it");
   if (h->ppo_stepped != h->ppo_closed) return fail(GRL_ERR_STATE, "the previous slot is still open: grl_ppo_rewards closes it");
@@ -839,7 +892,7 @@ int grl_ppo_step(grl_handle h, const float* obs, const float* done, const float*
 }
 
 int grl_ppo_rewards(grl_handle h, const float* rew, int n) {
-  PPO_ONLY(h, "grl_ppo_rewards");
+  ROLLOUT_ONLY(h, "grl_ppo_rewards");
   if (!rew || n != h->NA) return fail(GRL_ERR_INVALID, "grl_ppo_rewards takes n_envs rewards");
   if (h->ppo_stepped != h->ppo_closed + 1) return fail(GRL_ERR_STATE, "no open slot: grl_ppo_step opens one");
   if (int e = copy_from_caller(h, h->ppo_in + (size_t)h->NA * (h->ppo_ldo + 1 + h->A), rew, (size_t)n * 4)) return e;
@@ -850,7 +903,7 @@ int grl_ppo_rewards(grl_handle h, const float* rew, int n) {
 }
 
 int grl_ppo_finish(grl_handle h, const float* last_obs, const float* last_done) {
-  PPO_ONLY(h, "grl_ppo_finish");
+  ROLLOUT_ONLY(h, "grl_ppo_finish");
   if (!last_obs || !last_done) return fail(GRL_ERR_INVALID, "null argument");
   if (h->ppo_closed != h->pcfg.n_steps) return fail(GRL_ERR_STATE, "the rollout is not full: n_steps slots must be closed before grl_ppo_finish");
   if (int e = ppo_send(h, last_obs, last_done, nullptr, h->NA)) return e;
@@ -862,23 +915,27 @@ int grl_ppo_finish(grl_handle h, const float* last_obs, const float* last_done) 
   return GRL_OK;
 }
 
+// every row of perm [rows, R] a permutation of 0..R-1 (grl_ppo_train, grl_trpo_update)
+static int check_perm_rows(const int32_t* perm, int rows, int64_t R) {
+  std::vector<uint8_t> seen((size_t)R);
+  for (int e = 0; e < rows; ++e) {
+    std::fill(seen.begin(), seen.end(), 0);
+    for (int64_t i = 0; i < R; ++i) {
+      const int32_t v = perm[(int64_t)e * R + i];
+      if (v < 0 || v >= R || seen[(size_t)v]) return fail(GRL_ERR_INVALID, "perm row " + std::to_string(e) + " is no permutation of 0.." + std::to_string(R - 1));
+      seen[(size_t)v] = 1;
+    }
+  }
+  return GRL_OK;
+}
+
 int grl_ppo_train(grl_handle h, const int32_t* perm, int noptepochs) {
   PPO_ONLY(h, "grl_ppo_train");
   if (!perm || noptepochs < 1 || noptepochs > GRL_PPO_MAX_EPOCHS)
     return fail(GRL_ERR_INVALID, "grl_ppo_train takes 1.." + std::to_string(GRL_PPO_MAX_EPOCHS) + " permutations");
   if (!h->ppo_finished) return fail(GRL_ERR_STATE, "no finished rollout: grl_ppo_finish forms the advantages grl_ppo_train reads");
   const int64_t R = (int64_t)h->pcfg.n_envs * h->pcfg.n_steps;
-  {
-    std::vector<uint8_t> seen((size_t)R);
-    for (int e = 0; e < noptepochs; ++e) {
-      std::fill(seen.begin(), seen.end(), 0);
-      for (int64_t i = 0; i < R; ++i) {
-        const int32_t v = perm[(int64_t)e * R + i];
-        if (v < 0 || v >= R || seen[(size_t)v]) return fail(GRL_ERR_INVALID, "perm row " + std::to_string(e) + " is no permutation of 0.." + std::to_string(R - 1));
-        seen[(size_t)v] = 1;
-      }
-    }
-  }
+  if (int e = check_perm_rows(perm, noptepochs, R)) return e;
   if (int e = copy_from_caller(h, h->ppo_perm, perm, (size_t)noptepochs * R * 4)) return e;
   HIPCHK(hipMemsetAsync(&h->ppo_dev->cursor, 0, 4, h->stream));
   const int n_updates = noptepochs * (int)(R / h->cfg.batch_size);
@@ -909,10 +966,58 @@ int grl_ppo_get_metrics(grl_handle h, float* out, int cap) {
   return nu;
 }
 
+// ---------------------------------------------------------------------------------------------- TRPO (plan_trpo.inl)
+int grl_trpo_update(grl_handle h, const int32_t* vf_perm, int vf_iters) {
+  TRPO_ONLY(h, "grl_trpo_update");
+  if (vf_iters < 0 || vf_iters > GRL_PPO_MAX_EPOCHS || (vf_iters > 0 && !vf_perm))
+    return fail(GRL_ERR_INVALID, "grl_trpo_update takes 0.." + std::to_string(GRL_PPO_MAX_EPOCHS) + " permutations");
+  if (!h->ppo_finished) return fail(GRL_ERR_STATE, "no finished rollout: grl_ppo_finish forms the advantages grl_trpo_update reads");
+  const int64_t T = h->tcfg.n_steps, B = h->tcfg.vf_batch, per = T / B;
+  if (int e = check_perm_rows(vf_perm, vf_iters, T)) return e;
+  const int n_vf = (int)(vf_iters * per);
+  if (n_vf > 0) {      // the minibatches of every row back to back (the tail of a row is dropped): minibatch u takes [u B, (u + 1) B)
+    std::vector<int32_t> packed((size_t)n_vf * B);
+    for (int e = 0; e < vf_iters; ++e) memcpy(packed.data() + (size_t)e * per * B, vf_perm + (size_t)e * T, (size_t)(per * B) * 4);
+    // (`packed` is pageable: copy_from_caller has staged it when it returns, as it does grl_ppo_train's caller buffer)
+    if (int e = copy_from_caller(h, h->ppo_perm, packed.data(), packed.size() * 4)) return e;
+  }
+  HIPCHK(hipMemsetAsync(&h->ppo_dev->cursor, 0, 4, h->stream));
+  if (int e = h->run_seq("trpo_policy", {&h->ops_trpo_policy})) return e;
+  if (n_vf > 0)
+    if (int e = h->run_repeated("trpo_vf", {&h->ops_trpo_vf}, n_vf)) return e;
+  HIPCHK(hipMemsetAsync(&h->ppo_dev->slot, 0, 4, h->stream));      // the rollout is empty again
+  HIPCHK(hipGetLastError());
+  h->ppo_updates = n_vf;
+  h->ppo_stepped = h->ppo_closed = 0;
+  h->ppo_finished = false;
+  return GRL_OK;
+}
+
+int grl_trpo_get_metrics(grl_handle h, float* out, int cap) {
+  TRPO_ONLY(h, "grl_trpo_get_metrics");
+  if (!out) return fail(GRL_ERR_INVALID, "null argument");
+  if (cap < GRL_TRPO_METRICS) return fail(GRL_ERR_INVALID, "metrics buffer too small");
+  TrpoDev d;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpy(&d, h->trpo_dev, sizeof(d), hipMemcpyDeviceToHost));
+  for (int k = 0; k < 5; ++k) out[k] = d.before[k];
+  out[5] = (float)d.ls_index; out[6] = d.trial[0]; out[7] = d.trial[1];
+  out[8] = (float)d.cg_iters; out[9] = d.rr[std::max(0, std::min(d.cg_iters, GRL_TRPO_MAX_CG))]; out[10] = d.shs;
+  return GRL_TRPO_METRICS;
+}
+
+int grl_trpo_debug_fvp(grl_handle h) {
+  TRPO_ONLY(h, "grl_trpo_debug_fvp");
+  if (h->ppo_closed != h->pcfg.n_steps) return fail(GRL_ERR_STATE, "the rollout is not full: the Fisher rows are taken from it");
+  if (int e = h->run_seq("trpo_fvp", {&h->ops_trpo_fvp})) return e;
+  HIPCHK(hipGetLastError());
+  return GRL_OK;
+}
+
 int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps, float* out) {
   if (!h || !out || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (flags & ~(GRL_ACT_DETERMINISTIC | GRL_ACT_RAW_OBS | GRL_ACT_OBSERVED | GRL_ACT_GREEDY)) return fail(GRL_ERR_INVALID, "unknown flag bits");
-  if (h->cfg.algo == GRL_ALGO_PPO) return ppo_act(h, obs, n, flags, eps, out);
+  if (h->cfg.algo == GRL_ALGO_PPO || h->cfg.algo == GRL_ALGO_TRPO) return ppo_act(h, obs, n, flags, eps, out);
   const int deterministic = flags & GRL_ACT_DETERMINISTIC;
   const bool raw = (flags & GRL_ACT_RAW_OBS) != 0;        // raw observations: VecNormalize applied on the device (grl_norm_update statistics)
   const bool observed = (flags & GRL_ACT_OBSERVED) != 0;  // act on what grl_observe uploaded: no second upload
@@ -1396,7 +1501,7 @@ int64_t grl_debug_fetch(grl_handle h, const char* name, float* out, int64_t cap)
 
 int64_t grl_debug_store(grl_handle h, const char* name, const float* in, int64_t n) {
   if (!h || !name || !in) return fail(GRL_ERR_INVALID, "null argument");
-  if (h->cfg.algo == GRL_ALGO_PPO && !strcmp(name, "ppo_slots")) {      // a rollout placed through the names below: how far it has got
+  if ((h->cfg.algo == GRL_ALGO_PPO || h->cfg.algo == GRL_ALGO_TRPO) && !strcmp(name, "ppo_slots")) {      // a rollout placed through the names below: how far it has got
     if (n != 3) return fail(GRL_ERR_INVALID, "ppo_slots takes three values: slots written, slots closed, finished");
     const int32_t st = (int32_t)in[0], cl = (int32_t)in[1];
     if (cl < 0 || cl > h->pcfg.n_steps || st < cl || st > cl + 1 || st > h->pcfg.n_steps) return fail(GRL_ERR_INVALID, "ppo_slots out of range");

@@ -2,6 +2,7 @@
 // graph machinery); the launch plans and the C ABI of include/grl.h are included parts of this translation unit:
 //   plan_sac.inl (SAC update, act, encoder forward)   plan_q.inl (DQN / BDQ, prioritised replay)
 //   plan_ae.inl  (auto-encoder training)              plan_ppo.inl (PPO2: rollout, GAE, clipped update)
+//   plan_trpo.inl (TRPO: CG natural-gradient step, line search, value fit -- over plan_ppo.inl's policy and rollout)
 //   capi.inl     (extern "C" entry points)
 // The element-wise, replay, prioritised-sampling and exchange kernels are compiled here; the GEMM and head kernels in
 // gemm_fwd.hip / gemm_bwd.hip / gemm_wgrad.hip / heads.hip behind the launchers of launch.h.
@@ -47,6 +48,8 @@
 #include "dp_kernels.h"
 #define GRL_PPO_TYPES_ONLY          // (the PPO kernels are instantiated in ppo.hip)
 #include "ppo_kernels.h"
+#define GRL_TRPO_TYPES_ONLY         // (the TRPO kernels in trpo.hip)
+#include "trpo_kernels.h"
 
 namespace grl {
 
@@ -1459,8 +1462,10 @@ struct grl_ctx {
     return rt;
   }
 
+  // (bucket: a vector laid out like the gradient bucket that receives the sums instead of it -- plan_trpo.inl)
   void add_wgrad(std::vector<IgemmProb>& probs, IgemmProb p, int64_t w_off, int64_t w_rows_off, int rows,
-                 int64_t b_off) {
+                 int64_t b_off, float* bucket = nullptr) {
+    float* const grads = bucket ? bucket : this->grads;
     probs.push_back(p);
     ReduceDesc r;
     memset(&r, 0, sizeof(r));
@@ -1513,6 +1518,12 @@ struct grl_ctx {
   int ppo_stepped = 0, ppo_closed = 0, ppo_updates = 0;     // slots written / closed by rewards; updates of the last training call
   bool ppo_finished = false;                                // advantages and returns of the full rollout are on the device
   std::vector<Op> ops_ppo_step[2], ops_ppo_finish, ops_ppo_act[3], ops_ppo_rew, ops_ppo_update;   // [eps handed over | Philox]; act: mean | eps | Philox
+  int plan_trpo();     // TRPO (the policy, rollout and GAE of plan_ppo): natural-gradient step, line search, value fit
+  // TRPO state (plan_trpo.inl): its configuration block (pcfg is filled from it), the device words, the launch lists of the
+  // policy step, of one value minibatch and of the debug Fisher product; value minibatches of the last update
+  grl_trpo_config tcfg = {};
+  TrpoDev* trpo_dev = nullptr;
+  std::vector<Op> ops_trpo_policy, ops_trpo_vf, ops_trpo_fvp;
   int plan_ae_general(const AeNet& net);   // ... of any supported network but the shipped one (GRL_TUNE ae_general=1: that one too)
   int enc_dim = 100;   // floats per image grl_encode returns (auto-encoder handles: their encoding_dim)
   float* ae_x = nullptr;            // [B, 4096] minibatch of depth images (staged per step)
@@ -1553,7 +1564,7 @@ static ConvGeom cnn_geom(int l, int C_img) {
 
 // --------------------------------------------------------------------------------------------------
 int grl_ctx::plan() {
-  const int e = cfg.algo == GRL_ALGO_SAC ? plan_sac() : (cfg.algo == GRL_ALGO_AE ? plan_ae() : (cfg.algo == GRL_ALGO_PPO ? plan_ppo() : plan_q()));
+  const int e = cfg.algo == GRL_ALGO_SAC ? plan_sac() : (cfg.algo == GRL_ALGO_AE ? plan_ae() : (cfg.algo == GRL_ALGO_PPO ? plan_ppo() : (cfg.algo == GRL_ALGO_TRPO ? plan_trpo() : plan_q())));
   sw.note();
   return e;
 }
@@ -1562,6 +1573,7 @@ int grl_ctx::plan() {
 #include "plan_q.inl"
 #include "plan_ae.inl"
 #include "plan_ppo.inl"
+#include "plan_trpo.inl"
 
 int grl_ctx::run_ops(std::vector<Op>& ops) {
   if (!prof) {

@@ -132,15 +132,17 @@ struct PpoPlanner {
     op.run = [dd, n, rows, max_h, bwd](hipStream_t s) { bwd ? launch_tanh_bwd(dd, n, rows, max_h, s) : launch_tanh_fwd(dd, n, rows, max_h, s); };
     ops.push_back(op);
   }
-  void forward(std::vector<Op>& ops, const float* x, int rows, const PpoActs& a, const char* tag) {
+  // (towers: bit 0 pi, bit 1 vf -- plan_trpo.inl runs them apart)
+  void forward(std::vector<Op>& ops, const float* x, int rows, const PpoActs& a, const char* tag, int towers = 3) {
     const std::string t(tag);
+    auto on = [&](int tw, int l) { return ((towers >> tw) & 1) && l < T[tw].L(); };
     for (int l = 0; l < std::max(T[0].L(), T[1].L()); ++l) {
       std::vector<IgemmProb> pr;
       std::vector<TanhDesc> td;
       int n_here = 0;
-      for (int tw = 0; tw < 2; ++tw) n_here += l < T[tw].L() ? 1 : 0;
+      for (int tw = 0; tw < 2; ++tw) n_here += on(tw, l) ? 1 : 0;
       for (int tw = 0; tw < 2; ++tw) {
-        if (l >= T[tw].L()) continue;
+        if (!on(tw, l)) continue;
         const int N = T[tw].width[l];
         const float* in = l == 0 ? x : a.z[tw][l - 1];
         const int ldin = l == 0 ? ldo : T[tw].width[l - 1], K = l == 0 ? od : T[tw].width[l - 1];
@@ -167,6 +169,7 @@ struct PpoPlanner {
     }
     std::vector<IgemmProb> po;
     for (int tw = 0; tw < 2; ++tw) {
+      if (!on(tw, 0)) continue;
       const int Lt = T[tw].L(), H = T[tw].width.back();
       po.push_back(h.dense_fwd(a.z[tw][Lt - 1], H, H, nullptr, 0, 0, rows, P + T[tw].w[Lt], T[tw].out, P + T[tw].b[Lt], a.out[tw], a.ld_out[tw], ACT_NONE));
     }

@@ -45,6 +45,20 @@ class GrlPpoConfig(C.Structure):
 PPO_MAX_EPOCHS = 64      # GRL_PPO_MAX_EPOCHS
 
 
+class GrlTrpoConfig(C.Structure):
+    """include/grl.h: grl_trpo_config -- what a TRPO handle needs beside its GrlConfig."""
+    _fields_ = [
+        ("n_steps", C.c_int32),
+        ("n_vf_layers", C.c_int32), ("vf_layers", C.c_int32 * GRL_MAX_LAYERS),
+        ("cg_iters", C.c_int32), ("ls_steps", C.c_int32), ("fvp_stride", C.c_int32), ("vf_batch", C.c_int32),
+        ("lam", C.c_float), ("max_kl", C.c_float), ("cg_damping", C.c_float), ("ent_coef", C.c_float),
+        ("adam_eps", C.c_float),
+    ]
+
+
+TRPO_METRICS = 11        # GRL_TRPO_METRICS
+
+
 class GrlSizes(C.Structure):
     _fields_ = [("state_bytes", C.c_size_t), ("grads_bytes", C.c_size_t), ("work_bytes", C.c_size_t),
                 ("replay_bytes", C.c_size_t), ("n_params", C.c_int64), ("n_trainable", C.c_int64)]
@@ -74,6 +88,7 @@ EXPORTS = [
     "grl_state_size", "grl_state_export", "grl_state_import", "grl_replay_segments",
     "grl_ppo_query_sizes", "grl_ppo_create", "grl_ppo_step", "grl_ppo_rewards", "grl_ppo_finish", "grl_ppo_train",
     "grl_ppo_get_metrics",
+    "grl_trpo_query_sizes", "grl_trpo_create", "grl_trpo_update", "grl_trpo_get_metrics", "grl_trpo_debug_fvp",
 ]
 
 
@@ -169,6 +184,11 @@ def load_library(path=None):
     lib.grl_ppo_finish.argtypes = [vp, f32p, f32p]
     lib.grl_ppo_train.argtypes = [vp, vp, i32]
     lib.grl_ppo_get_metrics.argtypes = [vp, f32p, i32]
+    lib.grl_trpo_query_sizes.argtypes = [C.POINTER(GrlConfig), C.POINTER(GrlTrpoConfig), C.POINTER(GrlSizes)]
+    lib.grl_trpo_create.argtypes = [C.POINTER(GrlConfig), C.POINTER(GrlTrpoConfig), C.POINTER(GrlBuffers), C.POINTER(vp)]
+    lib.grl_trpo_update.argtypes = [vp, vp, i32]
+    lib.grl_trpo_get_metrics.argtypes = [vp, f32p, i32]
+    lib.grl_trpo_debug_fvp.argtypes = [vp]
     return lib
 
 
@@ -306,3 +326,24 @@ def make_ppo_config(obs_dim, act_dim, n_envs=1, n_steps=128, nminibatches=4, pi_
     ppo.max_grad_norm = 0.0 if max_grad_norm is None else max_grad_norm
     ppo.adam_eps = adam_eps
     return cfg, ppo
+
+
+def make_trpo_config(obs_dim, act_dim, timesteps_per_batch=1024, pi_layers=(64, 64), vf_layers=(64, 64), gamma=0.99, lam=0.98,
+                     max_kl=0.01, cg_iters=10, cg_damping=1e-2, entcoeff=0.0, vf_stepsize=3e-4, ls_steps=10, fvp_stride=5,
+                     vf_batch=128, adam_eps=1e-8, seed=0):
+    """(GrlConfig, GrlTrpoConfig) of a TRPO handle (stable-baselines 2.10.1 TRPO + actor-critic MlpPolicy, Box actions, one
+    environment).  ls_steps, fvp_stride and vf_batch are constants of stable-baselines (10, 5, 128); tests vary ls_steps."""
+    if len(vf_layers) > GRL_MAX_LAYERS:
+        raise GrlError("at most %d hidden layers are supported" % GRL_MAX_LAYERS)
+    cfg = make_config("mlp", obs_dim=int(obs_dim), act_dim=int(act_dim), layers=tuple(pi_layers), batch_size=int(vf_batch),
+                      act_batch=1, replay_capacity=int(timesteps_per_batch), normalize=False, gamma=gamma, lr=vf_stepsize, seed=seed)
+    cfg.algo = 5
+    cfg.tau = cfg.clip_obs = cfg.clip_reward = cfg.norm_eps = cfg.target_entropy = 0.0
+    t = GrlTrpoConfig()
+    t.n_steps = int(timesteps_per_batch)
+    t.n_vf_layers = len(vf_layers)
+    for i, h in enumerate(vf_layers):
+        t.vf_layers[i] = int(h)
+    t.cg_iters, t.ls_steps, t.fvp_stride, t.vf_batch = int(cg_iters), int(ls_steps), int(fvp_stride), int(vf_batch)
+    t.lam, t.max_kl, t.cg_damping, t.ent_coef, t.adam_eps = lam, max_kl, cg_damping, entcoeff, adam_eps
+    return cfg, t

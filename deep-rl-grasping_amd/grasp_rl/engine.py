@@ -855,3 +855,57 @@ class PpoEngine(SacEngine):
                           ("ppo_done", done)):
             self.store(name, arr)
         self.store("ppo_slots", [self.n_steps, self.n_steps, 0])
+
+
+class TrpoEngine(PpoEngine):
+    """TRPO handle (``_capi.make_trpo_config``): the rollout calls are PpoEngine's with one environment (``done`` is the step's
+    episode_start; ``finish`` forms V(last observation), GAE and tdlamret); ``update`` runs the natural-gradient policy step and
+    the value fit of one learn iteration on the device."""
+
+    METRIC_NAMES = ("optimgain", "meankl", "entbonus", "surrgain", "meanent", "ls_index", "trial_optimgain", "trial_meankl",
+                    "cg_iters", "rr", "shs")
+
+    def __init__(self, cfg, trpo, backend=None, lib_path=None, device="cuda:0"):
+        self.trpo = trpo
+        ppo = _capi.GrlPpoConfig()      # (what PpoEngine reads: one environment of n_steps rows)
+        ppo.n_envs, ppo.n_steps = 1, trpo.n_steps
+        super().__init__(cfg, ppo, backend=backend, lib_path=lib_path, device=device)
+        self.T, self.vf_batch = trpo.n_steps, trpo.vf_batch
+        self.n_minibatches = self.T // self.vf_batch
+
+    def _query_sizes(self, cfg, sizes):
+        return self.lib.grl_trpo_query_sizes(C.byref(cfg), C.byref(self.trpo), C.byref(sizes))
+
+    def _create(self, cfg, bufs, h):
+        return self.lib.grl_trpo_create(C.byref(cfg), C.byref(self.trpo), C.byref(bufs), C.byref(h))
+
+    def train(self, perm):
+        raise GrlError("a TRPO handle updates with update(vf_perm)")
+
+    def update(self, vf_perm=None):
+        """vf_perm [vf_iters, T] int32, each row a permutation of the rollout rows (None: no value fit)."""
+        if vf_perm is None or len(vf_perm) == 0:
+            check(self.lib, self.lib.grl_trpo_update(self.h, None, 0))
+            return
+        vf_perm = np.ascontiguousarray(vf_perm, dtype=np.int32).reshape(-1, self.T)
+        check(self.lib, self.lib.grl_trpo_update(self.h, vf_perm.ctypes.data, vf_perm.shape[0]))
+
+    def metrics(self):
+        """The last update: dict of METRIC_NAMES (ls_index: accepted trial, -1 restored, -2 zero gradient)."""
+        out = np.empty(_capi.TRPO_METRICS, np.float32)
+        check(self.lib, self.lib.grl_trpo_get_metrics(self.h, out.ctypes.data, out.size))
+        m = {k: float(v) for k, v in zip(self.METRIC_NAMES, out)}
+        m["ls_index"], m["cg_iters"] = int(m["ls_index"]), int(m["cg_iters"])
+        return m
+
+    def fisher_vector_product(self, vec):
+        """Parity: F(vec) at the current parameters over the Fisher rows of the full rollout on the device; vec and the result
+        are laid out like the gradient bucket ([n_trainable]).  The entries of the value variables are ignored: they are
+        cleared here, since the engine expects them zero, and come back zero."""
+        vec = np.array(vec, np.float32).reshape(-1)
+        for name, off, numel, _, trainable in self.table:
+            if trainable and "/pi" not in name:
+                vec[off:off + numel] = 0.0
+        self.store("trpo_fvp_in", vec)
+        check(self.lib, self.lib.grl_trpo_debug_fvp(self.h))
+        return self.fetch("trpo_fvp_out", (int(self.sizes.n_trainable),))

@@ -2,3 +2,4 @@
 (SURVEY.md 8b), re-implemented over the HIP engine.  ``deep-rl-grasping_amd/stable_baselines`` re-exports
 these modules under the import paths the reference's scripts use."""
 from .ppo2 import PPO2  # noqa: E402,F401
+from .trpo import TRPO  # noqa: E402,F401

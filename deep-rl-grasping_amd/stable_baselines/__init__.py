@@ -1,11 +1,13 @@
 """Import-path alias: lets the reference's scripts (``import stable_baselines as sb`` in
 train_stable_baselines.py:7, sb_helper.py:6, base_callbacks.py:11-14) run unmodified on top of the
 MI355X engine.  Put ``deep-rl-grasping_amd/`` on PYTHONPATH *instead of* installing stable-baselines
-(see INTEGRATION.md).  The SAC / DQN / BDQ / PPO2 update paths are implemented; the other algorithms
-the reference can also select (TRPO / DDPG, sb_helper.py:130-173) are out of scope and say so."""
+(see INTEGRATION.md).  The SAC / DQN / BDQ / PPO2 / TRPO update paths are implemented.  DDPG, the fifth algorithm the
+reference's SBPolicy names (sb_helper.py:166-173), cannot run in the reference either -- its policy `ddpgMlp` is never defined --
+so it stays out of scope and says so, as do the algorithms the reference never selects."""
 from grasp_rl.sb import logger  # noqa: F401
 from grasp_rl.sb.ppo2 import PPO2  # noqa: F401
 from grasp_rl.sb.sac import SAC  # noqa: F401
+from grasp_rl.sb.trpo import TRPO  # noqa: F401
 
 __version__ = "2.10.1+grasp_rl"
 
@@ -13,7 +15,7 @@ __version__ = "2.10.1+grasp_rl"
 def _unsupported(name):
     class _Unsupported:
         def __init__(self, *a, **k):
-            raise NotImplementedError("%s is outside the accelerated hot path (SAC / DQN / BDQ / PPO2); "
+            raise NotImplementedError("%s is outside the accelerated hot path (SAC / DQN / BDQ / PPO2 / TRPO); "
                                       "install stable-baselines itself to use it" % name)
 
         @classmethod
@@ -23,7 +25,7 @@ def _unsupported(name):
     return _Unsupported
 
 
-TRPO, DDPG, A2C, ACKTR, TD3 = (_unsupported(n) for n in ("TRPO", "DDPG", "A2C", "ACKTR", "TD3"))
+DDPG, A2C, ACKTR, TD3 = (_unsupported(n) for n in ("DDPG", "A2C", "ACKTR", "TD3"))
 try:
     from grasp_rl.sb.dqn import BDQ, DQN  # noqa: F401
 except ImportError:       # pragma: no cover

@@ -59,6 +59,7 @@ extern "C" {
 #define GRL_ALGO_BDQ 2   /* sb.BDQ  sb_helper.py:210-224 */
 #define GRL_ALGO_AE 3    /* depth auto-encoder training: gripperEnv/encoders.py:40-50,70-136, config/encoder.yaml */
 #define GRL_ALGO_PPO 4   /* sb.PPO2 sb_helper.py:137-154; created through grl_ppo_create (grl_ppo_config below) */
+#define GRL_ALGO_TRPO 5  /* sb.TRPO sb_helper.py:129-136; created through grl_trpo_create (grl_trpo_config below) */
 
 typedef struct grl_config {
   int32_t extractor;      /* GRL_EXTRACTOR_*                                                    */
@@ -406,6 +407,51 @@ int grl_ppo_get_metrics(grl_handle h, float* out, int cap);
    "ppo_last_v", "ppo_last_done", "ppo_mean", "ppo_v" (the last minibatch), "ppo_slots" (grl_debug_store only, three values: slots written,
    slots closed, finished -- says how far a rollout placed through the other names has got), "grads", "adam_m", "adam_v".  Every other entry point returns
    GRL_ERR_STATE on a PPO handle before anything moves. */
+
+/* ---------------------------------------------------------------------------------------------------------------------
+   TRPO (GRL_ALGO_TRPO): stable-baselines 2.10.1 TRPO with the actor-critic MlpPolicy on a Box action space, as
+   sb_helper.py:129-136 builds it: ONE environment, a rollout of n_steps = timesteps_per_batch rows, one natural-gradient policy
+   step (conjugate gradient on the Fisher-vector product over every fvp_stride-th row, backtracking line search) and the Adam fit
+   of the value tower per rollout.  The handle is described by a grl_config AND a grl_trpo_config.  The grl_config is read as on
+   a PPO handle with lr = vf_stepsize, act_batch = 1, batch_size = vf_batch and replay_capacity = n_steps; parameters and their
+   order are those of a PPO handle.  The policy variables are those whose name contains "/pi"; every other trainable variable
+   belongs to the value fit.
+   Rollout: grl_ppo_step / grl_ppo_rewards / grl_ppo_finish work on a TRPO handle with n_envs = 1 (done = episode_start of the
+   step; grl_ppo_finish forms V(last obs), GAE and tdlamret).  grl_ppo_train / grl_ppo_get_metrics are GRL_ERR_STATE. */
+typedef struct grl_trpo_config {
+  int32_t n_steps;                         /* T = timesteps_per_batch, 1 .. 65536 */
+  int32_t n_vf_layers; int32_t vf_layers[GRL_MAX_LAYERS];
+  int32_t cg_iters;                        /* 1 .. 64 */
+  int32_t ls_steps;                        /* line-search trials 2^-0 .. 2^-(ls_steps - 1): 1 .. 16 (stable-baselines: 10) */
+  int32_t fvp_stride;                      /* the Fisher rows are 0, fvp_stride, 2 fvp_stride, ... (stable-baselines: 5) */
+  int32_t vf_batch;                        /* rows of a value minibatch (stable-baselines: 128); must equal grl_config.batch_size */
+  float lam, max_kl, cg_damping, ent_coef;
+  float adam_eps;                          /* 1e-8 */
+} grl_trpo_config;
+int grl_trpo_query_sizes(const grl_config* cfg, const grl_trpo_config* trpo, grl_sizes* out);
+int grl_trpo_create(const grl_config* cfg, const grl_trpo_config* trpo, const grl_buffers* bufs, grl_handle* out);
+/* One learn iteration behind a finished rollout (GRL_ERR_STATE otherwise; empties it): advantage standardisation, losses and
+   gradient at the old parameters, cg_iters Fisher products, the closing product for shs, ls_steps trials, restore, then
+   vf_iters * floor(T / vf_batch) Adam minibatches of the value tower.  vf_perm: host int32 [vf_iters, T], each row a permutation
+   of 0..T-1 (checked as grl_ppo_train checks; row e's minibatch k takes its entries [k vf_batch, (k + 1) vf_batch), the tail is
+   dropped); 0 <= vf_iters <= GRL_PPO_MAX_EPOCHS (0: vf_perm may be NULL).  The launch list has a fixed shape -- a launch whose
+   device flag says "CG finished" / "trial accepted" returns at once.  Stream-ordered, no synchronisation. */
+int grl_trpo_update(grl_handle h, const int32_t* vf_perm, int vf_iters);
+/* host, synchronises: GRL_TRPO_METRICS floats of the last grl_trpo_update: [0..4] optimgain, meankl, entbonus, surrgain, meanent
+   before the step; [5] accepted line-search index (-1: parameters restored, -2: zero gradient, no step); [6], [7] optimgain and
+   meankl of the accepted trial (0 without one); [8] conjugate-gradient iterations run; [9] the final r.r; [10] shs. */
+#define GRL_TRPO_METRICS 11
+int grl_trpo_get_metrics(grl_handle h, float* out, int cap);
+/* parity: F(v) of the vector stored under "trpo_fvp_in" at the current parameters over the Fisher rows of the rollout on the
+   device, left under "trpo_fvp_out"; needs a full rollout (slots closed).  The entries of the value variables in the stored
+   vector must be zero (they are in every vector an update forms).  Stream-ordered. */
+int grl_trpo_debug_fvp(grl_handle h);
+/* grl_act, grl_param_*, grl_reset_optimizer, grl_set_learning_rate, grl_set_stream, grl_profile_* and grl_debug_fetch / _store
+   work as on a PPO handle.  Debug names: those of the PPO rollout, and -- laid out like the gradient bucket ([n_trainable], the
+   entries of the value variables 0) -- "trpo_g", "trpo_stepdir", "trpo_fullstep", "trpo_fvp_in", "trpo_fvp_out",
+   "trpo_theta_old" (every trainable variable as it was when the update began); "trpo_atarg" [T]; "trpo_mean_old" [T, A] (the
+   old policy's means).  Every other entry point returns
+   GRL_ERR_STATE on a TRPO handle before anything moves. */
 
 /* debugging / parity: copy a named internal activation of the last update to the host.
    Names: "x_obs","x_next","feat_pi","feat_vf","feat_tgt","mu","log_std","pi","logp","qf1","qf2",
