@@ -135,7 +135,8 @@ struct PpoPlanner {
   // (towers: bit 0 pi, bit 1 vf -- plan_trpo.inl runs them apart)
   void forward(std::vector<Op>& ops, const float* x, int rows, const PpoActs& a, const char* tag, int towers = 3) {
     const std::string t(tag);
-    auto on = [&](int tw, int l) { return ((towers >> tw) & 1) && l < T[tw].L(); };
+    std::string l0_note;
+    auto on =[&](int tw, int l) { return ((towers >> tw) & 1) && l < T[tw].L(); };
     for (int l = 0; l < std::max(T[0].L(), T[1].L()); ++l) {
       std::vector<IgemmProb> pr;
       std::vector<TanhDesc> td;
@@ -161,9 +162,18 @@ struct PpoPlanner {
             d.parts = parts; d.bias = P + T[tw].b[l]; d.part_stride = p.slab_stride; d.n_parts = p.split;
           }
         }
+        if (l == 0) {      // GRL_PLAN_DUMP: the route of this tower's first layer and of the tanh launch behind it
+          char buf[160];
+          const char* nm = tw == 0 ? "pi" : "vf";
+          if (p.split > 1) snprintf(buf, sizeof(buf), "  %s H %d split %d (part_stride %% 4 = %d, rows * H %% 4 = %d)", nm, N, p.split,
+                                    (int)(p.slab_stride & 3), (int)(((int64_t)rows * N) & 3));
+          else snprintf(buf, sizeof(buf), "  %s H %d whole (rows * H %% 4 = %d)", nm, N, (int)(((int64_t)rows * N) & 3));
+          l0_note += buf;
+        }
         pr.push_back(p);
         td.push_back(d);
       }
+      if (l == 0) plan_note("grl plan: ppo_l0        %s: %d rows;%s\n", tag, rows, l0_note.c_str());
       h.add_launch(ops, t + "_l" + std::to_string(l), 0, pr);
       add_tanh(ops, "ppo_tanh_fwd", false, td, rows);
     }

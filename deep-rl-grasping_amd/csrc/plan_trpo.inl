@@ -70,6 +70,7 @@ struct TrpoPlanner {
     xf = zeroed(wk, (int64_t)NF * ldo);
     nblk_T = trpo_loss_blocks(T);
     nvb = trpo_vec_blocks(n);
+    plan_note("grl plan: trpo vec      %lld entries in %d workgroups (reducing vector launches)\n", (long long)n, nvb);
     lpart = wk.f32((int64_t)nblk_T * 2); dls_T = wk.f32((int64_t)nblk_T * A);
     vpart = wk.f32((int64_t)nvb * 2); vpart2 = wk.f32(nvb);
   }

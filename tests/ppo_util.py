@@ -36,6 +36,132 @@ CASES = {
 }
 
 
+# ---------------------------------------------------------------------------------------------------
+# Shapes ON the edges of what csrc/plan_ppo.inl and csrc/ppo_kernels.h decide by shape alone (tests/test_gpu_ppo_shapes.py on the
+# MI355X, tests/test_hostemu_ppo_shapes.py on the emulation build), the smallest that still cross each edge.  `route` is what the
+# case exists for, written down from the conditions in the sources (restated in planned_route below), never from what the engine
+# prints:
+#   one | list_obs | list_width   the act path: ppo_act_kernel, or the launch list because of the observation / because of a width
+#   whole | split                 the first layer of the towers: one product, or partial sums that tanh_fwd adds (any call, any tower)
+#   quads | scalars               tanh_fwd over partial sums: 16-byte accesses, or none at all (`part_stride & 3`)
+#   straddle                      ... quads with H % 4 != 0: a float4 runs over a row end, the bias index wraps inside it
+#   grid2                         a first-level tanh launch beyond 1024 x 256 quads: the grid-stride loops take a second pass
+# The stride of the partial sums IS rows * H (engine.hip: set_split), so `part_stride % 4 == 0` together with `rows * H % 4 != 0`
+# -- quads AND a scalar tail over partial sums -- cannot be planned: no `wide_tail` case; route_from_dump asserts the two numbers of
+# every dumped line equal, so a stride that stops being rows * H fails here first.  What is no route of the plan sits in the
+# comments: loss blocks of 256 rows, GAE blocks of 64 environments, the 256-lane loops of the rewards and the gather statistics.
+# Every case passes check_update's preconditions at seed 0 except grid_stride (seeds 0 and 1 put a row within 1e-5 of a boundary)
+# and envs_257 (seed 0 passes with a margin of 1.7e-5 only; seed 7 leaves 3.0e-4, the most of seeds 0 ... 9).
+SHAPE_CASES = {
+    # one launch AT the input limit: the staging loop of ppo_act_kernel takes 8 passes
+    "act_in_2048": dict(obs_dim=2048, A=2, n_envs=2, n_steps=4, nmb=1, pi=(8,), vf=(8,), route="one whole"),
+    # one value beyond: launch list, split first layer; 1 x 17, 1 x 9, 7 x 17 and 7 x 9 floats per part: no quads, all scalars
+    "in_2049_odd": dict(obs_dim=2049, A=3, n_envs=1, n_steps=7, nmb=1, pi=(17,), vf=(9, 5), route="list_obs split scalars"),
+    # H % 4 != 0 with rows * H % 4 == 0 (2 x 6, 2 x 10, 6 x 6, 6 x 10): quads that straddle rows
+    "wide_quads": dict(obs_dim=2052, A=2, n_envs=2, n_steps=3, nmb=1, pi=(6,), vf=(10,), route="list_obs split quads straddle"),
+    # (added) ... and with H odd, rows a multiple of 4 (4 x 5, 4 x 7, 8 x 5, 8 x 7).  A quad starts at a multiple of 4, so with H even
+    # only its third and fourth component ever cross a row end; with H = 5 and 7 each of the last three does
+    "wide_quads_odd": dict(obs_dim=2052, A=2, n_envs=4, n_steps=2, nmb=1, pi=(5,), vf=(7,), route="list_obs split quads straddle"),
+    # one launch AT the width limit: Np = 256, S = 1 (256, 255), Np = 256 over 129 live outputs; staging loop 2 passes
+    "width_256": dict(obs_dim=300, A=2, n_envs=2, n_steps=5, nmb=1, pi=(256,), vf=(255, 129), route="one whole"),
+    "width_257": dict(obs_dim=300, A=2, n_envs=2, n_steps=5, nmb=1, pi=(257,), vf=(8,), route="list_width whole"),
+    # GRL_MAX_LAYERS: the hs[l & 1] ping-pong goes round twice; towers of depth 4 and 1
+    "depth_4_1": dict(obs_dim=9, A=2, n_envs=2, n_steps=9, nmb=2, pi=(8, 7, 6, 5), vf=(3,), route="one whole"),
+    # PPO_MAX_A: the closing sum of the loss crosses a wave, ws[..] to its last column, the gather's t == 64 lane, the sample tail
+    "A_64": dict(obs_dim=10, A=64, n_envs=2, n_steps=10, nmb=2, pi=(16,), vf=(16,), route="one whole"),
+    "envs_65": dict(obs_dim=6, A=2, n_envs=65, n_steps=2, nmb=1, pi=(8,), vf=(8,), route="one whole"),       # two GAE workgroups
+    # rewards loop second pass, n_steps = 1 (every step is the `end` step), 257 rows: a loss block with ONE live row, the gather's
+    # statistics in two passes
+    "envs_257": dict(obs_dim=6, A=2, n_envs=257, n_steps=1, nmb=1, pi=(8,), vf=(8,), route="one whole", seed=7),
+    "mb_256": dict(obs_dim=6, A=2, n_envs=4, n_steps=128, nmb=2, pi=(8,), vf=(8,), route="one whole"),       # exactly one full loss block
+    "mb_512": dict(obs_dim=6, A=2, n_envs=4, n_steps=128, nmb=1, pi=(8,), vf=(8,), route="one whole"),       # exactly two
+    # 4100 x 257 floats: 263 425 quads against 1024 x 256, so tanh_fwd / tanh_bwd take a second pass (and a scalar tail of one)
+    "grid_stride": dict(obs_dim=4, A=2, n_envs=1, n_steps=4100, nmb=1, pi=(257,), vf=(4,), route="list_width whole grid2", seed=2),
+}
+ACT_SHAPE_CASES = ("act_in_2048", "in_2049_odd", "wide_quads_odd", "width_256", "width_257", "depth_4_1", "A_64", "envs_65", "envs_257")
+ONE_LAUNCH_VS_LIST = ("act_in_2048", "width_256", "A_64")
+
+
+def case_args(name):
+    a = dict(CASES[name] if name in CASES else SHAPE_CASES[name])
+    a.pop("route", None)
+    return a
+
+
+def declared_route(name, table=None):
+    return frozenset((SHAPE_CASES if table is None else table)[name]["route"].split())
+
+
+def first_layer_calls(a):
+    """(rows, widths of the first layers planned together) of every PpoPlanner::forward call of a PPO2 handle."""
+    both = (a["pi"][0], a["vf"][0])
+    one_launch = a["obs_dim"] <= 2048 and max(tuple(a["pi"]) + tuple(a["vf"])) <= 256      # (no forward call on the act path then)
+    return ([] if one_launch else [(a["n_envs"], both)]) + [(a["n_envs"] * a["n_steps"] // a["nmb"], both)]
+
+
+def planned_route(obs_dim, widths, calls):
+    """The conditions of csrc/plan_ppo.inl (routes, forward), engine.hip (set_split), csrc/ppo_kernels.h (tanh_fwd_kernel) and
+    csrc/ppo.hip (tanh_grid) with no GRL_TUNE switch set, restated: PPO_ACT_MAX_IN 2048, PPO_ACT_MAX_HID 256, a reduction cut until
+    the launch has 64 tiles of 64 x 64 in chunks of whole 32-value steps, 1024 workgroups of 256 quads."""
+    r = set()
+    r.add("list_obs" if obs_dim > 2048 else ("list_width" if max(widths) > 256 else "one"))
+    cdiv = lambda x, y: (x + y - 1) // y
+    for rows, hs in calls:
+        for H in hs:
+            split = 1
+            if obs_dim > 2048:
+                base = len(hs) * cdiv(rows, 64) * cdiv(H, 64)
+                steps = cdiv(obs_dim, 32)
+                per = cdiv(steps, max(1, min(cdiv(64, base), steps)))
+                split = cdiv(obs_dim, per * 32)
+            r.add("split" if split > 1 else "whole")
+            if split > 1:
+                part_stride = rows * H
+                r.add("scalars" if part_stride % 4 else "quads")
+                if part_stride % 4 == 0 and H % 4:
+                    r.add("straddle")
+        if cdiv(rows * max(hs), 4) > 1024 * 256:
+            r.add("grid2")
+    return frozenset(r)
+
+
+def route_from_dump(plan):
+    """The route a GRL_PLAN_DUMP=1 text of a PPO2 / TRPO handle reports (lines `grl plan: ppo_act` and `grl plan: ppo_l0`)."""
+    import re
+    act = sorted(set(l for l in plan.splitlines() if l.startswith("grl plan: ppo_act ")))      # (sizing and creation both plan)
+    assert len(act) == 1, plan
+    r = set()
+    if "one launch per call" in act[0]:
+        r.add("one")
+    else:
+        assert "launch list (" in act[0], act
+        r.add("list_obs" if "observation beyond 2048 values" in act[0] else "list_width")
+        assert ("observation beyond 2048 values" in act[0]) != ("a width beyond 256" in act[0]), act
+    l0 = [l for l in plan.splitlines() if l.startswith("grl plan: ppo_l0 ")]
+    assert l0, plan
+    for line in l0:
+        rows = int(re.search(r": (\d+) rows;", line).group(1))
+        towers = re.findall(r"(pi|vf) H (\d+) (whole|split \d+) \(([^)]*)\)", line)
+        assert towers, line
+        for _, H, how, detail in towers:
+            H = int(H)
+            tail = int(re.search(r"rows \* H % 4 = (\d)", detail).group(1))
+            assert tail == rows * H % 4, line
+            if how == "whole":
+                r.add("whole")
+                continue
+            assert int(how.split()[1]) > 1, line
+            stride4 = int(re.search(r"part_stride % 4 = (\d)", detail).group(1))
+            assert stride4 == tail, "the stride of the partial sums is no longer rows * H: " + line
+            r.add("split")
+            r.add("scalars" if stride4 else "quads")
+            if not stride4 and H % 4:
+                r.add("straddle")
+        if (rows * max(int(t[1]) for t in towers) + 3) // 4 > 1024 * 256:
+            r.add("grid2")
+    return frozenset(r)
+
+
 def tower_shapes(case):
     return tuple(case["pi"]), tuple(case["vf"])
 
@@ -202,9 +328,11 @@ class Ref:
 
 
 # ------------------------------------------------------------------------------------------------- seeded cases
-def make_case(name, seed=0, noptepochs=2, lr=2.5e-4, **over):
-    c = dict(CASES[name])
+def make_case(name, seed=None, noptepochs=2, lr=2.5e-4, **over):
+    """seed None: the seed the table fixes for the case (0 where it names none)"""
+    c = case_args(name)
     c.update(over)
+    seed = c.get("seed", 0) if seed is None else seed
     c.update(name=name, seed=seed, noptepochs=noptepochs, lr=lr)
     pi, vf = tower_shapes(c)
     rng = np.random.default_rng(1000 + seed)
@@ -306,7 +434,8 @@ def check_step_and_gae(eng, c):
         close_fwd(a, a64, "action"); close_fwd(v, v64, "value"); close_fwd(p, p64, "neglogp")
         acts[:, t], vals[:, t], nlps[:, t] = a, v, p
         if t == 0:
-            with pytest.raises(_capi.GrlError, match="still open"):
+            # (n_steps = 1: the only slot is open AND the rollout holds every step it can; grl_ppo_step names the latter first)
+            with pytest.raises(_capi.GrlError, match="still open" if T > 1 else "rollout is full"):
                 eng.step(c["obs"][:, t], c["done"][:, t], c["eps"][:, t])
         eng.rewards(c["rew"][:, t])
     with pytest.raises(_capi.GrlError, match="rollout is full"):
@@ -354,3 +483,75 @@ def check_update(eng, c):
     P = eng.get_parameters()
     for n in ("model/q/w:0", "model/q/b:0"):
         assert np.array_equal(P[n], c["P"][n]), n
+
+
+def check_act_routes_agree(c, make):
+    """GRL_TUNE ppo_act=0 forces the launch list on a shape ppo_act_kernel takes: every step of the rollout gives the same
+    actions, values and neglogps on both routes (the comparison test_launch_list_and_one_launch_act_agree makes at default_64_64).
+    `make(c)` builds a handle; returns the plan dumps of the two handles when GRL_PLAN_DUMP is set."""
+    import os
+    outs = []
+    for tune in (None, "ppo_act=0"):
+        if tune:
+            os.environ["GRL_TUNE"] = tune
+        try:
+            eng = make(c)
+        finally:
+            os.environ.pop("GRL_TUNE", None)
+        steps = []
+        for t in range(c["n_steps"]):
+            steps.append(eng.step(c["obs"][:, t], c["done"][:, t], c["eps"][:, t]))
+            eng.rewards(c["rew"][:, t])
+        outs.append(steps)
+        eng.close()
+    for one, lst in zip(*outs):
+        for a, b in zip(one, lst):
+            assert np.allclose(a, b, rtol=1e-5, atol=1e-6), np.abs(a - b).max()
+
+
+# ------------------------------------------------------------------------------------------------- device draws
+DRAW_ENVS, DRAW_A, DRAW_CALLS = 257, 63, 16
+
+
+def check_device_draws(make):
+    """grl_act(deterministic=False, eps=NULL) draws its noise on the device (normal_pair_draw: Philox + Box-Muller, one pair per
+    two action components, one counter per call).  257 rows x 63 components (odd: the last pair is half used) x 16 calls give
+    N = 259 056 values z = (a - mean) / exp(logstd), held to what independent standard normals give: every bound is k = 6 standard
+    errors of its statistic -- mean 1/sqrt(N), variance sqrt(2/N), excess kurtosis sqrt(24/N), a correlation coefficient over n pairs
+    1/sqrt(n), which is at least 1/sqrt(N).  The output layer and logstd of the handle are zero, so a IS the draw, bit for bit, and
+    ties are counted on the draws themselves: float32 normals do tie now and then (a NumPy float32 standard-normal array of the same
+    size shows how often), the count is Poisson-like, and the bound is NumPy's count + 6 sqrt(count).  A pair reused across rows,
+    calls or components gives thousands."""
+    n, A, calls = DRAW_ENVS, DRAW_A, DRAW_CALLS
+    c = dict(obs_dim=5, A=A, n_envs=n, n_steps=1, nmb=1, pi=(4,), vf=(4,), name="draws", seed=11, noptepochs=1, lr=2.5e-4)
+    P = init_params(c["obs_dim"], A, c["pi"], c["vf"], c["seed"])
+    for name in ("model/pi/w:0", "model/pi/b:0", "model/pi/logstd:0"):
+        P[name] = np.zeros_like(P[name])
+    c["P"] = P
+    eng = make(c)
+    obs = np.random.default_rng(5).normal(0.0, 1.0, (n, c["obs_dim"])).astype(np.float32)
+    mean = eng.act(obs)
+    assert not mean.any()
+    a = np.stack([eng.act(obs, deterministic=False) for _ in range(calls)])
+    eng.close()
+    assert np.isfinite(a).all()
+    z = (a.astype(np.float64) - mean) / np.exp(P["model/pi/logstd:0"][0].astype(np.float64))
+    N = z.size
+    assert N == 259056
+    k = 6.0
+    m, var = z.mean(), z.var()
+    kurt = ((z - m) ** 4).mean() / var ** 2 - 3.0
+    corr = lambda x, y: float(np.corrcoef(x.reshape(-1), y.reshape(-1))[0, 1])
+    r_comp = corr(z[:, :, 0:A - 1:2], z[:, :, 1:A:2])      # the two halves of a pair
+    r_rows = corr(z[:, :-1], z[:, 1:])
+    r_call = corr(z[:-1], z[1:])
+    ties = sum(row.size - np.unique(row).size for row in a.reshape(calls, -1))
+    ties_np = sum(row.size - np.unique(row).size for row in np.random.default_rng(0).standard_normal((calls, n * A), dtype=np.float32))
+    print("draws: mean %.3e var-1 %.3e kurtosis %.3e corr pair %.3e rows %.3e calls %.3e ties %d (NumPy %d)"
+          % (m, var - 1.0, kurt, r_comp, r_rows, r_call, ties, ties_np))
+    assert abs(m) <= k / np.sqrt(N)
+    assert abs(var - 1.0) <= k * np.sqrt(2.0 / N)
+    assert abs(kurt) <= k * np.sqrt(24.0 / N)
+    for r in (r_comp, r_rows, r_call):
+        assert abs(r) <= k / np.sqrt(N)
+    assert ties <= ties_np + k * np.sqrt(max(ties_np, 1))
