@@ -1552,6 +1552,128 @@ int grl_profile_dump(grl_handle h, char* buf, int cap) {
   return GRL_OK;
 }
 
+// ---- behaviour-cloning pretraining (plan_bc.inl): a session on a SAC handle, in a buffer of the caller's
+#define SAC_ONLY(h, what)                                                                                        \
+  do {                                                                                                           \
+    if (!(h)) return fail(GRL_ERR_INVALID, "null handle");                                                       \
+    if ((h)->cfg.algo != GRL_ALGO_SAC) return fail(GRL_ERR_STATE, what " is defined for SAC handles (grl_create)"); \
+  } while (0)
+
+static int check_bc(grl_handle h, const grl_bc_config* c) {
+  if (!c || !c->act_low || !c->act_high) return fail(GRL_ERR_INVALID, "null behaviour-cloning config or action bounds");
+  if (c->batch < 1) return fail(GRL_ERR_INVALID, "bc: batch must be >= 1");
+  if (c->batch > h->cfg.batch_size)
+    return fail(GRL_ERR_INVALID, "bc: batch " + std::to_string(c->batch) + " exceeds the handle's batch_size " + std::to_string(h->cfg.batch_size));
+  if (!(c->lr > 0.f) || !(c->adam_eps > 0.f)) return fail(GRL_ERR_INVALID, "bc: lr and adam_eps must be > 0");
+  for (int j = 0; j < h->cfg.act_dim; ++j)
+    if (!(c->act_high[j] > c->act_low[j]) || !std::isfinite(c->act_high[j]) || !std::isfinite(c->act_low[j]))
+      return fail(GRL_ERR_INVALID, "bc: the action bounds must be finite with high > low (dimension " + std::to_string(j) + ")");
+  return GRL_OK;
+}
+
+static void bc_fill(grl_handle h, const grl_bc_config* c, BcPlan& p) {
+  p.cfg = *c;
+  p.low.assign(c->act_low, c->act_low + h->cfg.act_dim);
+  p.high.assign(c->act_high, c->act_high + h->cfg.act_dim);
+  p.cfg.act_low = p.cfg.act_high = nullptr;
+}
+
+int grl_bc_query_sizes(grl_handle h, const grl_bc_config* c, size_t* bytes) {
+  SAC_ONLY(h, "grl_bc_query_sizes");
+  if (!bytes) return fail(GRL_ERR_INVALID, "null out");
+  if (int e = check_bc(h, c)) return e;
+  BcPlan p;
+  bc_fill(h, c, p);
+  if (int e = h->plan_bc(p)) return e;
+  for (auto* l : p.launches) delete l;
+  *bytes = p.a.off + 256;
+  return GRL_OK;
+}
+
+int grl_bc_begin(grl_handle h, const grl_bc_config* c, void* buf) {
+  SAC_ONLY(h, "grl_bc_begin");
+  if (!buf) return fail(GRL_ERR_INVALID, "null buffer");
+  if (h->bc) return fail(GRL_ERR_STATE, "a behaviour-cloning session is open on this handle (grl_bc_end)");
+  if (int e = check_bc(h, c)) return e;
+  BcPlan* p = new BcPlan();
+  bc_fill(h, c, *p);
+  p->a.base = (char*)buf;
+  h->bc = p;
+  if (int e = h->plan_bc(*p)) { h->uploads.clear(); h->bc_drop(); return e; }
+  // the whole buffer zero (moments, row padding, untouched pixels), then the tables and the optimiser's words
+  hipError_t e = hipMemsetAsync(buf, 0, p->a.off, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  for (auto& u : h->uploads)
+    if (e == hipSuccess) e = hipMemcpy(u.dst, u.bytes.data(), u.bytes.size(), hipMemcpyHostToDevice);
+  h->uploads.clear();
+  BcDev d0;
+  memset(&d0, 0, sizeof(d0));
+  d0.beta1_power = 0.9f; d0.beta2_power = 0.999f; d0.lr = c->lr;
+  if (e == hipSuccess) e = hipMemcpy(p->dev, &d0, sizeof(d0), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { h->bc_drop(); return fail(GRL_ERR_HIP, std::string("bc begin: ") + hipGetErrorString(e)); }
+  return GRL_OK;
+}
+
+// a call's index rows on the host: every entry in [-1, n_rows), -1 only as a tail, at least one row present
+static int bc_check_idx(grl_handle h, const int32_t* idx, int64_t n_rows, int n) {
+  BcPlan& p = *h->bc;
+  const int batch = p.cfg.batch;
+  p.idx_host.resize((size_t)n * batch);
+  HIPCHK(hipMemcpyAsync(p.idx_host.data(), idx, p.idx_host.size() * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int u = 0; u < n; ++u) {
+    const int32_t* row = p.idx_host.data() + (size_t)u * batch;
+    bool tail = false;
+    for (int b = 0; b < batch; ++b) {
+      const std::string where = "bc: index row " + std::to_string(u) + ", entry " + std::to_string(b);
+      if (row[b] < -1 || row[b] >= n_rows) return fail(GRL_ERR_INVALID, where + " is outside the table (" + std::to_string(row[b]) + ")");
+      if (row[b] == -1) { if (b == 0) return fail(GRL_ERR_INVALID, where + ": a minibatch needs at least one row"); tail = true; }
+      else if (tail) return fail(GRL_ERR_INVALID, where + " follows a -1: absent rows must be trailing");
+    }
+  }
+  return GRL_OK;
+}
+
+static int bc_run(grl_handle h, const char* what, const float* obs, const float* act, int64_t n_rows, const int32_t* idx, int n, bool train) {
+  if (!h->bc) return fail(GRL_ERR_STATE, std::string(what) + " needs an open session (grl_bc_begin)");
+  if (!obs || !act || !idx || n_rows < 1) return fail(GRL_ERR_INVALID, "bc: null table or indices");
+  if (n < 1 || n > GRL_BC_MAX_UPDATES) return fail(GRL_ERR_INVALID, "bc: the count of a call must be 1..65536");
+  if (int e = bc_check_idx(h, idx, n_rows, n)) return e;
+  BcPlan& p = *h->bc;
+  hipLaunchKernelGGL(bc_open_kernel, dim3(1), dim3(1), 0, h->stream, p.dev, obs, act, idx);
+  if (int e = h->run_repeated(train ? "bc_train" : "bc_eval", {train ? &p.ops_train : &p.ops_eval}, n)) return e;
+  HIPCHK(hipGetLastError());
+  p.last_n = n;
+  return GRL_OK;
+}
+
+int grl_bc_train(grl_handle h, const float* obs, const float* act, int64_t n_rows, const int32_t* idx, int n_updates) {
+  SAC_ONLY(h, "grl_bc_train");
+  return bc_run(h, "grl_bc_train", obs, act, n_rows, idx, n_updates, true);
+}
+
+int grl_bc_eval(grl_handle h, const float* obs, const float* act, int64_t n_rows, const int32_t* idx, int n_batches) {
+  SAC_ONLY(h, "grl_bc_eval");
+  return bc_run(h, "grl_bc_eval", obs, act, n_rows, idx, n_batches, false);
+}
+
+int grl_bc_get_losses(grl_handle h, float* out, int cap) {
+  SAC_ONLY(h, "grl_bc_get_losses");
+  if (!h->bc) return fail(GRL_ERR_STATE, "grl_bc_get_losses needs an open session (grl_bc_begin)");
+  if (!out || cap < h->bc->last_n) return fail(GRL_ERR_INVALID, "bc: loss buffer too small");
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (h->bc->last_n) HIPCHK(hipMemcpy(out, h->bc->losses, (size_t)h->bc->last_n * 4, hipMemcpyDeviceToHost));
+  return h->bc->last_n;
+}
+
+int grl_bc_end(grl_handle h) {
+  SAC_ONLY(h, "grl_bc_end");
+  if (!h->bc) return fail(GRL_ERR_STATE, "grl_bc_end needs an open session (grl_bc_begin)");
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->bc_drop();
+  return GRL_OK;
+}
+
 #include "checkpoint.inl"
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 //   plan_sac.inl (SAC update, act, encoder forward)   plan_q.inl (DQN / BDQ, prioritised replay)
 //   plan_ae.inl  (auto-encoder training)              plan_ppo.inl (PPO2: rollout, GAE, clipped update)
 //   plan_trpo.inl (TRPO: CG natural-gradient step, line search, value fit -- over plan_ppo.inl's policy and rollout)
+//   plan_bc.inl  (behaviour-cloning pretraining of a SAC handle's policy, built at grl_bc_begin)
 //   capi.inl     (extern "C" entry points)
 // The element-wise, replay, prioritised-sampling and exchange kernels are compiled here; the GEMM and head kernels in
 // gemm_fwd.hip / gemm_bwd.hip / gemm_wgrad.hip / heads.hip behind the launchers of launch.h.
@@ -50,6 +51,7 @@
 #include "ppo_kernels.h"
 #define GRL_TRPO_TYPES_ONLY         // (the TRPO kernels in trpo.hip)
 #include "trpo_kernels.h"
+#include "bc_kernels.h"
 
 namespace grl {
 
@@ -327,6 +329,7 @@ struct HeadGrad {
   float* g[GRL_MAX_LAYERS];
   int ld0 = 0;   // row stride of g[0] (fused heads: the critics' g[0] are column blocks of one buffer)
 };
+struct BcPlan;   // an open behaviour-cloning session (plan_bc.inl)
 
 }  // namespace grl
 
@@ -478,6 +481,7 @@ struct grl_ctx {
   std::map<std::string, std::pair<const float*, int64_t>> dbg;
 
   ~grl_ctx() {
+    bc_drop();
     if (pin_in) hipHostFree(pin_in);
     if (pin_out) hipHostFree(pin_out);
     if (act_io_host) hipHostFree(act_io_host);
@@ -1524,6 +1528,10 @@ struct grl_ctx {
   grl_trpo_config tcfg = {};
   TrpoDev* trpo_dev = nullptr;
   std::vector<Op> ops_trpo_policy, ops_trpo_vf, ops_trpo_fvp;
+  // behaviour-cloning pretraining of a SAC handle (plan_bc.inl): the open session, built at grl_bc_begin into the caller's buffer
+  BcPlan* bc = nullptr;
+  int plan_bc(BcPlan& p);
+  void bc_drop();
   int plan_ae_general(const AeNet& net);   // ... of any supported network but the shipped one (GRL_TUNE ae_general=1: that one too)
   int enc_dim = 100;   // floats per image grl_encode returns (auto-encoder handles: their encoding_dim)
   float* ae_x = nullptr;            // [B, 4096] minibatch of depth images (staged per step)
@@ -1574,6 +1582,7 @@ int grl_ctx::plan() {
 #include "plan_ae.inl"
 #include "plan_ppo.inl"
 #include "plan_trpo.inl"
+#include "plan_bc.inl"
 
 int grl_ctx::run_ops(std::vector<Op>& ops) {
   if (!prof) {

@@ -59,6 +59,15 @@ class GrlTrpoConfig(C.Structure):
 TRPO_METRICS = 11        # GRL_TRPO_METRICS
 
 
+class GrlBcConfig(C.Structure):
+    """include/grl.h: grl_bc_config -- a behaviour-cloning session on a SAC handle."""
+    _fields_ = [("batch", C.c_int32), ("lr", C.c_float), ("adam_eps", C.c_float),
+                ("act_low", C.c_void_p), ("act_high", C.c_void_p)]
+
+
+BC_MAX_UPDATES = 65536   # GRL_BC_MAX_UPDATES
+
+
 class GrlSizes(C.Structure):
     _fields_ = [("state_bytes", C.c_size_t), ("grads_bytes", C.c_size_t), ("work_bytes", C.c_size_t),
                 ("replay_bytes", C.c_size_t), ("n_params", C.c_int64), ("n_trainable", C.c_int64)]
@@ -89,6 +98,7 @@ EXPORTS = [
     "grl_ppo_query_sizes", "grl_ppo_create", "grl_ppo_step", "grl_ppo_rewards", "grl_ppo_finish", "grl_ppo_train",
     "grl_ppo_get_metrics",
     "grl_trpo_query_sizes", "grl_trpo_create", "grl_trpo_update", "grl_trpo_get_metrics", "grl_trpo_debug_fvp",
+    "grl_bc_query_sizes", "grl_bc_begin", "grl_bc_train", "grl_bc_eval", "grl_bc_get_losses", "grl_bc_end",
 ]
 
 
@@ -189,6 +199,12 @@ def load_library(path=None):
     lib.grl_trpo_update.argtypes = [vp, vp, i32]
     lib.grl_trpo_get_metrics.argtypes = [vp, f32p, i32]
     lib.grl_trpo_debug_fvp.argtypes = [vp]
+    lib.grl_bc_query_sizes.argtypes = [vp, C.POINTER(GrlBcConfig), C.POINTER(C.c_size_t)]
+    lib.grl_bc_begin.argtypes = [vp, C.POINTER(GrlBcConfig), vp]
+    lib.grl_bc_train.argtypes = [vp, f32p, f32p, i64, vp, i32]
+    lib.grl_bc_eval.argtypes = [vp, f32p, f32p, i64, vp, i32]
+    lib.grl_bc_get_losses.argtypes = [vp, f32p, i32]
+    lib.grl_bc_end.argtypes = [vp]
     return lib
 
 

@@ -626,6 +626,53 @@ class SacEngine:
     def synchronize(self):
         self.be.synchronize()
 
+    # ------------------------------------------------------------------ behaviour cloning (grl_bc_*, csrc/plan_bc.inl)
+    def bc_begin(self, batch, learning_rate, adam_epsilon, act_low, act_high):
+        """Opens a pretraining session at `batch` rows per minibatch (<= the engine's batch_size): fresh Adam moments and
+        beta powers, its own buffer.  act_low / act_high: the action space's bounds."""
+        low = np.ascontiguousarray(act_low, dtype=np.float32).reshape(self.A)
+        high = np.ascontiguousarray(act_high, dtype=np.float32).reshape(self.A)
+        c = _capi.GrlBcConfig(int(batch), float(learning_rate), float(adam_epsilon), low.ctypes.data, high.ctypes.data)
+        nbytes = C.c_size_t()
+        check(self.lib, self.lib.grl_bc_query_sizes(self.h, C.byref(c), C.byref(nbytes)))
+        buf = self.be.alloc_f32(nbytes.value)
+        check(self.lib, self.lib.grl_bc_begin(self.h, C.byref(c), C.c_void_p(self.be.ptr(buf))))
+        self._bc = {"buf": buf, "batch": int(batch), "keep": None}
+
+    def bc_upload(self, obs, act):
+        """(observations, actions) of a dataset as float32 device arrays for bc_train / bc_eval: [n, obs_size], [n, A]."""
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        n = obs.shape[0]
+        act = np.ascontiguousarray(act, dtype=np.float32).reshape(n, self.A)
+        return self.be.to_device(obs.reshape(n, -1)), self.be.to_device(act), n
+
+    def _bc_call(self, fn, table, idx):
+        obs, act, n = table
+        idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1, self._bc["batch"])
+        di = self.be.to_device(idx)
+        p = self.be.ptr
+        check(self.lib, fn(self.h, p(obs), p(act), n, C.c_void_p(p(di)), idx.shape[0]))
+        self._bc["keep"] = (table, di)      # alive until the stream has consumed them
+
+    def bc_train(self, table, idx):
+        """One update per row of idx [n_updates, batch] (int32 rows of the table; a shorter minibatch ends in -1 entries),
+        back to back on the stream.  table: what bc_upload returned."""
+        self._bc_call(self.lib.grl_bc_train, table, idx)
+
+    def bc_eval(self, table, idx):
+        """Forward and loss only over the rows of idx [n_batches, batch]."""
+        self._bc_call(self.lib.grl_bc_eval, table, idx)
+
+    def bc_losses(self):
+        """Per-update / per-batch losses of the last bc_train / bc_eval call (synchronises)."""
+        out = np.empty(_capi.BC_MAX_UPDATES, np.float32)
+        n = check(self.lib, self.lib.grl_bc_get_losses(self.h, out.ctypes.data, out.size))
+        return out[:n].copy()
+
+    def bc_end(self):
+        check(self.lib, self.lib.grl_bc_end(self.h))
+        self._bc = None
+
     # ------------------------------------------------------------------ inference
     def act(self, obs, deterministic=True, eps=None, raw=False, observed=False):
         """raw=True: `obs` are un-normalised observations, VecNormalize is applied on the device (norm_update statistics).

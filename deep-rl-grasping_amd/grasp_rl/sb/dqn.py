@@ -243,6 +243,9 @@ class _QModel(CheckpointMixin):
         acts = np.asarray([self._bins_to_env_action(b) for b in self._act_bins(obs, eps)])
         return (acts[0] if single else acts), None
 
+    def pretrain(self, dataset, n_epochs=10, learning_rate=1e-4, adam_epsilon=1e-8, val_interval=None):
+        raise NotImplementedError("%s: pretrain is not implemented (behaviour cloning runs on SAC models only)" % type(self).__name__)
+
     # ------------------------------------------------------------------ learn
     def learn(self, total_timesteps, callback=None, log_interval=100, tb_log_name=None, reset_num_timesteps=True,
               replay_wrapper=None):

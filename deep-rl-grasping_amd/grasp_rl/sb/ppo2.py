@@ -164,6 +164,9 @@ class PPO2:
         acts = self._clip(acts.reshape((-1,) + tuple(self.action_space.shape)))
         return (acts[0] if single else acts), None
 
+    def pretrain(self, dataset, n_epochs=10, learning_rate=1e-4, adam_epsilon=1e-8, val_interval=None):
+        raise NotImplementedError("%s: pretrain is not implemented (behaviour cloning runs on SAC models only)" % type(self).__name__)
+
     # ------------------------------------------------------------------ learn
     def learn(self, total_timesteps, callback=None, log_interval=1, tb_log_name="PPO2", reset_num_timesteps=True):
         if self.env is None:

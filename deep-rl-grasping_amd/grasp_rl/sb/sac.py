@@ -286,6 +286,60 @@ class SAC(CheckpointMixin):
         act = np.clip(act, self.action_space.low, self.action_space.high)
         return (act[0] if single else act), None
 
+    # ------------------------------------------------------------------ pretrain
+    def pretrain(self, dataset, n_epochs=10, learning_rate=1e-4, adam_epsilon=1e-8, val_interval=None):
+        """stable-baselines ``BaseRLModel.pretrain``: behaviour cloning of ``dataset`` (``stable_baselines.gail.ExpertDataset``)
+        into the policy -- mean squared error between the expert's action and the policy's deterministic action, TF-1 Adam
+        with moments of its own -- on the engine (grl_bc_*).  Only the policy's mean path is trained; the critics, the value
+        and target networks, the entropy coefficient, the SAC optimiser, the replay and ``num_timesteps`` / ``n_updates`` stay
+        as they are.  The dataset is uploaded once, an epoch is one engine call, the validation loss (forward only) is
+        formed every ``val_interval`` epochs (None: every epoch below ten epochs, else every tenth of them).  Observations
+        are used as the dataset holds them: VecNormalize statistics are never applied (``generate_expert_traj`` records what
+        the wrapped environment hands out)."""
+        if self._dp_runtime() is not None:
+            raise NotImplementedError("SAC: pretrain is not implemented under data parallelism (pretrain one process, then "
+                                      "load its parameters into the replicas)")
+        if dataset.batch_size > self.batch_size:
+            raise ValueError("SAC: pretrain needs dataset.batch_size (%d) <= the model's batch_size (%d)"
+                             % (dataset.batch_size, self.batch_size))
+        eng = self.engine
+        obs_size = int(np.prod(self.observation_space.shape))
+        if dataset.observations.shape[1] != obs_size or dataset.actions.shape[1] != eng.A:
+            raise ValueError("SAC: pretrain: the dataset holds observations of %d and actions of %d values, the model takes %d and %d"
+                             % (dataset.observations.shape[1], dataset.actions.shape[1], obs_size, eng.A))
+        if val_interval is None:
+            val_interval = 1 if n_epochs < 10 else int(n_epochs / 10)
+        cap = _capi.BC_MAX_UPDATES
+
+        def run(call, rows, read):      # (an epoch of more than 65536 minibatches takes more than one call)
+            out = []
+            for k in range(0, len(rows), cap):
+                call(table, rows[k:k + cap])
+                if read:
+                    out.append(eng.bc_losses())
+            return float(np.mean(np.concatenate(out))) if read else None
+
+        eng.bc_begin(dataset.batch_size, learning_rate, adam_epsilon, self.action_space.low, self.action_space.high)
+        try:
+            table = eng.bc_upload(dataset.observations, dataset.actions)
+            for epoch in range(int(n_epochs)):
+                # losses are read -- a synchronisation -- only for an epoch whose line is printed
+                due = (epoch + 1) % val_interval == 0
+                show = due and self.verbose > 0
+                train_loss = run(eng.bc_train, dataset.train_loader.index_rows(), show)
+                if due:
+                    val_loss = run(eng.bc_eval, dataset.val_loader.index_rows(), show)
+                if show:
+                    print("==== Training progress {:.2f}% ====".format(100 * (epoch + 1) / n_epochs))
+                    print("Epoch {}".format(epoch + 1))
+                    print("Training loss: {:.6f}, Validation loss: {:.6f}".format(train_loss, val_loss))
+                    print()
+        finally:
+            eng.bc_end()
+        if self.verbose > 0:
+            print("Pretraining done.")
+        return self
+
     # ------------------------------------------------------------------ learn
     def learn(self, total_timesteps, callback=None, log_interval=4, tb_log_name="SAC", reset_num_timesteps=True,
               replay_wrapper=None):

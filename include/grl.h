@@ -453,6 +453,47 @@ int grl_trpo_debug_fvp(grl_handle h);
    old policy's means).  Every other entry point returns
    GRL_ERR_STATE on a TRPO handle before anything moves. */
 
+/* ---- Behaviour-cloning pretraining of a SAC handle's policy from recorded (observation, action) pairs: stable-baselines
+   2.10.1 BaseRLModel.pretrain with SAC._get_pretrain_placeholders.  One update on a minibatch of n present rows:
+     det = tanh(mu(obs));  a_env = low + 0.5 (det + 1)(high - low);  loss = mean over the n * act_dim elements of (a_exp - a_env)^2
+   Trained: model/pi without its log-std head (model/pi/dense_1); with a CNN policy pi's own extractor too.  Everything else --
+   the log-std head, the critics, the value and target networks, log_ent_coef, the SAC optimiser's moments and beta powers,
+   the Philox counters, the replay ring, the running statistics -- stays bit-unchanged.  Observations are used as the table
+   holds them (images divided by 255 as in the SAC update; VecNormalize statistics are never applied).  The optimiser is
+   TF-1 Adam with the session's own zero moments and fresh beta powers.  A session is
+     grl_bc_query_sizes -> (the caller allocates `bytes` of device memory) -> grl_bc_begin -> grl_bc_train / grl_bc_eval ... -> grl_bc_end
+   and holds nothing a checkpoint carries; the handle's own arenas are not touched except for the trained parameters and their
+   entries of the gradient bucket (grl_debug_fetch "grads").  1 <= batch <= grl_config.batch_size (a larger batch is
+   GRL_ERR_INVALID, the message names both numbers).  On a DQN / BDQ / auto-encoder / PPO / TRPO handle every grl_bc_* call is
+   GRL_ERR_STATE before anything moves. */
+typedef struct grl_bc_config {
+  int32_t batch;             /* rows of a minibatch */
+  float lr, adam_eps;
+  const float* act_low;      /* host, [act_dim]: the action space's bounds (high > low in every dimension) */
+  const float* act_high;
+} grl_bc_config;
+/* bytes of the session buffer: moments, scalars, loss slots, the minibatch's activations and gradients at `batch` rows, tables */
+int grl_bc_query_sizes(grl_handle h, const grl_bc_config* c, size_t* bytes);
+/* zeroes the buffer (the optimiser with it), builds the launch plan; synchronises.  GRL_ERR_STATE while a session is open. */
+int grl_bc_begin(grl_handle h, const grl_bc_config* c, void* buf);
+/* n_updates updates, back to back on the handle's stream.  obs [n_rows, obs_size] and act [n_rows, act_dim]: device, float32,
+   env layout and env scale; idx [n_updates, batch]: device, int32, rows of the table -- a minibatch of fewer rows ends in -1
+   entries (at least one row present).  The indices are checked on a host copy first (one synchronisation, in front of the
+   updates): an index outside [-1, n_rows) or a -1 that is not trailing is GRL_ERR_INVALID naming the update and the row, and
+   nothing moves.  1 <= n_updates <= 65536.  GRL_ERR_STATE without a session. */
+int grl_bc_train(grl_handle h, const float* obs, const float* act, int64_t n_rows, const int32_t* idx, int n_updates);
+/* forward and loss only over n_batches index rows; nothing is trained */
+int grl_bc_eval(grl_handle h, const float* obs, const float* act, int64_t n_rows, const int32_t* idx, int n_batches);
+/* host, synchronises: the per-update / per-batch losses of the last grl_bc_train / grl_bc_eval call; returns their number,
+   GRL_ERR_INVALID when cap (in floats) is too small */
+int grl_bc_get_losses(grl_handle h, float* out, int cap);
+/* closes the session (synchronises): the buffer is the caller's again */
+int grl_bc_end(grl_handle h);
+/* Debug names while a session is open (grl_debug_fetch), of the last update / batch: "bc_obs" (the network's input: images
+   [batch, 64, 64, C_img], vectors [batch, rup(obs_dim, 4)]), "bc_feat" [batch, rup(F, 4)], "bc_act" [batch, act_dim] (expert
+   actions as gathered), "bc_mu", "bc_det" [batch, act_dim], "bc_dmu" [batch, rup(act_dim, 4)], "bc_loss" (the loss slots of the
+   call), "bc_adam_m", "bc_adam_v" (moments over the trained range, which starts at parameter offset 0). */
+
 /* debugging / parity: copy a named internal activation of the last update to the host.
    Names: "x_obs","x_next","feat_pi","feat_vf","feat_tgt","mu","log_std","pi","logp","qf1","qf2",
    "v","v_tgt","qf1_pi","qf2_pi","rew","done".  Returns the number of floats written or <0. */
