@@ -12,6 +12,12 @@
     if ((h) && (h)->cfg.algo == GRL_ALGO_TRPO)                                                                                    \
       return fail(GRL_ERR_STATE, what " is not defined on a TRPO handle (TRPO handles: grl_ppo_step / _rewards / _finish, grl_trpo_update, grl_act)"); \
   } while (0)
+// ... except the statistics calls on a PPO / TRPO handle created with normalize = 2 (it keeps VecNormalize's observation
+// statistics: grl_observe, grl_set_obs_stats, grl_set_running_stats, grl_get_obs_stats)
+#define NOT_ON_PPO_WITHOUT_STATS(h, what)                                                                                         \
+  do {                                                                                                                            \
+    if ((h) && !(h)->n_sd) NOT_ON_PPO(h, what);                                                                                   \
+  } while (0)
 
 static int check_cfg(const grl_config* c, bool trpo_call = false) {
   if (!c) return fail(GRL_ERR_INVALID, "null config");
@@ -38,7 +44,11 @@ static int check_cfg(const grl_config* c, bool trpo_call = false) {
     if (c->obs_dim < 1 || c->obs_dim > 64 * 64 * 5) return fail(GRL_ERR_INVALID, "PPO: obs_dim must be 1..20480");
     for (int l = 0; l < c->n_layers; ++l)
       if (c->layers[l] > 1024) return fail(GRL_ERR_INVALID, "PPO: tower widths must be 1..1024");
-    if (c->normalize != 0) return fail(GRL_ERR_INVALID, "PPO: normalize must be 0 (VecNormalize stays on the host)");
+    if (c->normalize == 1 || c->normalize == 3)
+      return fail(GRL_ERR_INVALID, "PPO: normalize " + std::to_string(c->normalize) + " asks for rewards normalised at sample time; a rollout stores the reward "
+                                   "VecNormalize normalised at step time, on the host (normalize must be 0, or 2: observation statistics on the device, grl_observe)");
+    if (c->normalize != 0 && c->normalize != 2) return fail(GRL_ERR_INVALID, "PPO: normalize must be 0 or 2");
+    if (c->normalize == 2 && (!(c->clip_obs > 0.f) || !(c->norm_eps >= 0.f))) return fail(GRL_ERR_INVALID, "PPO: normalize = 2 needs clip_obs > 0 and norm_eps >= 0");
     if (c->act_batch < 1) return fail(GRL_ERR_INVALID, "PPO: act_batch must equal n_envs");
     if (c->q_branches || c->q_bins || c->q_n_common || c->q_n_branch || c->q_n_value || c->q_huber || c->q_double || c->q_grad_clip != 0.f ||
         c->q_trunk_scale != 0.f || c->q_per || c->q_per_alpha != 0.f || c->q_per_eps != 0.f || c->q_per_stratified || c->q_per_alpha64 != 0.0 ||
@@ -169,6 +179,11 @@ static hipError_t per_start(grl_ctx* h) {
   return hipMemcpy(h->per.st, &ps, sizeof(ps), hipMemcpyHostToDevice);
 }
 
+// epsilon of VecNormalize on a PPO / TRPO handle: the Python float when the second configuration block carries it
+static double ppo_norm_eps(const grl_ctx* h) { return h->pcfg.norm_eps64 != 0.0 ? h->pcfg.norm_eps64 : (double)h->cfg.norm_eps; }
+// mean, var (and sqrt(var + eps)) of a PPO / TRPO handle with normalize = 2, taken as given
+static int ppo_load_stats(grl_ctx* h, const double* mean, const double* var);
+
 static int create_handle(const grl_config* cfg, const grl_ppo_config* ppo, const grl_buffers* bufs, grl_handle* out,
                          const grl_trpo_config* trpo = nullptr) {
   if (!bufs || !out || !bufs->state || !bufs->grads || !bufs->work || !bufs->replay)
@@ -203,6 +218,10 @@ static int create_handle(const grl_config* cfg, const grl_ppo_config* ppo, const
     hipMemset(h->n_mean, 0, (size_t)h->n_elems * 8);
     hipMemcpy(h->n_var, ones.data(), ones.size() * 8, hipMemcpyHostToDevice);
     hipMemcpy(h->n_count, c2, 16, hipMemcpyHostToDevice);
+    if (h->n_sd) {      // PPO / TRPO, normalize = 2: sqrt(var + eps) beside them
+      std::vector<double> sd((size_t)h->n_elems, std::sqrt(1.0 + ppo_norm_eps(h)));
+      hipMemcpy(h->n_sd, sd.data(), sd.size() * 8, hipMemcpyHostToDevice);
+    }
   }
   if (h->per_on) {
     e = per_start(h);
@@ -283,8 +302,9 @@ int grl_set_learning_rate(grl_handle h, float lr) {
 }
 
 int grl_set_obs_stats(grl_handle h, const double* mean, const double* var, double ret_var) {
-  NOT_ON_PPO(h, "grl_set_obs_stats");
+  NOT_ON_PPO_WITHOUT_STATS(h, "grl_set_obs_stats");
   if (!h || !mean || !var) return fail(GRL_ERR_INVALID, "null argument");
+  if (h->n_sd) return ppo_load_stats(h, mean, var);      // (ret_var: rewards are normalised on the host)
   const grl_config& c = h->cfg;
   const double eps = c.norm_eps;
   const int nd = h->cnn ? h->F - 512 : 0;
@@ -362,13 +382,27 @@ int grl_set_ret_var(grl_handle h, double ret_var) {
   return GRL_OK;
 }
 
+static int ppo_load_stats(grl_ctx* h, const double* mean, const double* var) {
+  const double eps = ppo_norm_eps(h);
+  std::vector<double> sd((size_t)h->n_elems);
+  for (size_t e = 0; e < sd.size(); ++e) sd[e] = std::sqrt(var[e] + eps);
+  if (int e = copy_from_caller(h, h->n_mean, mean, sd.size() * 8)) return e;
+  if (int e = copy_from_caller(h, h->n_var, var, sd.size() * 8)) return e;
+  // (`sd` is pageable: hipMemcpyAsync has staged it when it returns; a GRL_TUNE host_copy_wait=1 run waits as for the others)
+  return copy_from_caller(h, h->n_sd, sd.data(), sd.size() * 8);
+}
+
 int grl_set_running_stats(grl_handle h, const double* mean, const double* var, double count) {
-  NOT_ON_PPO(h, "grl_set_running_stats");
+  NOT_ON_PPO_WITHOUT_STATS(h, "grl_set_running_stats");
   if (!h || !mean || !var) return fail(GRL_ERR_INVALID, "null argument");
   if (!h->n_mean) return fail(GRL_ERR_STATE, "this handle keeps no running statistics");
   // (rare: once per attach / load; pageable sources are staged before hipMemcpyAsync returns)
-  if (int e = copy_from_caller(h, h->n_mean, mean, (size_t)h->n_elems * 8)) return e;
-  if (int e = copy_from_caller(h, h->n_var, var, (size_t)h->n_elems * 8)) return e;
+  if (h->n_sd) {
+    if (int e = ppo_load_stats(h, mean, var)) return e;
+  } else {
+    if (int e = copy_from_caller(h, h->n_mean, mean, (size_t)h->n_elems * 8)) return e;
+    if (int e = copy_from_caller(h, h->n_var, var, (size_t)h->n_elems * 8)) return e;
+  }
   const double c2[2] = {count, count};
   HIPCHK(hipMemcpyAsync(h->n_count, c2, 16, hipMemcpyHostToDevice, h->stream));
   return GRL_OK;
@@ -418,7 +452,7 @@ int grl_norm_update(grl_handle h, const float* obs, int n) {
 }
 
 int grl_get_obs_stats(grl_handle h, double* mean, double* var, double* count) {
-  NOT_ON_PPO(h, "grl_get_obs_stats");
+  NOT_ON_PPO_WITHOUT_STATS(h, "grl_get_obs_stats");
   if (!h || !mean || !var || !count) return fail(GRL_ERR_INVALID, "null argument");
   if (!h->n_mean) return fail(GRL_ERR_STATE, "this handle keeps no running statistics");
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -531,9 +565,29 @@ static int ob_stage_release(grl_handle h) {
   return GRL_OK;
 }
 
+// PPO / TRPO handles with normalize = 2: one upload of the raw rows and ONE launch per env step (ppo_observe_kernel) -- the
+// statistics move (with the flag) and the normalised rows grl_ppo_step / grl_ppo_finish read with obs == NULL are written
+static int ppo_observe(grl_handle h, const float* obs, int n, int flags) {
+  if (n != h->NA) return fail(GRL_ERR_INVALID, "grl_observe on a PPO / TRPO handle takes the observations of all n_envs = " + std::to_string(h->NA) + " environments, got " + std::to_string(n));
+  if (flags & ~GRL_OBSERVE_UPDATE_STATS) return fail(GRL_ERR_INVALID, "unknown flag bits");
+  if (int e = copy_from_caller(h, h->n_stage, obs, (size_t)n * h->n_elems * 4)) return e;
+  PpoObserveArgs a;
+  memset(&a, 0, sizeof(a));
+  a.nu.obs = h->n_stage; a.nu.n = n; a.nu.elems = (int)h->n_elems;
+  a.nu.mean = h->n_mean; a.nu.var = h->n_var; a.nu.count = h->n_count; a.nu.parity = h->n_parity; a.nu.eps = ppo_norm_eps(h);
+  a.sd = h->n_sd; a.out = h->ppo_obs_n; a.ldo = h->ppo_ldo; a.clip = (double)h->cfg.clip_obs;
+  a.update = (flags & GRL_OBSERVE_UPDATE_STATS) ? 1 : 0;
+  launch_ppo_observe(a, h->stream);
+  if (a.update) h->n_parity ^= 1;
+  HIPCHK(hipGetLastError());
+  h->ppo_observed = true;
+  return GRL_OK;
+}
+
 int grl_observe(grl_handle h, const float* obs, int n, int flags) {
-  NOT_ON_PPO(h, "grl_observe");
+  NOT_ON_PPO_WITHOUT_STATS(h, "grl_observe");
   if (!h || !obs || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
+  if (h->n_sd) return ppo_observe(h, obs, n, flags);
   if (!h->ob_latest) return fail(GRL_ERR_STATE, "this handle keeps no observed observations (SAC / DQN / BDQ handles do)");
   if (n > h->stg_n) return fail(GRL_ERR_INVALID, "more observations than one env step of act_batch environments");
   if (flags & ~GRL_OBSERVE_UPDATE_STATS) return fail(GRL_ERR_INVALID, "unknown flag bits");
@@ -831,11 +885,13 @@ static int ppo_send(grl_handle h, const float* obs, const float* done, const flo
   const size_t n_in = (size_t)NA * (ldo + 1 + A);
   if (int e = pin_reserve(h, (size_t)NA * (ldo + 2 + A), (size_t)NA * (A + 2))) return e;
   // (the previous call synchronised the stream behind its copy: the staging buffer is free)
-  memset(h->pin_in, 0, n_in * 4);
-  for (int r = 0; r < n; ++r) memcpy(h->pin_in + (size_t)r * ldo, obs + (size_t)r * od, (size_t)od * 4);
+  // obs == NULL (grl_ppo_step / grl_ppo_finish on the rows grl_observe normalised): done | eps alone travel
+  const size_t lo = obs ? 0 : (size_t)NA * ldo;
+  memset(h->pin_in + lo, 0, (n_in - lo) * 4);
+  for (int r = 0; obs && r < n; ++r) memcpy(h->pin_in + (size_t)r * ldo, obs + (size_t)r * od, (size_t)od * 4);
   if (done) memcpy(h->pin_in + (size_t)NA * ldo, done, (size_t)n * 4);
   if (eps) memcpy(h->pin_in + (size_t)NA * (ldo + 1), eps, (size_t)n * A * 4);
-  HIPCHK(hipMemcpyAsync(h->ppo_in, h->pin_in, n_in * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->ppo_in + lo, h->pin_in + lo, (n_in - lo) * 4, hipMemcpyHostToDevice, h->stream));
   return GRL_OK;
 }
 // ... and what it returns: action [NA, A] | value [NA] | neglogp [NA]; synchronises
@@ -878,13 +934,26 @@ static int ppo_act(grl_handle h, const float* obs, int n, int flags, const float
   return ppo_receive(h, n, out, nullptr, nullptr);
 }
 
+// obs == NULL: "the rows the last grl_observe normalised"
+static int ppo_observed_rows(grl_handle h, const char* what) {
+  if (!h->n_sd) return fail(GRL_ERR_STATE, std::string(what) + ": obs is NULL, and this handle was created with normalize = 0 (it normalises no observations: hand them over)");
+  if (!h->ppo_observed) return fail(GRL_ERR_STATE, std::string(what) + ": obs is NULL, and no grl_observe call has normalised any rows yet");
+  return GRL_OK;
+}
+
 int grl_ppo_step(grl_handle h, const float* obs, const float* done, const float* eps, float* out_act, float* out_val, float* out_nlp) {
   ROLLOUT_ONLY(h, "grl_ppo_step");
-  if (!obs || !done || !out_act || !out_val || !out_nlp) return fail(GRL_ERR_INVALID, "null argument");
+  if (!done || !out_act || !out_val || !out_nlp) return fail(GRL_ERR_INVALID, "null argument");
+  if (!obs)
+    if (int e = ppo_observed_rows(h, "grl_ppo_step")) return e;
   if (h->ppo_stepped >= h->pcfg.n_steps) return fail(GRL_ERR_STATE, "the rollout is full: grl_ppo_finish and grl_ppo_train empty it");
   if (h->ppo_stepped != h->ppo_closed) return fail(GRL_ERR_STATE, "the previous slot is still open: grl_ppo_rewards closes it");
   if (int e = ppo_send(h, obs, done, eps, h->NA)) return e;
-  if (int e = h->run_seq(eps ? "ppo_step_eps" : "ppo_step_rng", {&h->ops_ppo_step[eps ? 0 : 1]})) return e;
+  if (obs) {
+    if (int e = h->run_seq(eps ? "ppo_step_eps" : "ppo_step_rng", {&h->ops_ppo_step[eps ? 0 : 1]})) return e;
+  } else {
+    if (int e = h->run_seq(eps ? "ppo_step_eps_n" : "ppo_step_rng_n", {&h->ops_ppo_step_n[eps ? 0 : 1]})) return e;
+  }
   if (int e = ppo_receive(h, h->NA, out_act, out_val, out_nlp)) return e;
   h->ppo_stepped += 1;
   h->ppo_finished = false;
@@ -904,10 +973,12 @@ int grl_ppo_rewards(grl_handle h, const float* rew, int n) {
 
 int grl_ppo_finish(grl_handle h, const float* last_obs, const float* last_done) {
   ROLLOUT_ONLY(h, "grl_ppo_finish");
-  if (!last_obs || !last_done) return fail(GRL_ERR_INVALID, "null argument");
+  if (!last_done) return fail(GRL_ERR_INVALID, "null argument");
+  if (!last_obs)
+    if (int e = ppo_observed_rows(h, "grl_ppo_finish")) return e;
   if (h->ppo_closed != h->pcfg.n_steps) return fail(GRL_ERR_STATE, "the rollout is not full: n_steps slots must be closed before grl_ppo_finish");
   if (int e = ppo_send(h, last_obs, last_done, nullptr, h->NA)) return e;
-  if (int e = h->run_seq("ppo_finish", {&h->ops_ppo_finish})) return e;
+  if (int e = last_obs ? h->run_seq("ppo_finish", {&h->ops_ppo_finish}) : h->run_seq("ppo_finish_n", {&h->ops_ppo_finish_n})) return e;
   // (the staging buffer of ppo_send is reused by the next call: wait for its copy, as every per-step call does)
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());

@@ -1522,6 +1522,13 @@ struct grl_ctx {
   int ppo_stepped = 0, ppo_closed = 0, ppo_updates = 0;     // slots written / closed by rewards; updates of the last training call
   bool ppo_finished = false;                                // advantages and returns of the full rollout are on the device
   std::vector<Op> ops_ppo_step[2], ops_ppo_finish, ops_ppo_act[3], ops_ppo_rew, ops_ppo_update;   // [eps handed over | Philox]; act: mean | eps | Philox
+  // normalize = 2 (VecNormalize observation statistics on the device, grl_observe): n_mean / n_var / n_count as on the other
+  // handles, n_stage the raw rows of one env step [n_envs, obs_dim]; sqrt(var + eps); the normalised rows [n_envs, ldo] and the
+  // step / finish lists that read THEM instead of the rows ppo_send uploads (obs == NULL)
+  double* n_sd = nullptr;
+  float* ppo_obs_n = nullptr;
+  bool ppo_observed = false;
+  std::vector<Op> ops_ppo_step_n[2], ops_ppo_finish_n;
   int plan_trpo();     // TRPO (the policy, rollout and GAE of plan_ppo): natural-gradient step, line search, value fit
   // TRPO state (plan_trpo.inl): its configuration block (pcfg is filled from it), the device words, the launch lists of the
   // policy step, of one value minibatch and of the debug Fisher product; value minibatches of the last update

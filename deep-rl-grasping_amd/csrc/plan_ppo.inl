@@ -6,6 +6,8 @@
 //
 //   act path     model.step / model.value / model.predict on act_batch rows: ONE launch (ppo_act_kernel) for observations up to
 //                2048 values and widths up to 256, else dense levels + tanh launches + the output launch + ppo_sample_kernel
+//                normalize = 2: the step and finish lists exist a second time over the rows ppo_observe_kernel normalised
+//                (grl_observe; grl_ppo_step / grl_ppo_finish with obs == NULL) -- the same launches, another input pointer
 //   rollout      in the replay arena, row = env * n_steps + t (swap_and_flatten): obs [R, ldo], action, value, neglogp, reward,
 //                done, advantage, return; the slot counter lives in device memory (PpoDev)
 //   update       ppo_gather | per level: dense (pi, vf) + tanh_fwd | outputs | ppo_loss | per level: backward-data + tanh_bwd |
@@ -118,6 +120,18 @@ struct PpoPlanner {
     h.zero_once.push_back({g_mb.out[1], (size_t)B * 4 * 4});
     dls_slab = wk.f32((int64_t)nblk * A);
     if (!fused_act) alloc_acts(act_a, NA, A, 1);
+    if (c.normalize == 2) {
+      // VecNormalize observation statistics on the device (grl_observe; ppo_observe_kernel) -- behind everything a normalize = 0
+      // handle holds, whose offsets and sizes stay what they were
+      h.n_elems = od;
+      h.n_count = (double*)st.take(16);
+      h.n_mean = (double*)st.take((size_t)od * 8);
+      h.n_var = (double*)st.take((size_t)od * 8);
+      h.n_sd = (double*)st.take((size_t)od * 8);
+      h.n_stage = wk.f32((int64_t)NA * od);
+      h.ppo_obs_n = wk.f32((int64_t)NA * ldo);
+      h.zero_once.push_back({h.ppo_obs_n, (size_t)NA * ldo * 4});
+    }
     P = h.params;
   }
 
@@ -187,12 +201,12 @@ struct PpoPlanner {
   }
 
   // ---------------- the act path: model.step (records), model.value (last values), model.predict (records nothing)
-  PpoSampleArgs sample_args(int mode, int deterministic, bool host_eps) const {
+  PpoSampleArgs sample_args(int mode, int deterministic, bool host_eps, const float* x) const {
     PpoSampleArgs s;
     memset(&s, 0, sizeof(s));
     if (!fused_act) { s.mean = act_a.out[0]; s.ld_mean = A; s.v = act_a.out[1]; s.ld_v = 1; }
     s.logstd = P + logstd_off;
-    s.x = h.ppo_in; s.ldx = ldo;
+    s.x = x; s.ldx = ldo;
     s.done_in = h.ppo_in + (int64_t)NA * ldo;
     s.eps = host_eps ? h.ppo_in + (int64_t)NA * (ldo + 1) : nullptr;
     s.r_obs = h.pr_obs; s.r_act = h.pr_act; s.r_val = h.pr_val; s.r_nlp = h.pr_nlp; s.r_done = h.pr_done;
@@ -203,8 +217,10 @@ struct PpoPlanner {
     return s;
   }
   void act_path() {
-    std::vector<Op> fwd;
+    // (observed: the rows ppo_observe_kernel normalised, normalize = 2 handles -- the same launches over the other buffer)
+    std::vector<Op> fwd, fwd_n;
     if (!fused_act) forward(fwd, h.ppo_in, NA, act_a, "ppo_act");
+    if (!fused_act && c.normalize == 2) forward(fwd_n, h.ppo_obs_n, NA, act_a, "ppo_act");
     PpoActArgs fa;
     memset(&fa, 0, sizeof(fa));
     for (int tw = 0; tw < 2; ++tw) {
@@ -214,9 +230,9 @@ struct PpoPlanner {
       t.ow = P + T[tw].w[t.L]; t.ob = P + T[tw].b[t.L];
     }
     DevScalars* sc = h.sc;
-    auto build = [&](std::vector<Op>& ops, int mode, int det, bool host_eps) {
-      ops = fwd;
-      const PpoSampleArgs sa = sample_args(mode, det, host_eps);
+    auto build = [&](std::vector<Op>& ops, int mode, int det, bool host_eps, bool observed = false) {
+      ops = observed ? fwd_n : fwd;
+      const PpoSampleArgs sa = sample_args(mode, det, host_eps, observed ? h.ppo_obs_n : h.ppo_in);
       Op op; op.tag = fused_act ? "ppo_act" : "ppo_sample";
       if (fused_act) {
         PpoActArgs a = fa;
@@ -238,6 +254,11 @@ struct PpoPlanner {
     build(h.ops_ppo_act[0], 0, 1, false);
     build(h.ops_ppo_act[1], 0, 0, true);
     build(h.ops_ppo_act[2], 0, 0, false);
+    if (c.normalize == 2) {
+      build(h.ops_ppo_step_n[0], 1, 0, true, true);
+      build(h.ops_ppo_step_n[1], 1, 0, false, true);
+      build(h.ops_ppo_finish_n, 2, 1, false, true);
+    }
     if (fused_act) plan_note("grl plan: ppo_act       one launch per call (ppo_act_kernel): %d rows x 2 towers, obs %d\n", NA, od);
     else plan_note("grl plan: ppo_act       launch list (%s): dense levels + tanh + outputs + ppo_sample, %d rows, obs %d\n",
                    od > PPO_ACT_MAX_IN ? "observation beyond 2048 values" : (h.sw.get(Sw::ppo_act) ? "a width beyond 256" : "ppo_act=0"), NA, od);
@@ -258,6 +279,7 @@ struct PpoPlanner {
       Op op; op.tag = "gae";
       op.run = [g](hipStream_t s) { launch_gae(g, s); };
       h.ops_ppo_finish.push_back(op);
+      if (c.normalize == 2) h.ops_ppo_finish_n.push_back(op);
     }
   }
 
@@ -380,6 +402,7 @@ struct PpoPlanner {
   void debug_views() {
     auto& dbg = h.dbg;
     dbg["ppo_obs"] = {h.pr_obs, (int64_t)R * ldo};
+    if (c.normalize == 2) dbg["ppo_obs_n"] = {h.ppo_obs_n, (int64_t)NA * ldo};
     dbg["ppo_act"] = {h.pr_act, (int64_t)R * A};
     dbg["ppo_old_v"] = {h.pr_val, R}; dbg["ppo_old_nlp"] = {h.pr_nlp, R};
     dbg["ppo_rew"] = {h.pr_rew, R}; dbg["ppo_done"] = {h.pr_done, R};

@@ -294,7 +294,7 @@ int grl_ctx::plan_trpo() {
   pcfg.n_envs = 1; pcfg.n_steps = tcfg.n_steps;
   pcfg.n_vf_layers = tcfg.n_vf_layers;
   for (int l = 0; l < tcfg.n_vf_layers; ++l) pcfg.vf_layers[l] = tcfg.vf_layers[l];
-  pcfg.lam = tcfg.lam; pcfg.adam_eps = tcfg.adam_eps;
+  pcfg.lam = tcfg.lam; pcfg.adam_eps = tcfg.adam_eps; pcfg.norm_eps64 = tcfg.norm_eps64;
   PpoPlanner pp(*this);
   pp.layout();
   pp.routes();

@@ -1,4 +1,4 @@
-// ppo.hip -- the PPO2 kernels (ppo_kernels.h: one-launch act, policy tail, rewards, GAE, minibatch gather, tanh, loss).
+// ppo.hip -- the PPO2 kernels (ppo_kernels.h: one-launch act, policy tail, rewards, GAE, minibatch gather, tanh, loss, observe).
 // Launchers declared there.
 #ifdef GRL_HOSTEMU
 #include "hostemu.h"
@@ -31,6 +31,10 @@ void launch_tanh_bwd(const TanhDesc* descs, int n_desc, int rows, int max_h, hip
 }
 void launch_ppo_loss(const PpoLossArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(ppo_loss_kernel, dim3(ppo_loss_blocks(a.mb)), dim3(PPO_LOSS_ROWS), 0, s, a);
+}
+// (one thread per column of the normalised rows, the zero padding included)
+void launch_ppo_observe(const PpoObserveArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(ppo_observe_kernel, dim3((a.ldo + 255) / 256), dim3(256), 0, s, a);
 }
 
 }  // namespace grl

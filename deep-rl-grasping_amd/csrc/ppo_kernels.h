@@ -20,6 +20,9 @@
 //   ppo_loss_kernel     row-local: one lane per row, a loop over the action components.  d mean, d v, per-block slabs of d logstd
 //                       (summed into the bucket by a reduction descriptor, as every other gradient) and per-block sums of the
 //                       diagnostics (added in index order by grl_ppo_get_metrics).
+//   ppo_observe_kernel  normalize = 2 handles: RunningMeanStd.update over one env step's raw observations and the normalised rows
+//                       the act path reads, in one launch (the arithmetic of elem_kernels.h: norm_batch_moments, norm_chan_merge,
+//                       norm_obs_act)
 //
 // Every batch sum leaves as per-block slabs and is added in index order, as ln_kernels.h does for dbeta / dgamma.
 #pragma once
@@ -250,6 +253,52 @@ __device__ __forceinline__ float ppo_entropy(const PpoLossArgs& a) {
   return e;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- observe
+// VecNormalize observation statistics of a normalize = 2 handle (grl_observe): stable-baselines normalises a PPO observation ONCE,
+// at step time, with the statistics as they stand right after that step's RunningMeanStd.update -- the normalised row is what the
+// rollout stores -- so one launch per env step does both.  One thread owns element e of the flattened observation:
+//   update = 1   norm_update_kernel's work (float32 batch moments over the n staged rows in row order, the float64 Chan merge with
+//                `batch_var * n` a float32 product; mean, var, sqrt(var + eps) stored; count double buffered by parity), then
+//   every call   out[i, e] = norm_obs_act(x[i, e], mean, sd, clip) for every row with the statistics just formed (update = 0: the
+//                stored ones); columns [elems, ldo) of `out` are written zero.  A NaN observation stays a NaN (np.clip leaves it).
+// A raw element is fetched from HBM by the first pass over its column; the second pass of the moments and the normalising pass hit
+// L2 (n_envs x obs_dim floats: 512 KiB at 16 x 8192).  The arithmetic is elem_kernels.h's, one copy.  Compiles as it stands in
+// the emulation build, like norm_update_kernel.
+struct PpoObserveArgs {
+  NormUpdateArgs nu;      // obs: the raw staged rows [n, elems]; mean, var, count, parity, eps (the derived arrays and image fields: unused)
+  double* sd;             // [elems] sqrt(var + eps)
+  float* out; int ldo;    // [n, ldo]
+  double clip;
+  int update;
+};
+
+#ifndef GRL_PPO_TYPES_ONLY
+__global__ __launch_bounds__(256) void ppo_observe_kernel(PpoObserveArgs a) {
+  const NormUpdateArgs& u = a.nu;
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= a.ldo) return;
+  if (e >= u.elems) {
+    for (int i = 0; i < u.n; ++i) a.out[(long)i * a.ldo + e] = 0.f;
+    return;
+  }
+  double mean = u.mean[e], sd;
+  if (a.update) {
+    double cnt = u.count[u.parity], var = u.var[e];
+    float bm, bv;
+    norm_batch_moments(u, e, bm, bv);
+    norm_chan_merge(mean, var, cnt, bm, bv, u.n, true);
+    sd = sqrt(var + u.eps);
+    u.mean[e] = mean;
+    u.var[e] = var;
+    a.sd[e] = sd;
+    if (e == 0) u.count[u.parity ^ 1] = cnt;
+  } else {
+    sd = a.sd[e];
+  }
+  for (int i = 0; i < u.n; ++i) a.out[(long)i * a.ldo + e] = norm_obs_act(u.obs[(long)i * u.elems + e], mean, sd, a.clip);
+}
+#endif
+
 #ifndef GRL_PPO_TYPES_ONLY
 #ifdef GRL_HOSTEMU
 #include "ppo_kernels_ref1.h"   // tests/hostemu: the emulation build only
@@ -459,5 +508,6 @@ void launch_ppo_gather(const PpoGatherArgs& a, hipStream_t s);
 void launch_tanh_fwd(const TanhDesc* descs, int n_desc, int rows, int max_h, hipStream_t s);
 void launch_tanh_bwd(const TanhDesc* descs, int n_desc, int rows, int max_h, hipStream_t s);
 void launch_ppo_loss(const PpoLossArgs& a, hipStream_t s);
+void launch_ppo_observe(const PpoObserveArgs& a, hipStream_t s);
 
 }  // namespace grl

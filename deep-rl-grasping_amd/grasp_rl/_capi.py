@@ -38,7 +38,7 @@ class GrlPpoConfig(C.Structure):
         ("n_vf_layers", C.c_int32), ("vf_layers", C.c_int32 * GRL_MAX_LAYERS),
         ("lam", C.c_float), ("clip_range", C.c_float), ("clip_range_vf", C.c_float),
         ("ent_coef", C.c_float), ("vf_coef", C.c_float), ("max_grad_norm", C.c_float),
-        ("adam_eps", C.c_float),
+        ("adam_eps", C.c_float), ("norm_eps64", C.c_double),
     ]
 
 
@@ -52,7 +52,7 @@ class GrlTrpoConfig(C.Structure):
         ("n_vf_layers", C.c_int32), ("vf_layers", C.c_int32 * GRL_MAX_LAYERS),
         ("cg_iters", C.c_int32), ("ls_steps", C.c_int32), ("fvp_stride", C.c_int32), ("vf_batch", C.c_int32),
         ("lam", C.c_float), ("max_kl", C.c_float), ("cg_damping", C.c_float), ("ent_coef", C.c_float),
-        ("adam_eps", C.c_float),
+        ("adam_eps", C.c_float), ("norm_eps64", C.c_double),
     ]
 
 
@@ -316,11 +316,20 @@ def make_q_config(algo, obs_dim, n_branches, n_bins, common=(), branch_hidden=(6
     return cfg
 
 
+def _ppo_normalize(cfg, second, normalize, clip_obs, norm_eps):
+    """grl_config.normalize / clip_obs / norm_eps of a PPO2 / TRPO handle; the epsilon also as the float64 it is (norm_eps64)."""
+    cfg.normalize = norm_mode(normalize)
+    if cfg.normalize:
+        cfg.clip_obs, cfg.norm_eps, second.norm_eps64 = float(clip_obs), float(norm_eps), float(norm_eps)
+
+
 def make_ppo_config(obs_dim, act_dim, n_envs=1, n_steps=128, nminibatches=4, pi_layers=(64, 64), vf_layers=(64, 64), gamma=0.99,
                     lam=0.95, lr=2.5e-4, ent_coef=0.01, vf_coef=0.5, max_grad_norm=0.5, cliprange=0.2, cliprange_vf=None,
-                    adam_eps=1e-5, seed=0):
+                    adam_eps=1e-5, seed=0, normalize=0, clip_obs=10.0, norm_eps=1e-8):
     """(GrlConfig, GrlPpoConfig) of a PPO2 handle (stable-baselines 2.10.1 PPO2 + actor-critic MlpPolicy, Box actions).
-    cliprange_vf None: the policy's cliprange; negative: no value clipping.  max_grad_norm None or <= 0: no clipping."""
+    cliprange_vf None: the policy's cliprange; negative: no value clipping.  max_grad_norm None or <= 0: no clipping.
+    normalize 2 (or "obs"): the handle keeps VecNormalize's observation statistics (grl_observe) and normalises with clip_obs
+    and norm_eps, the wrapper's clip_obs / epsilon; 0: it is handed normalised observations and the two are not read."""
     n_batch = int(n_envs) * int(n_steps)
     if n_batch % int(nminibatches):
         raise GrlError("The number of minibatches (`nminibatches`) is not a factor of the total number of samples "
@@ -332,6 +341,7 @@ def make_ppo_config(obs_dim, act_dim, n_envs=1, n_steps=128, nminibatches=4, pi_
     cfg.algo = 4
     cfg.tau = cfg.clip_obs = cfg.clip_reward = cfg.norm_eps = cfg.target_entropy = 0.0
     ppo = GrlPpoConfig()
+    _ppo_normalize(cfg, ppo, normalize, clip_obs, norm_eps)
     ppo.n_envs, ppo.n_steps = int(n_envs), int(n_steps)
     ppo.n_vf_layers = len(vf_layers)
     for i, h in enumerate(vf_layers):
@@ -346,7 +356,7 @@ def make_ppo_config(obs_dim, act_dim, n_envs=1, n_steps=128, nminibatches=4, pi_
 
 def make_trpo_config(obs_dim, act_dim, timesteps_per_batch=1024, pi_layers=(64, 64), vf_layers=(64, 64), gamma=0.99, lam=0.98,
                      max_kl=0.01, cg_iters=10, cg_damping=1e-2, entcoeff=0.0, vf_stepsize=3e-4, ls_steps=10, fvp_stride=5,
-                     vf_batch=128, adam_eps=1e-8, seed=0):
+                     vf_batch=128, adam_eps=1e-8, seed=0, normalize=0, clip_obs=10.0, norm_eps=1e-8):
     """(GrlConfig, GrlTrpoConfig) of a TRPO handle (stable-baselines 2.10.1 TRPO + actor-critic MlpPolicy, Box actions, one
     environment).  ls_steps, fvp_stride and vf_batch are constants of stable-baselines (10, 5, 128); tests vary ls_steps."""
     if len(vf_layers) > GRL_MAX_LAYERS:
@@ -356,6 +366,7 @@ def make_trpo_config(obs_dim, act_dim, timesteps_per_batch=1024, pi_layers=(64, 
     cfg.algo = 5
     cfg.tau = cfg.clip_obs = cfg.clip_reward = cfg.norm_eps = cfg.target_entropy = 0.0
     t = GrlTrpoConfig()
+    _ppo_normalize(cfg, t, normalize, clip_obs, norm_eps)
     t.n_steps = int(timesteps_per_batch)
     t.n_vf_layers = len(vf_layers)
     for i, h in enumerate(vf_layers):

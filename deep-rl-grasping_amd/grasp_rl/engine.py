@@ -828,7 +828,11 @@ class QEngine(SacEngine):
 class PpoEngine(SacEngine):
     """PPO2 handle (``_capi.make_ppo_config``): the rollout lives on the device; ``step`` / ``rewards`` fill a slot per env step,
     ``finish`` forms the last values and GAE, ``train`` runs noptepochs * nminibatches updates over the permutations handed to
-    it.  Parameters, ``set_learning_rate``, ``reset_optimizer``, ``fetch`` / ``store`` and profiling as on every handle."""
+    it.  Parameters, ``set_learning_rate``, ``reset_optimizer``, ``fetch`` / ``store`` and profiling as on every handle.
+
+    A handle configured with ``normalize=2`` keeps VecNormalize's observation statistics: ``observe`` (the n_envs raw rows of one
+    env step, one upload and one launch), ``set_obs_stats`` / ``set_running_stats`` / ``get_obs_stats`` are SacEngine's methods,
+    and ``step`` / ``finish`` with ``obs=None`` act on the rows the last ``observe`` normalised."""
 
     def __init__(self, cfg, ppo, backend=None, lib_path=None, device="cuda:0"):
         self.ppo = ppo
@@ -837,6 +841,7 @@ class PpoEngine(SacEngine):
         self.R = self.n_envs * self.n_steps
         self.ldo = (self.obs_dim + 3) // 4 * 4
         self.n_minibatches = self.R // cfg.batch_size
+        self.observe_rows = self.n_envs      # grl_observe on these handles takes exactly one env step of all environments
 
     def _query_sizes(self, cfg, sizes):
         return self.lib.grl_ppo_query_sizes(C.byref(cfg), C.byref(self.ppo), C.byref(sizes))
@@ -845,16 +850,18 @@ class PpoEngine(SacEngine):
         return self.lib.grl_ppo_create(C.byref(cfg), C.byref(self.ppo), C.byref(bufs), C.byref(h))
 
     def step(self, obs, done, eps=None):
-        """model.step on the n_envs observations: (actions [n, A] unclipped, values [n], neglogps [n]); recorded in the open slot."""
+        """model.step on the n_envs observations: (actions [n, A] unclipped, values [n], neglogps [n]); recorded in the open slot.
+        obs None: the rows the last ``observe`` normalised on the device."""
         n, A = self.n_envs, self.A
-        obs = np.ascontiguousarray(obs, dtype=np.float32).reshape(n, self.obs_dim)
+        if obs is not None:
+            obs = np.ascontiguousarray(obs, dtype=np.float32).reshape(n, self.obs_dim)
         done = np.ascontiguousarray(done, dtype=np.float32).reshape(n)
         pe = None
         if eps is not None:
             eps = np.ascontiguousarray(eps, dtype=np.float32).reshape(n, A)
             pe = eps.ctypes.data
         act, val, nlp = np.empty((n, A), np.float32), np.empty(n, np.float32), np.empty(n, np.float32)
-        check(self.lib, self.lib.grl_ppo_step(self.h, obs.ctypes.data, done.ctypes.data, pe, act.ctypes.data, val.ctypes.data,
+        check(self.lib, self.lib.grl_ppo_step(self.h, None if obs is None else obs.ctypes.data, done.ctypes.data, pe, act.ctypes.data, val.ctypes.data,
                                               nlp.ctypes.data))
         return act, val, nlp
 
@@ -863,9 +870,10 @@ class PpoEngine(SacEngine):
         check(self.lib, self.lib.grl_ppo_rewards(self.h, rew.ctypes.data, self.n_envs))
 
     def finish(self, last_obs, last_done):
-        last_obs = np.ascontiguousarray(last_obs, dtype=np.float32).reshape(self.n_envs, self.obs_dim)
+        if last_obs is not None:      # (None: the rows the last ``observe`` normalised)
+            last_obs = np.ascontiguousarray(last_obs, dtype=np.float32).reshape(self.n_envs, self.obs_dim)
         last_done = np.ascontiguousarray(last_done, dtype=np.float32).reshape(self.n_envs)
-        check(self.lib, self.lib.grl_ppo_finish(self.h, last_obs.ctypes.data, last_done.ctypes.data))
+        check(self.lib, self.lib.grl_ppo_finish(self.h, None if last_obs is None else last_obs.ctypes.data, last_done.ctypes.data))
 
     def train(self, perm):
         """perm [noptepochs, R] int32: one permutation of the rollout rows per epoch."""

@@ -11,7 +11,15 @@ permutation per epoch from the model's seeded generator, episode statistics and 
 Scope: the actor-critic ``MlpPolicy`` (two tanh towers, ``net_arch=[dict(vf=[...], pi=[...])]``) on ``Box`` actions, observations
 of any rank flattened in C order and not divided by 255, N environments (a VecEnv, or GRL_NUM_ENVS around the script's
 one-factory DummyVecEnv).  Everything else says what it refuses.  ``model.save`` writes the stable-baselines zip only
-(GRL_CHECKPOINT_STATE is not defined for PPO2); VecNormalize stays on the host, where stable-baselines applies it at step time.
+(GRL_CHECKPOINT_STATE is not defined for PPO2).
+
+VecNormalize: stable-baselines normalises a PPO observation once, at step time, with the statistics right after that step's
+update, and the rollout stores the normalised row.  By default the wrapper does that on the host.  ``device_norm=True`` (or
+GRL_DEVICE_NORM=1 / auto; unset means off) keeps the OBSERVATION statistics in device memory while ``learn`` runs: every env step
+uploads the raw observations once (``engine.observe``: one launch updates the statistics and writes the normalised rows) and
+``step`` / ``finish`` read those rows -- the same bits as the host path, float64 statistics included; the wrapper carries them
+again when ``learn`` returns.  Rewards are normalised on the host in both cases (n_envs floats per step); callbacks see raw
+observations in ``locals`` while the device path is on, which is why ``'auto'`` leaves it off for a callback that may read them.
 """
 import time
 from collections import deque
@@ -41,13 +49,29 @@ def _safe_mean(xs):
     return np.nan if len(xs) == 0 else float(np.mean(xs))
 
 
+def _device_norm_setting(device_norm):
+    """The ``device_norm`` keyword of PPO2 / TRPO: True, False or 'auto'; None reads GRL_DEVICE_NORM with the DQN / BDQ rule (unset
+    means off, 1 on, auto auto)."""
+    import os
+    if device_norm is None:
+        device_norm = {"0": False, "1": True, "auto": "auto"}.get(os.environ.get("GRL_DEVICE_NORM", "0"), False)
+    return device_norm if device_norm == "auto" else bool(device_norm)
+
+
+def _normalize_kwargs(vn):
+    """make_ppo_config / make_trpo_config: a handle that can keep the wrapper's observation statistics (normalize = 2)."""
+    if vn is None or not vn.norm_obs:
+        return {}
+    return dict(normalize=2, clip_obs=float(vn.clip_obs), norm_eps=float(vn.epsilon))
+
+
 class PPO2:
     _engine_factory = staticmethod(lambda cfg, ppo, device: PpoEngine(cfg, ppo, device=device))
 
     def __init__(self, policy, env, gamma=0.99, n_steps=128, ent_coef=0.01, learning_rate=2.5e-4, vf_coef=0.5,
                  max_grad_norm=0.5, lam=0.95, nminibatches=4, noptepochs=4, cliprange=0.2, cliprange_vf=None, verbose=0,
                  tensorboard_log=None, _init_setup_model=True, policy_kwargs=None, full_tensorboard_log=False, seed=None,
-                 n_cpu_tf_sess=None, device="cuda:0", data_parallel=None):
+                 n_cpu_tf_sess=None, device="cuda:0", data_parallel=None, device_norm=None):
         import os
         if data_parallel is None:
             data_parallel = os.environ.get("GRL_DATA_PARALLEL") or None
@@ -56,6 +80,7 @@ class PPO2:
         if callable(cliprange) or callable(cliprange_vf):
             raise NotImplementedError("PPO2: a callable cliprange / cliprange_vf is not implemented (the clip ranges are "
                                       "constants of the device plan)")
+        self.device_norm = _device_norm_setting(device_norm)
         self.policy, self.policy_kwargs = policy, ({} if policy_kwargs is None else dict(policy_kwargs))
         self.gamma, self.n_steps, self.ent_coef, self.learning_rate = gamma, int(n_steps), ent_coef, learning_rate
         self.vf_coef, self.max_grad_norm, self.lam = vf_coef, max_grad_norm, lam
@@ -147,7 +172,7 @@ class PPO2:
                                          lr=float(_constfn(self.learning_rate)(1.0)), ent_coef=self.ent_coef, vf_coef=self.vf_coef,
                                          max_grad_norm=self.max_grad_norm, cliprange=float(self.cliprange),
                                          cliprange_vf=None if self.cliprange_vf is None else float(self.cliprange_vf),
-                                         seed=0 if self.seed is None else int(self.seed))
+                                         seed=0 if self.seed is None else int(self.seed), **_normalize_kwargs(self._vec_normalize_env))
         self.engine = self._engine_factory(cfg, ppo, self.device)
         self.engine.set_parameters(init_ppo_parameters(self.engine.table, 0 if self.seed is None else int(self.seed)))
 
@@ -175,16 +200,49 @@ class PPO2:
         if reset_num_timesteps:
             self.num_timesteps = 0
         lr_fn = _constfn(self.learning_rate)
+        device_norm = self._resolve_device_norm(callback)      # (decided from the callback the USER handed over)
         callback = as_callback(callback)
         callback.init_callback(self)
         # stable-baselines hands callbacks a FileWriter when tensorboard_log is set, None otherwise
         writer = logger.SummaryWriter(self.tensorboard_log, tb_log_name) if self.tensorboard_log else None
         try:
+            self._attach_device_norm(device_norm)
             self._learn_loop(total_timesteps, callback, log_interval, writer, lr_fn)
         finally:
+            self._detach_device_norm()
             if writer is not None:
                 writer.close()
         return self
+
+    # ------------------------------------------------------------------ VecNormalize observation statistics on the device
+    def _resolve_device_norm(self, user_callback):
+        from .sac import resolve_device_norm
+        return self.device_norm is not False and resolve_device_norm(self.device_norm, user_callback, None, None)
+
+    def _attach_device_norm(self, device_norm):
+        vn = self._vec_normalize_env
+        if not device_norm or vn is None or not vn.norm_obs:
+            return
+        if self.engine.cfg.normalize == 2:
+            vn.attach_device(self.engine)
+        else:      # a zip loaded without env and given a normalised env later: the device plan holds no statistics
+            logger.warn("%s: device_norm needs a model built on the VecNormalize env (pass env= to the constructor or to load); "
+                        "this one was built without it -> VecNormalize stays on the host" % type(self).__name__)
+
+    def _detach_device_norm(self):
+        vn = self._vec_normalize_env
+        if vn is not None and vn._dev is not None:      # whatever ended the loop: the wrapper carries the statistics again
+            vn.detach_device()
+
+    def _rows(self, obs, n):
+        """What ``engine.step`` / ``engine.finish`` get for the observations in hand: None when the wrapper's latest
+        ``engine.observe`` uploaded exactly them (the device normalised them with the statistics of that moment, as the host
+        path would have), else the array -- a callback cleared ``training``, the host path, or no wrapper at all."""
+        vn = self._vec_normalize_env
+        if vn is not None and vn._dev is self.engine and vn.observed_serial is not None \
+                and vn.observed_serial == getattr(self.engine, "_observe_serial", None):
+            return None
+        return obs.reshape(n, -1)
 
     def _learn_loop(self, total_timesteps, callback, log_interval, writer, lr_fn):
         eng, N, T = self.engine, self.n_envs, self.n_steps
@@ -202,7 +260,7 @@ class PPO2:
             # ---- Runner._run: n_steps policy steps; what the update needs stays on the device
             values, rewards, ep_infos, go_on = np.zeros((T, N), np.float32), np.zeros((T, N), np.float32), [], True
             for step in range(T):
-                actions, values[step], neglogpacs = eng.step(obs.reshape(N, -1), dones)
+                actions, values[step], neglogpacs = eng.step(self._rows(obs, N), dones)
                 clipped_actions = self._clip(actions.reshape((N,) + tuple(self.action_space.shape)))
                 obs, rew, done, infos = self.env.step(clipped_actions)
                 obs, dones = np.asarray(obs, np.float32), np.asarray(done, np.float32).reshape(N)
@@ -219,7 +277,7 @@ class PPO2:
                 eng.rewards(rewards[step])
             if not go_on:
                 break
-            eng.finish(obs.reshape(N, -1), dones)
+            eng.finish(self._rows(obs, N), dones)      # (device path: the rows serve the next rollout's first step as well)
             callback.on_rollout_end()
             self.ep_info_buf.extend(ep_infos)
             # ---- noptepochs epochs over nminibatches consecutive slices of a fresh permutation each

@@ -17,8 +17,11 @@ updated policy.
 
 Scope: the actor-critic ``MlpPolicy`` (two tanh towers, ``net_arch=[dict(vf=[...], pi=[...])]``) on ``Box`` actions, observations
 of any rank flattened in C order and not divided by 255, one environment (GRL_NUM_ENVS does not fan a TRPO env out).  GAIL, data
-parallelism and GRL_CHECKPOINT_STATE are not defined for TRPO; VecNormalize stays on the host.  Everything else says what it
-refuses.
+parallelism and GRL_CHECKPOINT_STATE are not defined for TRPO.  Everything else says what it refuses.
+
+VecNormalize works on the host by default; ``device_norm=True`` (GRL_DEVICE_NORM=1 / auto; unset means off) keeps its observation
+statistics on the device while ``learn`` runs, exactly as ``PPO2(device_norm=...)`` does (ppo2.py): one ``engine.observe`` per
+env step and per reset, ``step`` / ``finish`` on the rows it normalised, rewards on the host.
 """
 import os
 import time
@@ -33,7 +36,7 @@ from . import logger
 from . import save_util
 from . import spaces as sp
 from .callbacks import as_callback
-from .ppo2 import PPO2, _safe_mean, explained_variance
+from .ppo2 import PPO2, _device_norm_setting, _normalize_kwargs, _safe_mean, explained_variance
 from .vec_env import DummyVecEnv, VecEnv, unwrap_vec_normalize
 
 VF_BATCH = 128      # trpo_mpi.py: dataset.iterbatches(..., batch_size=128, include_final_partial_batch=False)
@@ -44,7 +47,8 @@ class TRPO(PPO2):
 
     def __init__(self, policy, env, gamma=0.99, timesteps_per_batch=1024, max_kl=0.01, cg_iters=10, lam=0.98, entcoeff=0.0,
                  cg_damping=1e-2, vf_stepsize=3e-4, vf_iters=3, verbose=0, tensorboard_log=None, _init_setup_model=True,
-                 policy_kwargs=None, full_tensorboard_log=False, seed=None, n_cpu_tf_sess=1, device="cuda:0", **gail):
+                 policy_kwargs=None, full_tensorboard_log=False, seed=None, n_cpu_tf_sess=1, device="cuda:0", device_norm=None,
+                 **gail):
         if policy is None:
             raise NotImplementedError("TRPO: policy None is not implemented (only the actor-critic MlpPolicy)")
         if gail:
@@ -56,6 +60,7 @@ class TRPO(PPO2):
             raise NotImplementedError("TRPO: the GAIL arguments %s are not implemented (no adversary on the device)" % sorted(gail))
         if os.environ.get("GRL_DATA_PARALLEL") not in (None, "", "0", "off"):
             raise NotImplementedError("TRPO: data_parallel is not implemented (one replica, one environment)")
+        self.device_norm = _device_norm_setting(device_norm)
         self.policy, self.policy_kwargs = policy, ({} if policy_kwargs is None else dict(policy_kwargs))
         self.gamma, self.timesteps_per_batch, self.max_kl, self.cg_iters = gamma, int(timesteps_per_batch), max_kl, int(cg_iters)
         self.lam, self.entcoeff, self.cg_damping, self.vf_stepsize, self.vf_iters = lam, entcoeff, cg_damping, vf_stepsize, int(vf_iters)
@@ -119,7 +124,8 @@ class TRPO(PPO2):
         cfg, trpo = _capi.make_trpo_config(self._obs_dim, self._act_dim, timesteps_per_batch=self.timesteps_per_batch, pi_layers=pi,
                                            vf_layers=vf, gamma=self.gamma, lam=self.lam, max_kl=self.max_kl, cg_iters=self.cg_iters,
                                            cg_damping=self.cg_damping, entcoeff=self.entcoeff, vf_stepsize=float(self.vf_stepsize),
-                                           vf_batch=VF_BATCH, seed=0 if self.seed is None else int(self.seed))
+                                           vf_batch=VF_BATCH, seed=0 if self.seed is None else int(self.seed),
+                                           **_normalize_kwargs(self._vec_normalize_env))
         self.engine = self._engine_factory(cfg, trpo, self.device)
         self.engine.set_parameters(init_ppo_parameters(self.engine.table, 0 if self.seed is None else int(self.seed)))
 
@@ -135,12 +141,15 @@ class TRPO(PPO2):
         total_timesteps = int(total_timesteps)
         if reset_num_timesteps:
             self.num_timesteps = 0
+        device_norm = self._resolve_device_norm(callback)      # (decided from the callback the USER handed over)
         callback = as_callback(callback)
         callback.init_callback(self)
         writer = logger.SummaryWriter(self.tensorboard_log, tb_log_name) if self.tensorboard_log else None
         try:
+            self._attach_device_norm(device_norm)
             self._learn_loop(total_timesteps, callback, log_interval, writer, None)
         finally:
+            self._detach_device_norm()
             if writer is not None:
                 writer.close()
         return self
@@ -158,7 +167,7 @@ class TRPO(PPO2):
             # ---- traj_segment_generator: T policy steps of the one environment; what the update needs stays on the device
             vpreds, rewards, ep_rets, ep_lens, ep_infos, go_on = np.zeros(T, np.float32), np.zeros(T, np.float32), [], [], [], True
             for step in range(T):
-                actions, vpred, _ = eng.step(obs.reshape(1, -1), episode_start)
+                actions, vpred, _ = eng.step(self._rows(obs, 1), episode_start)
                 vpreds[step] = vpred[0]
                 clipped_actions = self._clip(actions.reshape((1,) + tuple(self.action_space.shape)))
                 obs, rew, done, infos = self.env.step(clipped_actions)
@@ -184,7 +193,7 @@ class TRPO(PPO2):
                     obs = np.asarray(self.env.reset(), np.float32)
             if not go_on:
                 break
-            eng.finish(obs.reshape(1, -1), episode_start)      # nextvpred = V(obs_T) * (1 - episode_start_T), GAE, tdlamret
+            eng.finish(self._rows(obs, 1), episode_start)      # nextvpred = V(obs_T) * (1 - episode_start_T), GAE, tdlamret
             callback.on_rollout_end()
             self.ep_info_buf.extend(ep_infos)
             want_log = self.verbose >= 1

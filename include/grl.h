@@ -185,7 +185,10 @@ int grl_set_learning_rate(grl_handle h, float lr);
 /* VecNormalize statistics (host float64, HWC layout of the observation space or [obs_dim]);
    obs_var/ret_var are variances, epsilon is added inside.  Copied before returning. */
 int grl_set_obs_stats(grl_handle h, const double* obs_mean, const double* obs_var, double ret_var);
-/* The same statistics maintained ON THE DEVICE (SAC, DQN and BDQ handles).  VecNormalize.step_wait -> obs_rms.update(obs)
+/* The same statistics maintained ON THE DEVICE (SAC, DQN and BDQ handles; PPO / TRPO handles created with normalize = 2 keep the
+   OBSERVATION statistics the same way, see grl_observe and the PPO2 block: grl_set_running_stats and grl_get_obs_stats work on
+   them as described here, grl_set_obs_stats loads mean / var and ignores ret_var, grl_norm_update is GRL_ERR_STATE; on a
+   normalize = 0 PPO / TRPO handle all of them are GRL_ERR_STATE).  VecNormalize.step_wait -> obs_rms.update(obs)
    (stable-baselines RunningMeanStd.update / update_from_moments, wrapper created at sb_helper.py:117-119): merges the
    batch moments of the n raw observations of one env step (HOST pointer, env layout [n, 64, 64, C+1] or [n, obs_dim],
    n <= max(act_batch, 64)) into the running mean / variance / count in device memory -- float32 batch moments like
@@ -339,7 +342,12 @@ int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps_o
    GRL_ERR_STATE unless the last two grl_observe calls both held n observations.  Rows whose episode ended store the
    terminal observation instead: term_rows [n_term] names them, term_obs [n_term, env layout] holds their observations
    (the auto-resetting VecEnv has already put the next episode's first observation in the observed row).
-   All stream-ordered; nothing synchronises. */
+   All stream-ordered; nothing synchronises.
+   PPO / TRPO handles created with normalize = 2: n must equal n_envs (GRL_ERR_INVALID otherwise).  The raw rows are uploaded once
+   and ONE launch (ppo_observe_kernel) folds them into the running statistics (with GRL_OBSERVE_UPDATE_STATS; without it the
+   statistics stay) and writes VecNormalize.normalize_obs of every row, float32, with the statistics as they stand after that
+   update -- what stable-baselines stores in a PPO rollout -- into the rows grl_ppo_step / grl_ppo_finish read when their obs is
+   NULL.  A NaN observation stays a NaN.  grl_replay_add_observed is GRL_ERR_STATE on these handles. */
 #define GRL_OBSERVE_UPDATE_STATS 1
 int grl_observe(grl_handle h, const float* obs, int n, int flags);
 int grl_replay_add_observed(grl_handle h, const float* act, const float* rew, const float* done, int n,
@@ -369,8 +377,13 @@ int grl_encode(grl_handle h, const float* depth, int n, float* out_feat);
    calls below (grl_query_sizes / grl_create return GRL_ERR_INVALID for algo 4 and name them).  In the grl_config of such a handle
    extractor is GRL_EXTRACTOR_MLP; obs_dim (observations of any rank flattened in C order, not divided by 255), act_dim and seed
    mean what they say; n_layers / layers[] describe the pi tower (tanh, widths 1..1024); batch_size is the minibatch row count;
-   act_batch equals n_envs; replay_capacity is R = n_envs * n_steps; normalize is 0; gamma and lr mean what they say; every q_*,
-   ae_* and replay_rgb_u8 field is 0.  The four arenas keep their roles; the rollout lives in the replay arena.
+   act_batch equals n_envs; replay_capacity is R = n_envs * n_steps; gamma and lr mean what they say; every q_*,
+   ae_* and replay_rgb_u8 field is 0.  normalize is 0 (the handle is handed normalised observations) or 2: the handle also
+   keeps VecNormalize's observation statistics in float64 -- running mean / var [obs_dim] and count, starting at 0 / 1 / 1e-4,
+   and sqrt(var + eps) -- the raw rows of one env step and their normalised form [n_envs, rup(obs_dim, 4)] (grl_observe;
+   clip_obs and norm_eps are read, the epsilon as grl_ppo_config.norm_eps64 when that is set).  1 and 3 are GRL_ERR_INVALID:
+   they normalise rewards at sample time, and a rollout stores the reward VecNormalize normalised at step time, on the host.
+   A normalize = 0 handle is what it was before the value 2 existed: arena sizes, plan and launches.  The four arenas keep their roles; the rollout lives in the replay arena.
    Parameters (grl_param_info), TF creation order: model/pi_fc<l>/{w,b}:0 and model/vf_fc<l>/{w,b}:0 with the layer index
    outermost, model/vf/{w,b}:0, model/pi/{w,b}:0, model/pi/logstd:0 [1, A], model/q/{w,b}:0 (initialised, never read, not trainable). */
 typedef struct grl_ppo_config {
@@ -379,6 +392,8 @@ typedef struct grl_ppo_config {
   float lam, clip_range, clip_range_vf;    /* clip_range_vf < 0: no value clipping */
   float ent_coef, vf_coef, max_grad_norm;  /* max_grad_norm <= 0: no clipping */
   float adam_eps;                          /* 1e-5 */
+  double norm_eps64;                       /* normalize = 2: VecNormalize's epsilon as the Python float it is (1e-8 is no float32);
+                                              0: grl_config.norm_eps widened */
 } grl_ppo_config;
 int grl_ppo_query_sizes(const grl_config* cfg, const grl_ppo_config* ppo, grl_sizes* out);
 int grl_ppo_create(const grl_config* cfg, const grl_ppo_config* ppo, const grl_buffers* bufs, grl_handle* out);
@@ -386,7 +401,9 @@ int grl_ppo_create(const grl_config* cfg, const grl_ppo_config* ppo, const grl_b
 /* model.step: n == n_envs rows. obs [n, obs_dim], done [n] (flags from before the step), eps_or_null [n, A] are host pointers
    (NULL: device Philox from cfg.seed). Writes obs / action / value / neglogp / done into slot t of the rollout on the device
    and copies action (unclipped), value, neglogp to the host outputs; synchronises. GRL_ERR_STATE when the rollout is full or the
-   previous slot has not been closed by grl_ppo_rewards. */
+   previous slot has not been closed by grl_ppo_rewards.  obs == NULL (grl_ppo_finish: last_obs == NULL) means "the rows the last
+   grl_observe normalised": GRL_ERR_STATE when there are none or the handle has normalize = 0; a non-NULL obs is taken as
+   already normalised. */
 int grl_ppo_step(grl_handle h, const float* obs, const float* done, const float* eps_or_null,
                  float* out_act, float* out_val, float* out_nlp);
 int grl_ppo_rewards(grl_handle h, const float* rew, int n);                     /* closes slot t; stream-ordered */
@@ -405,8 +422,10 @@ int grl_ppo_get_metrics(grl_handle h, float* out, int cap);
    grl_set_learning_rate, grl_set_stream, grl_profile_* and grl_debug_fetch / _store work; the debug names are "ppo_obs" [R, ld],
    "ppo_act", "ppo_old_v", "ppo_old_nlp", "ppo_rew", "ppo_done", "ppo_adv", "ppo_ret" (rollout, row = env * n_steps + t),
    "ppo_last_v", "ppo_last_done", "ppo_mean", "ppo_v" (the last minibatch), "ppo_slots" (grl_debug_store only, three values: slots written,
-   slots closed, finished -- says how far a rollout placed through the other names has got), "grads", "adam_m", "adam_v".  Every other entry point returns
-   GRL_ERR_STATE on a PPO handle before anything moves. */
+   slots closed, finished -- says how far a rollout placed through the other names has got), "grads", "adam_m", "adam_v", and with
+   normalize = 2 "ppo_obs_n" [n_envs, ld] (the rows the last grl_observe normalised).  Every other entry point returns
+   GRL_ERR_STATE on a PPO handle before anything moves (normalize = 2: but for grl_observe and the three statistics calls).
+   grl_act is the same on both kinds of handle: the observations handed to it are taken as normalised. */
 
 /* ---------------------------------------------------------------------------------------------------------------------
    TRPO (GRL_ALGO_TRPO): stable-baselines 2.10.1 TRPO with the actor-critic MlpPolicy on a Box action space, as
@@ -417,7 +436,8 @@ int grl_ppo_get_metrics(grl_handle h, float* out, int cap);
    order are those of a PPO handle.  The policy variables are those whose name contains "/pi"; every other trainable variable
    belongs to the value fit.
    Rollout: grl_ppo_step / grl_ppo_rewards / grl_ppo_finish work on a TRPO handle with n_envs = 1 (done = episode_start of the
-   step; grl_ppo_finish forms V(last obs), GAE and tdlamret).  grl_ppo_train / grl_ppo_get_metrics are GRL_ERR_STATE. */
+   step; grl_ppo_finish forms V(last obs), GAE and tdlamret).  normalize = 2, grl_observe, the statistics calls and obs == NULL
+   work as on a PPO handle (one row).  grl_ppo_train / grl_ppo_get_metrics are GRL_ERR_STATE. */
 typedef struct grl_trpo_config {
   int32_t n_steps;                         /* T = timesteps_per_batch, 1 .. 65536 */
   int32_t n_vf_layers; int32_t vf_layers[GRL_MAX_LAYERS];
@@ -427,6 +447,7 @@ typedef struct grl_trpo_config {
   int32_t vf_batch;                        /* rows of a value minibatch (stable-baselines: 128); must equal grl_config.batch_size */
   float lam, max_kl, cg_damping, ent_coef;
   float adam_eps;                          /* 1e-8 */
+  double norm_eps64;                       /* as grl_ppo_config.norm_eps64 */
 } grl_trpo_config;
 int grl_trpo_query_sizes(const grl_config* cfg, const grl_trpo_config* trpo, grl_sizes* out);
 int grl_trpo_create(const grl_config* cfg, const grl_trpo_config* trpo, const grl_buffers* bufs, grl_handle* out);
