@@ -1746,5 +1746,6 @@ int grl_bc_end(grl_handle h) {
 }
 
 #include "checkpoint.inl"
+#include "ppo_checkpoint.inl"
 
 }  // extern "C"

@@ -95,6 +95,7 @@ EXPORTS = [
     "grl_allreduce_init", "grl_allreduce_connect", "grl_train_step_allreduce", "grl_allreduce_status", "grl_allreduce_set_overlap", "grl_allreduce_set_mode", "grl_allreduce_set_timeout",
     "grl_allreduce_disconnect",
     "grl_state_size", "grl_state_export", "grl_state_import", "grl_replay_segments",
+    "grl_ppo_state_size", "grl_ppo_state_export", "grl_ppo_state_import",
     "grl_ppo_query_sizes", "grl_ppo_create", "grl_ppo_step", "grl_ppo_rewards", "grl_ppo_finish", "grl_ppo_train",
     "grl_ppo_get_metrics",
     "grl_trpo_query_sizes", "grl_trpo_create", "grl_trpo_update", "grl_trpo_get_metrics", "grl_trpo_debug_fvp",
@@ -187,6 +188,10 @@ def load_library(path=None):
     lib.grl_state_export.restype = i64
     lib.grl_state_import.argtypes = [vp, vp, C.c_size_t]
     lib.grl_replay_segments.argtypes = [vp, i32, C.POINTER(GrlSegment)]
+    lib.grl_ppo_state_size.argtypes = [vp, C.POINTER(C.c_size_t)]
+    lib.grl_ppo_state_export.argtypes = [vp, vp, C.c_size_t]
+    lib.grl_ppo_state_export.restype = i64
+    lib.grl_ppo_state_import.argtypes = [vp, vp, C.c_size_t]
     lib.grl_ppo_query_sizes.argtypes = [C.POINTER(GrlConfig), C.POINTER(GrlPpoConfig), C.POINTER(GrlSizes)]
     lib.grl_ppo_create.argtypes = [C.POINTER(GrlConfig), C.POINTER(GrlPpoConfig), C.POINTER(GrlBuffers), C.POINTER(vp)]
     lib.grl_ppo_step.argtypes = [vp, f32p, f32p, f32p, f32p, f32p, f32p]

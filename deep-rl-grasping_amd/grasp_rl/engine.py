@@ -902,6 +902,40 @@ class PpoEngine(SacEngine):
         """Empty the rollout (slot 0 is next), whatever state a stopped run left it in."""
         self.store("ppo_slots", [0, 0, 0])
 
+    # ------------------------------------------------------------------ checkpoint / resume (DESIGN.md section 9)
+    # save_state / load_state are SacEngine's: same directory protocol, meta.json, state.bin, handle.bin and extra files.  What
+    # differs is the blob (grl_ppo_state_*) and the replay arena, which holds the rollout and is written whole as replay_0.bin.
+    def export_state(self):
+        """The handle's host-side state as bytes (grl_ppo_state_export; synchronises the stream): the rollout cursor, the parity
+        of the statistics' double buffer and the rows the last ``observe`` normalised."""
+        size = C.c_size_t()
+        check(self.lib, self.lib.grl_ppo_state_size(self.h, C.byref(size)))
+        buf = C.create_string_buffer(max(1, size.value))
+        n = check(self.lib, self.lib.grl_ppo_state_export(self.h, buf, size.value))
+        return buf.raw[:n]
+
+    def import_state(self, blob):
+        check(self.lib, self.lib.grl_ppo_state_import(self.h, C.c_char_p(bytes(blob)), len(blob)))
+
+    def replay_segments(self):
+        """One array saved whole: the rollout arena of R = n_envs * n_steps rows (no ring, no stored-rows prefix;
+        grl_replay_segments stays undefined on these handles)."""
+        return [(0, 4 * int(self.replay.shape[0]), 0)]
+
+    def rollout_cursor(self):
+        """(slots written, slots closed, finished) as grl_ppo_state_export reports them."""
+        blob = self.export_state()
+        second = C.sizeof(self.trpo) if hasattr(self, "trpo") else C.sizeof(self.ppo)
+        off = C.sizeof(_capi.GrlStateHeader) + C.sizeof(_capi.GrlConfig) + second
+        written, closed, finished = np.frombuffer(blob, np.int32, 3, off)
+        return int(written), int(closed), bool(finished)
+
+    def _load_state(self, dirpath):
+        meta = super()._load_state(dirpath)
+        if not meta.get("include_replay"):      # the rollout stayed out: an empty one (cursor 0 / 0 / not finished)
+            self.reset_rollout()
+        return meta
+
     def place_rollout(self, obs, act, val, nlp, rew, done):
         """Parity tests: a whole rollout through grl_debug_store.  Arrays are [n_envs, n_steps, ...] (row = env * n_steps + t)."""
         o = np.zeros((self.R, self.ldo), np.float32)

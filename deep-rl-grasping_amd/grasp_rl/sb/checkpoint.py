@@ -1,9 +1,10 @@
-"""Full-state checkpoints of the ``SAC`` / ``DQN`` / ``BDQ`` models: the stable-baselines zip plus, next
-to it, a directory with the engine's training state (``engine.save_state``: parameters, optimiser moments and counters,
-device RNG position, running statistics, replay ring, priorities) and ``host.pkl``, the few things this host loop keeps
-itself: ``num_timesteps``, ``n_updates``, the exploration generator, the schedules' reference length, the VecNormalize
-statistics and returns.  A model restored from it continues with ``learn(n, reset_num_timesteps=False)`` as if ``learn`` had
-never returned.
+"""Full-state checkpoints of the ``SAC`` / ``DQN`` / ``BDQ`` / ``PPO2`` / ``TRPO`` models: the
+stable-baselines zip plus, next to it, a directory with the engine's training state (``engine.save_state``: parameters, optimiser
+moments and counters, device RNG position, running statistics, replay ring, priorities -- PPO2 / TRPO: the rollout) and
+``host.pkl``, the few things this host loop keeps itself: ``num_timesteps``, ``n_updates``, the exploration generator, the
+schedules' reference length, the VecNormalize statistics and returns -- PPO2 / TRPO: the permutation generator, the index of the
+update in progress and what the loop holds between two engine calls (``_on_policy_host_state``).  A model restored from it
+continues with ``learn(n, reset_num_timesteps=False)`` as if ``learn`` had never returned.
 
 ``model.save_checkpoint(path)`` / ``Model.load_checkpoint(path, env)`` do this explicitly.  For scripts that only know
 ``model.save`` / ``Model.load`` -- the reference's callbacks and its ``--load_dir`` -- GRL_CHECKPOINT_STATE=1 makes ``save``
@@ -49,7 +50,37 @@ def _rms_state(rms):
     return {"mean": np.array(rms.mean, np.float64), "var": np.array(rms.var, np.float64), "count": rms.count}     # count: type kept
 
 
+def _vn_state(vn):
+    vn.pull_device_stats()          # attached: the device holds the observation statistics
+    return {"obs_rms": _rms_state(vn.obs_rms), "ret_rms": _rms_state(vn.ret_rms),
+            "ret": np.array(vn.ret, np.float64), "clip_obs": vn.clip_obs, "clip_reward": vn.clip_reward,
+            "gamma": vn.gamma, "epsilon": vn.epsilon, "norm_obs": vn.norm_obs, "norm_reward": vn.norm_reward}
+
+
+def _vn_restore(vn, vs):
+    for rms, s in ((vn.obs_rms, vs["obs_rms"]), (vn.ret_rms, vs["ret_rms"])):
+        rms.mean, rms.var, rms.count = s["mean"].copy(), s["var"].copy(), s["count"]
+    vn.ret = vs["ret"].copy()
+    vn.clip_obs, vn.clip_reward = vs["clip_obs"], vs["clip_reward"]
+
+
+def _on_policy_host_state(model, include_replay):
+    """host.pkl of a PPO2 / TRPO model: the same format number and the keys ``_read_host`` checks, then what these loops keep.
+    ``loop`` is the model's own record of the rollout in progress (``_loop_snapshot``: the flags the next step or finish takes,
+    the rewards of a slot that is written and not closed, the episode infos and value / reward rows collected so far, the index
+    of the update in progress; TRPO: its generator's counters), ``extra`` what else the model class carries."""
+    vn = model._vec_normalize_env
+    return {"format": HOST_FORMAT, "model": type(model).__name__, "world": 1, "include_replay": bool(include_replay),
+            "num_timesteps": int(model.num_timesteps), "n_updates": int(getattr(model, "n_updates", 0)),
+            "rng": model._rng.get_state(),          # np.random.RandomState: draws the permutations
+            "schedule_total": model._schedule_total, "ep_info_buf": list(model.ep_info_buf),
+            "vec_normalize": None if vn is None else _vn_state(vn),
+            "loop": model._loop_snapshot(include_replay), "extra": model._host_extra()}
+
+
 def host_state(model, include_replay):
+    if getattr(model, "_on_policy", False):
+        return _on_policy_host_state(model, include_replay)
     rt = model._dp_rt
     st = {"format": HOST_FORMAT, "model": type(model).__name__, "world": 1 if rt is None else rt.world,
           "include_replay": bool(include_replay), "num_timesteps": int(model.num_timesteps), "n_updates": int(model.n_updates),
@@ -64,10 +95,7 @@ def host_state(model, include_replay):
         st["action_space_rng"] = (gen[0], pickle.dumps(gen[1]))
     vn = model._vec_normalize_env
     if vn is not None:
-        vn.pull_device_stats()          # attached: the device holds the observation statistics
-        st["vec_normalize"] = {"obs_rms": _rms_state(vn.obs_rms), "ret_rms": _rms_state(vn.ret_rms),
-                               "ret": np.array(vn.ret, np.float64), "clip_obs": vn.clip_obs, "clip_reward": vn.clip_reward,
-                               "gamma": vn.gamma, "epsilon": vn.epsilon, "norm_obs": vn.norm_obs, "norm_reward": vn.norm_reward}
+        st["vec_normalize"] = _vn_state(vn)
     return st
 
 
@@ -132,6 +160,8 @@ def restore_state(model, path, required):
             return False
         raise GrlError(why)
     model.engine.load_state(d)
+    if getattr(model, "_on_policy", False):
+        return _restore_on_policy(model, st)
     model.num_timesteps, model.n_updates = st["num_timesteps"], st["n_updates"]
     model._rng = np.random.default_rng()
     model._rng.bit_generator.state = st["rng"]
@@ -143,14 +173,45 @@ def restore_state(model, path, required):
         setattr(model.action_space, st["action_space_rng"][0], pickle.loads(st["action_space_rng"][1]))
     vn, vs = model._vec_normalize_env, st["vec_normalize"]
     if vn is not None:
-        for rms, s in ((vn.obs_rms, vs["obs_rms"]), (vn.ret_rms, vs["ret_rms"])):
-            rms.mean, rms.var, rms.count = s["mean"].copy(), s["var"].copy(), s["count"]
-        vn.ret = vs["ret"].copy()
-        vn.clip_obs, vn.clip_reward = vs["clip_obs"], vs["clip_reward"]
+        _vn_restore(vn, vs)
     # consumed by the next learn(reset_num_timesteps=False): continue in place (no reset statistics, no new schedules)
     model._resume = {"schedule_total": st["schedule_total"], "ret": None if vs is None else vs["ret"].copy()}
     model._restored_norm_stamp()
     return True
+
+
+def _restore_on_policy(model, st):
+    """The host half of a PPO2 / TRPO restore (the engine is loaded): counters, the permutation generator, episode statistics,
+    VecNormalize, and the record of the rollout in progress for the next ``learn(reset_num_timesteps=False)``."""
+    from collections import deque
+    model.num_timesteps = st["num_timesteps"]
+    if hasattr(model, "n_updates"):
+        model.n_updates = st["n_updates"]
+    model._rng = np.random.RandomState()
+    model._rng.set_state(st["rng"])
+    model.ep_info_buf = deque(st["ep_info_buf"], maxlen=100)
+    vn, vs = model._vec_normalize_env, st["vec_normalize"]
+    if vn is not None:
+        _vn_restore(vn, vs)
+    model._set_host_extra(st["extra"])
+    model._loop = None
+    model._resume = {"schedule_total": st["schedule_total"], "ret": None if vs is None else vs["ret"].copy(), "loop": st["loop"]}
+    return True
+
+
+def _refuse_other_model(cls, path):
+    """Before the zip is read: a state directory written by another model class is refused by name (its zip need not even hold
+    this class's parameters)."""
+    d = _find(path, None)
+    if d is None:
+        return
+    try:
+        with open(os.path.join(d, HOST_FILE), "rb") as f:
+            name = pickle.load(f).get("model")
+    except (OSError, pickle.UnpicklingError, EOFError, AttributeError):
+        return          # restore_state says what is wrong with it
+    if name != cls.__name__:
+        raise GrlError("checkpoint of a %s model loaded into %s" % (name, cls.__name__))
 
 
 class CheckpointMixin:
@@ -171,6 +232,7 @@ class CheckpointMixin:
 
     @classmethod
     def load_checkpoint(cls, path, env=None, **kwargs):
+        _refuse_other_model(cls, path)
         model = cls._load_zip(path, env=env, **kwargs)
         restore_state(model, path, required=True)
         return model

@@ -10,8 +10,10 @@ permutation per epoch from the model's seeded generator, episode statistics and 
 
 Scope: the actor-critic ``MlpPolicy`` (two tanh towers, ``net_arch=[dict(vf=[...], pi=[...])]``) on ``Box`` actions, observations
 of any rank flattened in C order and not divided by 255, N environments (a VecEnv, or GRL_NUM_ENVS around the script's
-one-factory DummyVecEnv).  Everything else says what it refuses.  ``model.save`` writes the stable-baselines zip only
-(GRL_CHECKPOINT_STATE is not defined for PPO2).
+one-factory DummyVecEnv).  Everything else says what it refuses.  ``model.save`` writes the stable-baselines zip only;
+``save_checkpoint`` / ``load_checkpoint`` -- or GRL_CHECKPOINT_STATE=1 behind ``save`` / ``load`` -- keep the full training state
+next to it (sb/checkpoint.py), and ``learn(n, reset_num_timesteps=False)`` on a restored model continues the rollout that was
+in progress (``_resumed_start``: the open slot, the seam).
 
 VecNormalize: stable-baselines normalises a PPO observation once, at step time, with the statistics right after that step's
 update, and the rollout stores the normalised row.  By default the wrapper does that on the host.  ``device_norm=True`` (or
@@ -33,6 +35,7 @@ from . import logger
 from . import save_util
 from . import spaces as sp
 from .callbacks import as_callback
+from .checkpoint import CheckpointMixin
 from .vec_env import DummyVecEnv, VecEnv, expand_training_env, unwrap_vec_normalize
 
 
@@ -65,7 +68,14 @@ def _normalize_kwargs(vn):
     return dict(normalize=2, clip_obs=float(vn.clip_obs), norm_eps=float(vn.epsilon))
 
 
-class PPO2:
+def _episodes(infos):
+    return [info["episode"] for info in infos if isinstance(info, dict) and info.get("episode") is not None]
+
+
+class PPO2(CheckpointMixin):
+    _on_policy = True      # sb/checkpoint.py: host.pkl of the on-policy models
+    _dp_rt = None          # one replica
+    _loop = None           # the running (or last) learn's record of its rollout: what a checkpoint keeps of the host loop
     _engine_factory = staticmethod(lambda cfg, ppo, device: PpoEngine(cfg, ppo, device=device))
 
     def __init__(self, policy, env, gamma=0.99, n_steps=128, ent_coef=0.01, learning_rate=2.5e-4, vf_coef=0.5,
@@ -200,14 +210,18 @@ class PPO2:
         if reset_num_timesteps:
             self.num_timesteps = 0
         lr_fn = _constfn(self.learning_rate)
+        # a model restored from a checkpoint continues in place (sb/checkpoint.py): the rollout, the update index and the
+        # learning-rate schedule's length stand where the saved run left them
+        resume = self._take_resume(reset_num_timesteps)
+        self._schedule_total = total_timesteps if resume is None else (resume["schedule_total"] or total_timesteps)
         device_norm = self._resolve_device_norm(callback)      # (decided from the callback the USER handed over)
         callback = as_callback(callback)
         callback.init_callback(self)
         # stable-baselines hands callbacks a FileWriter when tensorboard_log is set, None otherwise
         writer = logger.SummaryWriter(self.tensorboard_log, tb_log_name) if self.tensorboard_log else None
         try:
-            self._attach_device_norm(device_norm)
-            self._learn_loop(total_timesteps, callback, log_interval, writer, lr_fn)
+            self._attach_device_norm(device_norm, upload=resume is None)      # restored: the device holds the statistics already
+            self._learn_loop(total_timesteps, callback, log_interval, writer, lr_fn, resume)
         finally:
             self._detach_device_norm()
             if writer is not None:
@@ -219,12 +233,15 @@ class PPO2:
         from .sac import resolve_device_norm
         return self.device_norm is not False and resolve_device_norm(self.device_norm, user_callback, None, None)
 
-    def _attach_device_norm(self, device_norm):
+    def _attach_device_norm(self, device_norm, upload=True):
         vn = self._vec_normalize_env
         if not device_norm or vn is None or not vn.norm_obs:
             return
         if self.engine.cfg.normalize == 2:
-            vn.attach_device(self.engine)
+            if not upload:      # ... unless the saved run kept them on the host: then the wrapper's restored copy is the newer one
+                mean, var, count = self.engine.get_obs_stats(tuple(vn.obs_rms.mean.shape))
+                upload = not (np.array_equal(mean, vn.obs_rms.mean) and np.array_equal(var, vn.obs_rms.var) and count == vn.obs_rms.count)
+            vn.attach_device(self.engine, upload=upload)
         else:      # a zip loaded without env and given a normalised env later: the device plan holds no statistics
             logger.warn("%s: device_norm needs a model built on the VecNormalize env (pass env= to the constructor or to load); "
                         "this one was built without it -> VecNormalize stays on the host" % type(self).__name__)
@@ -244,32 +261,93 @@ class PPO2:
             return None
         return obs.reshape(n, -1)
 
-    def _learn_loop(self, total_timesteps, callback, log_interval, writer, lr_fn):
+    # ------------------------------------------------------------------ checkpoint / resume (sb/checkpoint.py)
+    def _loop_snapshot(self, include_replay=True):
+        """What the loop holds between two engine calls, as host.pkl keeps it (None before the first ``learn``).  A callback
+        saves between ``engine.step`` and ``engine.rewards``: the slot is then written and not closed, its rewards are in
+        ``rewards`` already and its infos have not been looked at yet -- their episodes are taken in here."""
+        lp = self._loop
+        if lp is None:
+            return None
+        written, closed, _ = self.engine.rollout_cursor()
+        out = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in lp.items() if k not in ("infos", "ep_infos")}
+        out["ep_infos"] = list(lp["ep_infos"]) + (_episodes(lp["infos"]) if written == closed + 1 else [])
+        return out
+
+    def _host_extra(self):
+        return {}
+
+    def _set_host_extra(self, extra):
+        pass
+
+    def _resumed_start(self, resume):
+        """The seam of a continued run: (observations, cursor, the saved loop record or None).  The environment is the one thing
+        a checkpoint cannot hold: it is reset ONCE, its first observations normalised with the restored statistics and not
+        counted into them (``reset_restored``; device path: uploaded without a statistics update), and every sub-environment
+        starts an episode -- the caller's flags are 1 whatever the checkpoint says, so neither the value bootstrap nor GAE
+        crosses the seam.  The record is None when the rollout stayed out of the checkpoint (an empty one starts here)."""
+        vn, eng = self._vec_normalize_env, self.engine
+        obs = np.asarray(vn.reset_restored(resume["ret"]) if vn is not None else self.env.reset(), np.float32)
+        written, closed, finished = eng.rollout_cursor()
+        saved = resume["loop"]
+        if written > 0 and (saved is None or "rewards" not in saved):      # (a rollout no learn of this class wrote)
+            eng.reset_rollout()
+            written = closed = 0
+        return obs, (written, closed, finished), (saved if written > 0 else None)
+
+    def _learn_loop(self, total_timesteps, callback, log_interval, writer, lr_fn, resume=None):
         eng, N, T = self.engine, self.n_envs, self.n_steps
-        eng.reset_rollout()      # (a run a callback stopped mid-rollout left a slot open)
-        obs = np.asarray(self.env.reset(), np.float32)
-        dones = np.zeros(N, np.float32)
-        t_first_start = time.time()
         n_updates = total_timesteps // self.n_batch
+        saved, finished = None, False
+        if resume is None:
+            eng.reset_rollout()      # (a run a callback stopped mid-rollout left a slot open)
+            obs = np.asarray(self.env.reset(), np.float32)
+            dones = np.zeros(N, np.float32)
+            updates, sched_updates = range(1, n_updates + 1), n_updates
+        else:
+            # the restored rollout goes on: the open slot is closed with the restored rewards, the remaining slots are filled,
+            # the update index and the schedule's length are the saved run's, and the run ends where num_timesteps has grown by
+            # total_timesteps -- at the rollout boundaries the uninterrupted run has (a rollout that would end later is not begun)
+            obs, (written, closed, finished), saved = self._resumed_start(resume)
+            dones = np.ones(N, np.float32)
+            first = (resume["loop"] or {}).get("update", 1)
+            left = total_timesteps - (T - written) * N
+            updates = range(first, first + (0 if left < 0 else 1 + left // self.n_batch))
+            sched_updates = max(1, int(resume["schedule_total"] or total_timesteps) // self.n_batch)
+        lp = self._loop = {"update": updates.start, "dones": dones, "infos": (), "ep_infos": [],
+                           "values": np.zeros((T, N), np.float32), "rewards": np.zeros((T, N), np.float32)}
+        t_first_start = time.time()
         callback.on_training_start(locals(), globals())
-        for update in range(1, n_updates + 1):
+        for update in updates:
             t_start = time.time()
-            frac = 1.0 - (update - 1.0) / n_updates
+            frac = 1.0 - (update - 1.0) / sched_updates
             lr_now = float(lr_fn(frac))
-            callback.on_rollout_start()
+            if saved is None:
+                values, rewards, ep_infos = np.zeros((T, N), np.float32), np.zeros((T, N), np.float32), []
+                step0, reopened = 0, False
+            else:      # the rollout the checkpoint was taken in
+                values, rewards, ep_infos = saved["values"].copy(), saved["rewards"].copy(), list(saved["ep_infos"])
+                step0, reopened, saved = closed, written == closed + 1, None
+            lp.update(update=update, values=values, rewards=rewards, ep_infos=ep_infos, infos=())
+            if step0 == 0 and not reopened:
+                callback.on_rollout_start()
             # ---- Runner._run: n_steps policy steps; what the update needs stays on the device
-            values, rewards, ep_infos, go_on = np.zeros((T, N), np.float32), np.zeros((T, N), np.float32), [], True
-            for step in range(T):
-                actions, values[step], neglogpacs = eng.step(self._rows(obs, N), dones)
-                clipped_actions = self._clip(actions.reshape((N,) + tuple(self.action_space.shape)))
-                obs, rew, done, infos = self.env.step(clipped_actions)
-                obs, dones = np.asarray(obs, np.float32), np.asarray(done, np.float32).reshape(N)
-                rewards[step] = np.asarray(rew, np.float32).reshape(N)
-                self.num_timesteps += N
-                callback.update_locals(locals())
-                if callback.on_step() is False:
-                    go_on = False
-                    break
+            go_on = True
+            for step in range(step0, T):
+                if reopened:      # written before the save, its rewards and infos taken then: only closing it is left
+                    reopened, infos = False, ()
+                else:
+                    actions, values[step], neglogpacs = eng.step(self._rows(obs, N), dones)
+                    clipped_actions = self._clip(actions.reshape((N,) + tuple(self.action_space.shape)))
+                    obs, rew, done, infos = self.env.step(clipped_actions)
+                    obs, dones = np.asarray(obs, np.float32), np.asarray(done, np.float32).reshape(N)
+                    rewards[step] = np.asarray(rew, np.float32).reshape(N)
+                    self.num_timesteps += N
+                    lp["dones"], lp["infos"] = dones, infos
+                    callback.update_locals(locals())
+                    if callback.on_step() is False:
+                        go_on = False
+                        break
                 for info in infos:
                     maybe = info.get("episode") if isinstance(info, dict) else None
                     if maybe is not None:
@@ -277,8 +355,10 @@ class PPO2:
                 eng.rewards(rewards[step])
             if not go_on:
                 break
-            eng.finish(self._rows(obs, N), dones)      # (device path: the rows serve the next rollout's first step as well)
-            callback.on_rollout_end()
+            if not finished:      # (a checkpoint taken in on_rollout_end holds the advantages already)
+                eng.finish(self._rows(obs, N), dones)      # (device path: the rows serve the next rollout's first step as well)
+                callback.on_rollout_end()
+            finished = False
             self.ep_info_buf.extend(ep_infos)
             # ---- noptepochs epochs over nminibatches consecutive slices of a fresh permutation each
             eng.set_learning_rate(lr_now)
@@ -286,6 +366,7 @@ class PPO2:
             returns = eng.fetch("ppo_ret", (N, T)).T if want_log else None
             perm = np.stack([self._rng.permutation(self.n_batch) for _ in range(self.noptepochs)]).astype(np.int32)
             eng.train(perm)
+            lp["update"] = update + 1      # (the rollout is empty: the next one belongs to the next update)
             self.n_updates += self.noptepochs * self.nminibatches
             if writer is not None:
                 self._write_summary(writer, eng.metrics().mean(axis=0), lr_now)
@@ -334,7 +415,7 @@ class PPO2:
     _SAVED = ("gamma", "n_steps", "vf_coef", "ent_coef", "max_grad_norm", "lam", "nminibatches", "noptepochs", "cliprange",
               "cliprange_vf", "verbose", "n_cpu_tf_sess", "seed", "policy_kwargs")
 
-    def save(self, save_path, cloudpickle=False):
+    def _save_zip(self, save_path):
         data = {k: getattr(self, k) for k in self._SAVED}
         data["learning_rate"] = float(_constfn(self.learning_rate)(1.0))
         data.update(observation_space=self.observation_space, action_space=self.action_space, policy=self.policy,
@@ -342,7 +423,7 @@ class PPO2:
         return save_util.save_to_zip(save_path, data, self.get_parameters())
 
     @classmethod
-    def load(cls, load_path, env=None, custom_objects=None, **kwargs):
+    def _load_zip(cls, load_path, env=None, custom_objects=None, **kwargs):
         data, params = save_util.load_from_zip(load_path)
         policy = data.get("policy")
         model = cls(policy=policy if (isinstance(policy, (type, str)) and policy is not None) else "MlpPolicy", env=None,

@@ -16,8 +16,10 @@ re-evaluates only its value afterwards.  Here ``finish`` evaluates V(last observ
 updated policy.
 
 Scope: the actor-critic ``MlpPolicy`` (two tanh towers, ``net_arch=[dict(vf=[...], pi=[...])]``) on ``Box`` actions, observations
-of any rank flattened in C order and not divided by 255, one environment (GRL_NUM_ENVS does not fan a TRPO env out).  GAIL, data
-parallelism and GRL_CHECKPOINT_STATE are not defined for TRPO.  Everything else says what it refuses.
+of any rank flattened in C order and not divided by 255, one environment (GRL_NUM_ENVS does not fan a TRPO env out).  GAIL and data
+parallelism are not defined for TRPO.  Everything else says what it refuses.  ``save_checkpoint`` / ``load_checkpoint`` -- or
+GRL_CHECKPOINT_STATE=1 behind ``save`` / ``load`` -- keep the full training state next to the zip, and
+``learn(n, reset_num_timesteps=False)`` on a restored model continues the batch that was in progress, as PPO2 does (ppo2.py).
 
 VecNormalize works on the host by default; ``device_norm=True`` (GRL_DEVICE_NORM=1 / auto; unset means off) keeps its observation
 statistics on the device while ``learn`` runs, exactly as ``PPO2(device_norm=...)`` does (ppo2.py): one ``engine.observe`` per
@@ -141,42 +143,90 @@ class TRPO(PPO2):
         total_timesteps = int(total_timesteps)
         if reset_num_timesteps:
             self.num_timesteps = 0
+        resume = self._take_resume(reset_num_timesteps)      # a restored model continues in place (sb/checkpoint.py)
+        self._schedule_total = total_timesteps if resume is None else (resume["schedule_total"] or total_timesteps)
         device_norm = self._resolve_device_norm(callback)      # (decided from the callback the USER handed over)
         callback = as_callback(callback)
         callback.init_callback(self)
         writer = logger.SummaryWriter(self.tensorboard_log, tb_log_name) if self.tensorboard_log else None
         try:
-            self._attach_device_norm(device_norm)
-            self._learn_loop(total_timesteps, callback, log_interval, writer, None)
+            self._attach_device_norm(device_norm, upload=resume is None)      # restored: the device holds the statistics already
+            self._learn_loop(total_timesteps, callback, log_interval, writer, None, resume)
         finally:
             self._detach_device_norm()
             if writer is not None:
                 writer.close()
         return self
 
-    def _learn_loop(self, total_timesteps, callback, log_interval, writer, lr_fn):
+    # ------------------------------------------------------------------ checkpoint / resume (sb/checkpoint.py)
+    def _host_extra(self):
+        """What this class carries beside PPO2's host state: the episode statistics of the log line and oldpi/* of the zip (the
+        device's snapshot lives in scratch a checkpoint does not hold, so it is fetched here)."""
+        old = self._oldpi
+        if self._updated:
+            snap, params = self.engine.fetch("trpo_theta_old"), self.get_parameters()
+            old = OrderedDict((n, snap[off:off + numel].reshape(shape).copy() if trainable else params[n])
+                              for n, off, numel, shape, trainable in self.engine.table)
+        return {"len_buffer": list(self.len_buffer), "rew_buffer": list(self.rew_buffer), "episodes_so_far": self.episodes_so_far,
+                "oldpi": old}
+
+    def _set_host_extra(self, extra):
+        self.len_buffer, self.rew_buffer = deque(extra["len_buffer"], maxlen=40), deque(extra["rew_buffer"], maxlen=40)
+        self.episodes_so_far = extra["episodes_so_far"]
+        self._oldpi, self._updated = extra["oldpi"], False
+
+    def _learn_loop(self, total_timesteps, callback, log_interval, writer, lr_fn, resume=None):
         eng, T = self.engine, self.timesteps_per_batch
-        eng.reset_rollout()      # (a run a callback stopped mid-batch left a slot open)
-        obs = np.asarray(self.env.reset(), np.float32)
+        saved, finished, written, closed = None, False, 0, 0
         episode_start = np.ones(1, np.float32)
         cur_ep_ret, cur_ep_len = 0.0, 0
         timesteps_so_far, iters_so_far, t_start = 0, 0, time.time()
+        if resume is None:
+            eng.reset_rollout()      # (a run a callback stopped mid-batch left a slot open)
+            obs = np.asarray(self.env.reset(), np.float32)
+            end = total_timesteps
+        else:
+            # the restored batch goes on (ppo2.py: _resumed_start): the generator's counters are the saved run's, and the run
+            # ends where its timesteps_so_far has grown by total_timesteps; episode_start is 1 at the seam
+            obs, (written, closed, finished), saved = self._resumed_start(resume)
+            st = resume["loop"] or {}
+            timesteps_so_far, iters_so_far = st.get("timesteps_so_far", 0), st.get("iters_so_far", 0)
+            if saved is not None and written == closed + 1:      # (no open slot: the seam cuts the episode, the counters start over)
+                cur_ep_ret, cur_ep_len = saved["cur_ep_ret"], saved["cur_ep_len"]
+            end = timesteps_so_far + total_timesteps
+        lp = self._loop = {"update": iters_so_far + 1, "dones": episode_start, "infos": (), "ep_infos": [], "done": False,
+                           "values": np.zeros(T, np.float32), "rewards": np.zeros(T, np.float32), "ep_rets": [], "ep_lens": [],
+                           "cur_ep_ret": cur_ep_ret, "cur_ep_len": cur_ep_len, "timesteps_so_far": timesteps_so_far,
+                           "iters_so_far": iters_so_far}
         callback.on_training_start(locals(), globals())
-        while timesteps_so_far < total_timesteps:
-            callback.on_rollout_start()
+        while timesteps_so_far < end:
+            if saved is None:
+                vpreds, rewards, ep_rets, ep_lens, ep_infos = np.zeros(T, np.float32), np.zeros(T, np.float32), [], [], []
+                step0, reopened = 0, False
+            else:      # the batch the checkpoint was taken in
+                vpreds, rewards, ep_infos = saved["values"].copy(), saved["rewards"].copy(), list(saved["ep_infos"])
+                ep_rets, ep_lens, done = list(saved["ep_rets"]), list(saved["ep_lens"]), saved["done"]
+                step0, reopened, saved = closed, written == closed + 1, None
+            lp.update(values=vpreds, rewards=rewards, ep_infos=ep_infos, ep_rets=ep_rets, ep_lens=ep_lens, infos=())
+            if step0 == 0 and not reopened:
+                callback.on_rollout_start()
             # ---- traj_segment_generator: T policy steps of the one environment; what the update needs stays on the device
-            vpreds, rewards, ep_rets, ep_lens, ep_infos, go_on = np.zeros(T, np.float32), np.zeros(T, np.float32), [], [], [], True
-            for step in range(T):
-                actions, vpred, _ = eng.step(self._rows(obs, 1), episode_start)
-                vpreds[step] = vpred[0]
-                clipped_actions = self._clip(actions.reshape((1,) + tuple(self.action_space.shape)))
-                obs, rew, done, infos = self.env.step(clipped_actions)
-                obs = np.asarray(obs, np.float32)
-                rewards[step] = float(np.asarray(rew).reshape(-1)[0])
-                callback.update_locals(locals())
-                if callback.on_step() is False:
-                    go_on = False
-                    break
+            go_on = True
+            for step in range(step0, T):
+                if reopened:      # written before the save, its reward, flag and infos taken then: only closing it is left
+                    infos = ()
+                else:
+                    actions, vpred, _ = eng.step(self._rows(obs, 1), episode_start)
+                    vpreds[step] = vpred[0]
+                    clipped_actions = self._clip(actions.reshape((1,) + tuple(self.action_space.shape)))
+                    obs, rew, done, infos = self.env.step(clipped_actions)
+                    obs = np.asarray(obs, np.float32)
+                    rewards[step] = float(np.asarray(rew).reshape(-1)[0])
+                    lp.update(done=bool(np.asarray(done).reshape(-1)[0]), infos=infos, cur_ep_ret=cur_ep_ret, cur_ep_len=cur_ep_len)
+                    callback.update_locals(locals())
+                    if callback.on_step() is False:
+                        go_on = False
+                        break
                 eng.rewards(rewards[step:step + 1])
                 cur_ep_ret += float(rewards[step])
                 cur_ep_len += 1
@@ -191,10 +241,16 @@ class TRPO(PPO2):
                     ep_lens.append(cur_ep_len)
                     cur_ep_ret, cur_ep_len = 0.0, 0
                     obs = np.asarray(self.env.reset(), np.float32)
+                elif reopened:      # the seam cuts the episode the saved run was in: the fresh environment starts one
+                    episode_start[0], cur_ep_ret, cur_ep_len = 1.0, 0.0, 0
+                reopened = False
             if not go_on:
                 break
-            eng.finish(self._rows(obs, 1), episode_start)      # nextvpred = V(obs_T) * (1 - episode_start_T), GAE, tdlamret
-            callback.on_rollout_end()
+            lp.update(cur_ep_ret=cur_ep_ret, cur_ep_len=cur_ep_len)
+            if not finished:      # (a checkpoint taken in on_rollout_end holds the advantages already)
+                eng.finish(self._rows(obs, 1), episode_start)      # nextvpred = V(obs_T) * (1 - episode_start_T), GAE, tdlamret
+                callback.on_rollout_end()
+            finished = False
             self.ep_info_buf.extend(ep_infos)
             want_log = self.verbose >= 1
             tdlamret = eng.fetch("ppo_ret", (T,)) if want_log else None
@@ -205,6 +261,7 @@ class TRPO(PPO2):
             timesteps_so_far += T
             self.num_timesteps += T
             iters_so_far += 1
+            lp.update(update=iters_so_far + 1, timesteps_so_far=timesteps_so_far, iters_so_far=iters_so_far)
             self.episodes_so_far += len(ep_lens)
             self.len_buffer.extend(ep_lens)
             self.rew_buffer.extend(ep_rets)
@@ -242,7 +299,7 @@ class TRPO(PPO2):
         # (a zip carries oldpi/* behind model/*: the engine keeps the old policy only for the length of an update)
         super().load_parameters(OrderedDict((n, a) for n, a in params.items() if not n.startswith("oldpi/")), exact_match=exact_match)
 
-    def save(self, save_path, cloudpickle=False):
+    def _save_zip(self, save_path):
         data = {k: getattr(self, k) for k in self._SAVED}
         data.update(observation_space=self.observation_space, action_space=self.action_space, policy=self.policy, n_envs=self.n_envs,
                     _vectorize_action=False)
@@ -257,7 +314,7 @@ class TRPO(PPO2):
         return save_util.save_to_zip(save_path, data, params)
 
     @classmethod
-    def load(cls, load_path, env=None, custom_objects=None, **kwargs):
+    def _load_zip(cls, load_path, env=None, custom_objects=None, **kwargs):
         data, params = save_util.load_from_zip(load_path)
         policy = data.get("policy")
         model = cls(policy=policy if (isinstance(policy, (type, str)) and policy is not None) else "MlpPolicy", env=None,

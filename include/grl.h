@@ -419,7 +419,8 @@ int grl_ppo_train(grl_handle h, const int32_t* perm, int noptepochs);
 int grl_ppo_get_metrics(grl_handle h, float* out, int cap);
 /* On a PPO handle grl_act (n <= act_batch rows; GRL_ACT_DETERMINISTIC: the mean, else a sample -- eps_or_null NULL draws on the
    device; unclipped; records nothing; the other flags are GRL_ERR_STATE), grl_param_count / _info, grl_reset_optimizer,
-   grl_set_learning_rate, grl_set_stream, grl_profile_* and grl_debug_fetch / _store work; the debug names are "ppo_obs" [R, ld],
+   grl_set_learning_rate, grl_set_stream, grl_profile_*, grl_ppo_state_size / _export / _import (checkpoints, below) and
+   grl_debug_fetch / _store work; the debug names are "ppo_obs" [R, ld],
    "ppo_act", "ppo_old_v", "ppo_old_nlp", "ppo_rew", "ppo_done", "ppo_adv", "ppo_ret" (rollout, row = env * n_steps + t),
    "ppo_last_v", "ppo_last_done", "ppo_mean", "ppo_v" (the last minibatch), "ppo_slots" (grl_debug_store only, three values: slots written,
    slots closed, finished -- says how far a rollout placed through the other names has got), "grads", "adam_m", "adam_v", and with
@@ -467,8 +468,8 @@ int grl_trpo_get_metrics(grl_handle h, float* out, int cap);
    device, left under "trpo_fvp_out"; needs a full rollout (slots closed).  The entries of the value variables in the stored
    vector must be zero (they are in every vector an update forms).  Stream-ordered. */
 int grl_trpo_debug_fvp(grl_handle h);
-/* grl_act, grl_param_*, grl_reset_optimizer, grl_set_learning_rate, grl_set_stream, grl_profile_* and grl_debug_fetch / _store
-   work as on a PPO handle.  Debug names: those of the PPO rollout, and -- laid out like the gradient bucket ([n_trainable], the
+/* grl_act, grl_param_*, grl_reset_optimizer, grl_set_learning_rate, grl_set_stream, grl_profile_*, grl_ppo_state_size /
+   _export / _import and grl_debug_fetch / _store work as on a PPO handle.  Debug names: those of the PPO rollout, and -- laid out like the gradient bucket ([n_trainable], the
    entries of the value variables 0) -- "trpo_g", "trpo_stepdir", "trpo_fullstep", "trpo_fvp_in", "trpo_fvp_out",
    "trpo_theta_old" (every trainable variable as it was when the update began); "trpo_atarg" [T]; "trpo_mean_old" [T, A] (the
    old policy's means).  Every other entry point returns
@@ -572,6 +573,42 @@ int grl_state_size(grl_handle h, size_t* bytes);
 int64_t grl_state_export(grl_handle h, void* host_buf, size_t cap);
 int grl_state_import(grl_handle h, const void* host_buf, size_t n);
 int grl_replay_segments(grl_handle h, int cap, grl_segment* out);
+
+/* Checkpoint and resume of a PPO or TRPO handle (DESIGN.md "Checkpoints of the on-policy models").  Valid on both kinds, as
+   grl_ppo_step is; GRL_ERR_STATE on every other handle (the message names the call) -- and the four calls above stay
+   GRL_ERR_STATE on these two.  The training state lives in the STATE arena (parameters, Adam moments, DevScalars with the beta
+   powers / learning rate / Philox counter of the action draws, PpoDev with the device's slot counter, TrpoDev, and with
+   normalize = 2 the float64 running statistics with their double-buffered count) and the REPLAY arena (the rollout: observations,
+   actions, values, neglogps, rewards, flags, advantages, returns, last values and flags; R = n_envs * n_steps rows, saved whole)
+   -- both caller-owned, the caller copies them -- and a few host-side fields of the handle, which these calls move as one blob:
+     grl_ppo_state_size    bytes grl_ppo_state_export will write now (it depends on whether grl_observe holds rows);
+     grl_ppo_state_export  host; synchronises the handle's stream.  Writes a grl_state_header (replay_pos = replay_size = 0;
+                           config_hash covers both configuration blocks), the grl_config and the grl_ppo_config or
+                           grl_trpo_config the handle was created with (field by field, no padding bytes), behind them, in
+                           this order, the rollout cursor (three int32: slots written, slots closed, finished), the parity of the running-statistics double buffer,
+                           the number of rows the last grl_observe normalised (0 or n_envs) and -- the only training state in
+                           the WORK arena -- those rows [n_envs, rup(obs_dim, 4)] in their normalised form, which obs == NULL
+                           acts on.  NOT in the blob, and not state: the raw rows of grl_observe (normalised by the launch that
+                           uploads them, read by nothing later), what a step sends and returns, the permutations and
+                           diagnostics of the last training call (grl_ppo_get_metrics / grl_trpo_get_metrics are read behind
+                           the call they describe), and TRPO's scratch between the launches of one update (theta_old, the
+                           conjugate-gradient vectors, the line-search words): an update is never interrupted.  Returns the
+                           bytes written, GRL_ERR_INVALID when cap is too small;
+     grl_ppo_state_import  host; synchronises.  Checks everything before it changes anything; every failure is
+                           GRL_ERR_INVALID and leaves the handle exactly as it was: a short blob ("truncated"), a foreign one
+                           ("wrong magic"), another grl_version() or layout version, a blob of the other kind of handle (PPO
+                           into TRPO or the reverse, or one written by grl_state_export), a blob of another configuration --
+                           the message names the first field that differs as grl_config.<field>, grl_ppo_config.<field> or
+                           grl_trpo_config.<field> -- and host fields out of range ("damaged": a cursor outside
+                           0 <= closed <= n_steps, closed <= written <= closed + 1, or more observed rows than n_envs).
+                           Then restores the host fields and the observed rows and re-derives the device's slot counter
+                           (PpoDev.slot) from the blob, so the caller restores the state arena BEFORE importing; a caller
+                           that leaves the rollout out empties it behind the import (grl_debug_store "ppo_slots" 0, 0, 0).
+                           Captured graphs stay valid, as with grl_state_import.
+   No reference call stands behind these three. */
+int grl_ppo_state_size(grl_handle h, size_t* bytes);
+int64_t grl_ppo_state_export(grl_handle h, void* host_buf, size_t cap);
+int grl_ppo_state_import(grl_handle h, const void* host_buf, size_t n);
 
 /* wall-clock free kernel timing: enables hipEvent timing of tagged kernels in later steps */
 int grl_profile_enable(grl_handle h, int on);
