@@ -3,7 +3,7 @@ stable-baselines zip plus, next to it, a directory with the engine's training st
 moments and counters, device RNG position, running statistics, replay ring, priorities -- PPO2 / TRPO: the rollout) and
 ``host.pkl``, the few things this host loop keeps itself: ``num_timesteps``, ``n_updates``, the exploration generator, the
 schedules' reference length, the VecNormalize statistics and returns -- PPO2 / TRPO: the permutation generator, the index of the
-update in progress and what the loop holds between two engine calls (``_on_policy_host_state``).  A model restored from it
+update in progress and what the loop holds between two engine calls (``OnPolicyModel._host_state``).  A model restored from it
 continues with ``learn(n, reset_num_timesteps=False)`` as if ``learn`` had never returned.
 
 ``model.save_checkpoint(path)`` / ``Model.load_checkpoint(path, env)`` do this explicitly.  For scripts that only know
@@ -64,46 +64,29 @@ def _vn_restore(vn, vs):
     vn.clip_obs, vn.clip_reward = vs["clip_obs"], vs["clip_reward"]
 
 
-def _on_policy_host_state(model, include_replay):
-    """host.pkl of a PPO2 / TRPO model: the same format number and the keys ``_read_host`` checks, then what these loops keep.
-    ``loop`` is the model's own record of the rollout in progress (``_loop_snapshot``: the flags the next step or finish takes,
-    the rewards of a slot that is written and not closed, the episode infos and value / reward rows collected so far, the index
-    of the update in progress; TRPO: its generator's counters), ``extra`` what else the model class carries."""
-    vn = model._vec_normalize_env
-    return {"format": HOST_FORMAT, "model": type(model).__name__, "world": 1, "include_replay": bool(include_replay),
-            "num_timesteps": int(model.num_timesteps), "n_updates": int(getattr(model, "n_updates", 0)),
-            "rng": model._rng.get_state(),          # np.random.RandomState: draws the permutations
-            "schedule_total": model._schedule_total, "ep_info_buf": list(model.ep_info_buf),
-            "vec_normalize": None if vn is None else _vn_state(vn),
-            "loop": model._loop_snapshot(include_replay), "extra": model._host_extra()}
+def _common_state(model, include_replay):
+    """The keys of host.pkl that every model class writes: those ``_read_host`` checks, the step counter, what the schedules
+    measure their progress against, and the VecNormalize statistics."""
+    rt, vn = model._dp_rt, model._vec_normalize_env
+    return {"format": HOST_FORMAT, "model": type(model).__name__, "world": 1 if rt is None else rt.world,
+            "include_replay": bool(include_replay), "num_timesteps": int(model.num_timesteps),
+            "schedule_total": model._schedule_total, "vec_normalize": None if vn is None else _vn_state(vn)}
 
 
-def host_state(model, include_replay):
-    if getattr(model, "_on_policy", False):
-        return _on_policy_host_state(model, include_replay)
-    rt = model._dp_rt
-    st = {"format": HOST_FORMAT, "model": type(model).__name__, "world": 1 if rt is None else rt.world,
-          "include_replay": bool(include_replay), "num_timesteps": int(model.num_timesteps), "n_updates": int(model.n_updates),
-          "rng": model._rng.bit_generator.state, "max_priority": getattr(model, "_max_priority", None),
-          # what the exploration / beta / learning-rate schedules measure their progress against, and where they stand
-          "schedule_total": getattr(model, "_schedule_total", None),
-          "exploration_eps": None if getattr(model, "exploration", None) is None
-          else float(model.exploration.value(model.num_timesteps)),
-          "ent_init": getattr(model, "_ent_init", None), "action_space_rng": None, "vec_normalize": None}
-    gen = _space_rng(model.action_space)       # the learning_starts phase samples from the space's own generator
-    if gen is not None:
-        st["action_space_rng"] = (gen[0], pickle.dumps(gen[1]))
-    vn = model._vec_normalize_env
+def _restore_common(model, st):
+    """Puts back what ``_common_state`` took; returns the start of the model's ``_resume`` record."""
+    model.num_timesteps = st["num_timesteps"]
+    vn, vs = model._vec_normalize_env, st["vec_normalize"]
     if vn is not None:
-        st["vec_normalize"] = _vn_state(vn)
-    return st
+        _vn_restore(vn, vs)
+    return {"schedule_total": st["schedule_total"], "ret": None if vs is None else vs["ret"].copy()}
 
 
 def write_state(model, path, include_replay=True):
     """The engine directory with host.pkl inside, one atomic step (engine.save_state)."""
     d = state_dir(path, model._dp_rt)
     model.engine.save_state(d, include_replay=include_replay,
-                            extra={HOST_FILE: pickle.dumps(host_state(model, include_replay), protocol=4)})
+                            extra={HOST_FILE: pickle.dumps(model._host_state(include_replay), protocol=4)})
     return d
 
 
@@ -160,42 +143,7 @@ def restore_state(model, path, required):
             return False
         raise GrlError(why)
     model.engine.load_state(d)
-    if getattr(model, "_on_policy", False):
-        return _restore_on_policy(model, st)
-    model.num_timesteps, model.n_updates = st["num_timesteps"], st["n_updates"]
-    model._rng = np.random.default_rng()
-    model._rng.bit_generator.state = st["rng"]
-    if st["max_priority"] is not None:
-        model._max_priority = st["max_priority"]
-    if st["ent_init"] is not None:
-        model._ent_init = st["ent_init"]
-    if st["action_space_rng"] is not None and hasattr(model.action_space, st["action_space_rng"][0]):
-        setattr(model.action_space, st["action_space_rng"][0], pickle.loads(st["action_space_rng"][1]))
-    vn, vs = model._vec_normalize_env, st["vec_normalize"]
-    if vn is not None:
-        _vn_restore(vn, vs)
-    # consumed by the next learn(reset_num_timesteps=False): continue in place (no reset statistics, no new schedules)
-    model._resume = {"schedule_total": st["schedule_total"], "ret": None if vs is None else vs["ret"].copy()}
-    model._restored_norm_stamp()
-    return True
-
-
-def _restore_on_policy(model, st):
-    """The host half of a PPO2 / TRPO restore (the engine is loaded): counters, the permutation generator, episode statistics,
-    VecNormalize, and the record of the rollout in progress for the next ``learn(reset_num_timesteps=False)``."""
-    from collections import deque
-    model.num_timesteps = st["num_timesteps"]
-    if hasattr(model, "n_updates"):
-        model.n_updates = st["n_updates"]
-    model._rng = np.random.RandomState()
-    model._rng.set_state(st["rng"])
-    model.ep_info_buf = deque(st["ep_info_buf"], maxlen=100)
-    vn, vs = model._vec_normalize_env, st["vec_normalize"]
-    if vn is not None:
-        _vn_restore(vn, vs)
-    model._set_host_extra(st["extra"])
-    model._loop = None
-    model._resume = {"schedule_total": st["schedule_total"], "ret": None if vs is None else vs["ret"].copy(), "loop": st["loop"]}
+    model._restore_host_state(st)
     return True
 
 
@@ -216,7 +164,7 @@ def _refuse_other_model(cls, path):
 
 class CheckpointMixin:
     """save_checkpoint / load_checkpoint and the GRL_CHECKPOINT_STATE hooks of save / load.  The model class provides
-    ``_save_zip(path)``, ``_load_zip(path, env, ...)`` and ``_restored_norm_stamp()``."""
+    ``_save_zip(path)`` and ``_load_zip(path, env, ...)``, and fills in or replaces ``_host_state`` / ``_restore_host_state``."""
     _resume = None
     _schedule_total = None
 
@@ -255,5 +203,24 @@ class CheckpointMixin:
         resume, self._resume = (None if reset_num_timesteps else self._resume), None
         return resume
 
-    def _restored_norm_stamp(self):
-        pass
+    # ------------------------------------------------------------------ host.pkl: the off-policy models; OnPolicyModel has its own
+    def _host_state(self, include_replay):
+        """host.pkl of a SAC / DQN / BDQ model.  ``max_priority`` and ``exploration_eps`` are the Q models' to fill, ``ent_init``
+        is SAC's; every class writes all the keys."""
+        st = _common_state(self, include_replay)
+        st.update(n_updates=int(self.n_updates), rng=self._rng.bit_generator.state, max_priority=None, exploration_eps=None,
+                  ent_init=None, action_space_rng=None)
+        gen = _space_rng(self.action_space)       # the learning_starts phase samples from the space's own generator
+        if gen is not None:
+            st["action_space_rng"] = (gen[0], pickle.dumps(gen[1]))
+        return st
+
+    def _restore_host_state(self, st):
+        """The host half of a restore (the engine is loaded)."""
+        # consumed by the next learn(reset_num_timesteps=False): continue in place (no reset statistics, no new schedules)
+        self._resume = _restore_common(self, st)
+        self.n_updates = st["n_updates"]
+        self._rng = np.random.default_rng()
+        self._rng.bit_generator.state = st["rng"]
+        if st["action_space_rng"] is not None and hasattr(self.action_space, st["action_space_rng"][0]):
+            setattr(self.action_space, st["action_space_rng"][0], pickle.loads(st["action_space_rng"][1]))

@@ -38,10 +38,8 @@ from . import logger
 from . import policies as pol
 from . import save_util
 from . import spaces as sp
+from .base import BaseModel, device_norm_setting, resolve_device_norm
 from .callbacks import as_callback
-from .sac import resolve_device_norm
-from .checkpoint import CheckpointMixin
-from .vec_env import DummyVecEnv, VecEnv, expand_training_env, unwrap_vec_normalize
 
 
 class LinearSchedule:
@@ -53,7 +51,7 @@ class LinearSchedule:
         return self.initial_p + frac * (self.final_p - self.initial_p)
 
 
-class _QModel(CheckpointMixin):
+class _QModel(BaseModel):
     """Shared host loop of DQN and BDQ."""
     _engine_factory = staticmethod(lambda cfg, device: QEngine(cfg, device=device))
     algo = "dqn"
@@ -72,11 +70,9 @@ class _QModel(CheckpointMixin):
         # ``sb.SAC(device_norm=...)``: every observation crosses the bus once, the loop acts on the uploaded rows (GRL_ACT_OBSERVED),
         # appends with ``replay_add_observed`` and pushes no statistics before an update.  True / False / "auto"; None reads
         # GRL_DEVICE_NORM, and for these two classes an UNSET variable means off (SAC: auto).  True and "auto" go through
-        # ``sac.resolve_device_norm``; under data parallelism the host path is taken (the Q handles do not merge their device
+        # ``resolve_device_norm``; under data parallelism the host path is taken (the Q handles do not merge their device
         # statistics over the ranks).
-        if device_norm is None:
-            device_norm = {"0": False, "1": True, "auto": "auto"}.get(os.environ.get("GRL_DEVICE_NORM", "0"), False)
-        self.device_norm = device_norm if device_norm == "auto" else bool(device_norm)
+        self.device_norm = device_norm_setting(device_norm, unset=False)
         if data_parallel is None:
             data_parallel = os.environ.get("GRL_DATA_PARALLEL") or None
         self.data_parallel, self.dp_exchange = data_parallel, dp_exchange
@@ -104,40 +100,6 @@ class _QModel(CheckpointMixin):
         if _init_setup_model and self.observation_space is not None:
             self.setup_model()
 
-    # ------------------------------------------------------------------ env
-    def set_env(self, env):
-        if env is not None and not isinstance(env, VecEnv) and not hasattr(env, "num_envs"):
-            env = DummyVecEnv([lambda: env])
-        if env is not None:
-            # GRL_NUM_ENVS: the single-factory DummyVecEnv of the reference's script (train_stable_baselines.py:52-54) fans out
-            # to worker processes, as for SAC -- this process's share of the job's environments under data parallelism
-            rt = self._dp_runtime()
-            env = expand_training_env(env, rank=0 if rt is None else rt.rank, world=1 if rt is None else rt.world)
-            if self.observation_space is not None and tuple(env.observation_space.shape) != tuple(self.observation_space.shape):
-                raise ValueError("observation space of the new env does not match the model")
-            if self.engine is not None and env.num_envs > self.engine.cfg.act_batch:
-                raise ValueError("env has more sub-environments than the model was built for")
-            self.observation_space, self.action_space = env.observation_space, env.action_space
-            self.n_envs = env.num_envs
-            self._vec_normalize_env = unwrap_vec_normalize(env)
-        self.env = env
-
-    def get_env(self):
-        return self.env
-
-    def get_vec_normalize_env(self):
-        return self._vec_normalize_env
-
-    # ------------------------------------------------------------------ data parallel
-    def _dp_runtime(self):
-        if self._dp_rt is not None:
-            return self._dp_rt
-        if self.data_parallel in (None, False, "", "0", "off"):
-            return None
-        from ..parallel import runtime_for
-        self._dp_rt = runtime_for(self.data_parallel)
-        return self._dp_rt
-
     # ------------------------------------------------------------------ model
     def _towers(self):
         raise NotImplementedError
@@ -161,7 +123,6 @@ class _QModel(CheckpointMixin):
         kw = {}
         if vn is not None:
             kw = dict(clip_obs=vn.clip_obs, clip_reward=vn.clip_reward, norm_eps=vn.epsilon)
-        lr = float(self.learning_rate(1.0)) if callable(self.learning_rate) else float(self.learning_rate)
         rt = self._dp_runtime()
         self._local_batch = self.batch_size if rt is None else rt.shard(self.batch_size, "minibatch rows")
         engine_seed = 0 if self.seed is None else int(self.seed)
@@ -170,7 +131,7 @@ class _QModel(CheckpointMixin):
             self.device = rt.device
         cfg = _capi.make_q_config(self.algo, self._obs_dim, D, bins, common, branch, value, batch_size=self._local_batch,
                                   act_batch=max(1, self.n_envs), replay_capacity=self.buffer_size, normalize=0 if vn is None else _capi.norm_mode(vn), gamma=self.gamma,
-                                  lr=lr, double_q=self.double_q, seed=engine_seed,
+                                  lr=self._learning_rate_value(), double_q=self.double_q, seed=engine_seed,
                                   prioritized=bool(self.prioritized_replay), per_alpha=self.prioritized_replay_alpha,
                                   per_eps=self.prioritized_replay_eps, layer_norm=self.layer_norm, **kw)
         self.engine = self._engine_factory(cfg, self.device)
@@ -243,21 +204,13 @@ class _QModel(CheckpointMixin):
         acts = np.asarray([self._bins_to_env_action(b) for b in self._act_bins(obs, eps)])
         return (acts[0] if single else acts), None
 
-    def pretrain(self, dataset, n_epochs=10, learning_rate=1e-4, adam_epsilon=1e-8, val_interval=None):
-        raise NotImplementedError("%s: pretrain is not implemented (behaviour cloning runs on SAC models only)" % type(self).__name__)
-
     # ------------------------------------------------------------------ learn
     def learn(self, total_timesteps, callback=None, log_interval=100, tb_log_name=None, reset_num_timesteps=True,
               replay_wrapper=None):
-        if self.env is None:
-            raise ValueError("learn() needs an environment")
-        total_timesteps = int(total_timesteps)
-        if reset_num_timesteps:
-            self.num_timesteps = 0
-        # a model restored from a checkpoint continues in place (sb/checkpoint.py): the exploration, beta and learning-rate
-        # schedules keep the length they had in the saved run and read on from the restored counter
-        resume = self._take_resume(reset_num_timesteps)
-        self._schedule_total = sched_total = total_timesteps if resume is None else (resume["schedule_total"] or total_timesteps)
+        # (the exploration, beta and learning-rate schedules of a restored model keep the length they had in the saved run and read
+        # on from the restored counter)
+        total_timesteps, resume = self._begin_learn(total_timesteps, reset_num_timesteps)
+        sched_total = self._schedule_total
         rt, dp = self._dp_rt, self._dp
         W = 1 if rt is None else rt.world
         lead = rt is None or rt.rank == 0
@@ -387,21 +340,6 @@ class _QModel(CheckpointMixin):
                 logger.dumpkvs()
 
     # ------------------------------------------------------------------ persistence
-    def get_parameter_list(self):
-        return self.engine.param_names()
-
-    def get_parameters(self):
-        return self.engine.get_parameters()
-
-    def load_parameters(self, load_path_or_dict, exact_match=True):
-        params = load_path_or_dict
-        if isinstance(params, str):
-            _, params = save_util.load_from_zip(params)
-        unknown = [k for k in params if k not in set(self.get_parameter_list())]
-        if unknown:
-            raise RuntimeError("load_parameters: unknown parameter(s) %s" % unknown[:5])
-        self.engine.set_parameters(params, exact_match=exact_match)
-
     _SAVED = ("double_q", "param_noise", "learning_starts", "train_freq", "prioritized_replay",
               "prioritized_replay_eps", "batch_size", "target_network_update_freq", "prioritized_replay_alpha",
               "prioritized_replay_beta0", "prioritized_replay_beta_iters", "exploration_final_eps",
@@ -411,7 +349,7 @@ class _QModel(CheckpointMixin):
         d = {k: getattr(self, k) for k in self._SAVED}
         if getattr(self, "layer_norm", False):      # the zip rebuilds the same network whichever way it was asked for
             d["policy_kwargs"] = dict(self.policy_kwargs, layer_norm=True)
-        d["learning_rate"] = float(self.learning_rate(1.0)) if callable(self.learning_rate) else float(self.learning_rate)
+        d["learning_rate"] = self._learning_rate_value()
         d.update(observation_space=self.observation_space, action_space=self.action_space, policy=self.policy,
                  n_envs=self.n_envs, _vectorize_action=True)
         return d
@@ -427,21 +365,15 @@ class _QModel(CheckpointMixin):
         for k, v in data.items():
             if k in cls._SAVED + ("learning_rate", "num_actions_pad", "epsilon_greedy") and v is not None:
                 setattr(model, k, v)
-        model.policy_kwargs = dict(model.policy_kwargs or {})
-        for k, v in kwargs.items():
-            setattr(model, k, v)
-        model.observation_space, model.action_space = data.get("observation_space"), data.get("action_space")
-        if env is not None:
-            model.set_env(env)
-        if model.observation_space is None or model.action_space is None:
-            raise ValueError("the zip holds no readable spaces; pass env=")
-        model._infer_shapes(params)
-        model.setup_model()
-        model.load_parameters(params)
-        return model
+        return model._finish_load(data, params, env, kwargs)
 
-    def _infer_shapes(self, params):
-        pass
+    def _host_state(self, include_replay):
+        return dict(super()._host_state(include_replay), max_priority=self._max_priority,
+                    exploration_eps=None if self.exploration is None else float(self.exploration.value(self.num_timesteps)))
+
+    def _restore_host_state(self, st):
+        super()._restore_host_state(st)
+        self._max_priority = st["max_priority"]
 
 
 class DQN(_QModel):

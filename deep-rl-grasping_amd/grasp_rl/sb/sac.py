@@ -41,35 +41,14 @@ from . import logger
 from . import policies as pol
 from . import save_util
 from . import spaces as sp
-from .callbacks import as_callback, may_read_observations
-from .checkpoint import CheckpointMixin
-from .vec_env import DummyVecEnv, VecEnv, expand_training_env, unwrap_vec_normalize
+from .base import BaseModel, device_norm_setting, resolve_device_norm  # noqa: F401  (resolve_device_norm: imported from here too)
+from .callbacks import as_callback
 
 _POLICY_NAMES = {"MlpPolicy": pol.SacMlpPolicy, "CnnPolicy": pol.SacCnnPolicy, "LnMlpPolicy": pol.SacLnMlpPolicy,
                  "LnCnnPolicy": pol.SacLnCnnPolicy}
 
 
-def resolve_device_norm(setting, user_callback, rt, dp):
-    """Where the VecNormalize statistics live during ``learn``: True = on the device (``grl_observe`` / ``grl_norm_update``).
-    'auto' looks at the callback the USER handed over -- before ``learn`` replaces it by a bare one on ranks > 0 -- and under
-    data parallelism the decision is COLLECTIVE (``rt.all``): with the statistics on the device every env step runs an
-    in-kernel merge that waits for all peers, with them on the host an all_gather on the control group; replicas that chose
-    differently (a script that hands only rank 0 a callback) would wait for each other in two different exchanges."""
-    if setting == "auto":
-        setting = not (user_callback is not None and may_read_observations(as_callback(user_callback)))
-    setting = bool(setting)
-    if rt is not None:
-        if setting and not hasattr(dp, "check"):
-            # the device-side merge of the statistics rides on the in-graph exchange's channel; with the collective
-            # fallback (RCCL / gloo) the handle is not connected and every replica would keep its own observation
-            # statistics: take the host path, whose moments are gathered over the ranks
-            logger.warn("device_norm needs the in-graph exchange; this job fell back to a collective library -> host statistics")
-            setting = False
-        setting = rt.all(setting)
-    return setting
-
-
-class SAC(CheckpointMixin):
+class SAC(BaseModel):
     # tests substitute the g++ emulation build here; the product default needs a HIP device
     _engine_factory = staticmethod(lambda cfg, device: SacEngine(cfg, device=device))
 
@@ -111,9 +90,7 @@ class SAC(CheckpointMixin):
         # wrapper's host copy is refreshed whenever it is pickled / saved / synchronised into an evaluation env and when
         # learn() returns.  True / False, or "auto" (default; GRL_DEVICE_NORM=0 / 1 / auto): on unless a callback may look at
         # the observations (callbacks.may_read_observations: everything but this package's and the reference's own callbacks).
-        if device_norm is None:
-            device_norm = {"0": False, "1": True}.get(os.environ.get("GRL_DEVICE_NORM", "auto"), "auto")
-        self.device_norm = device_norm if device_norm == "auto" else bool(device_norm)
+        self.device_norm = device_norm_setting(device_norm, unset="auto")
         # Opt-in: one replica of a data-parallel job (module docstring).  None / False: off; "auto": when this process was
         # launched by torch.distributed.run with WORLD_SIZE > 1; True: required (raises without a launch).
         if data_parallel is None:
@@ -140,44 +117,11 @@ class SAC(CheckpointMixin):
 
     # ------------------------------------------------------------------ environment
     def set_env(self, env):
-        if env is not None and not isinstance(env, VecEnv) and not hasattr(env, "num_envs"):
-            env = DummyVecEnv([lambda: env])
+        super().set_env(env)
         if env is not None:
-            # GRL_NUM_ENVS: the env a model is handed is its TRAINING env -- the one the reference's script wraps as
-            # DummyVecEnv([one factory]) (train_stable_baselines.py:52-54) fans out to worker processes here (row J3)
-            rt = self._dp_runtime()
-            env = expand_training_env(env, rank=0 if rt is None else rt.rank, world=1 if rt is None else rt.world)
-            if self.observation_space is not None and tuple(env.observation_space.shape) != tuple(self.observation_space.shape):
-                raise ValueError("observation space of the new env does not match the model")
-            self.observation_space, self.action_space = env.observation_space, env.action_space
-            self.n_envs = env.num_envs
-            self._vec_normalize_env = unwrap_vec_normalize(env)
-            if self.engine is not None and self.n_envs > self.engine.cfg.act_batch:
-                raise ValueError("env has more sub-environments than the model was built for")
             self._norm_stamp = None     # a new wrapper: its statistics must reach the device whatever their counts are
-        self.env = env
-
-    def get_env(self):
-        return self.env
-
-    def get_vec_normalize_env(self):
-        return self._vec_normalize_env
-
-    # ------------------------------------------------------------------ data parallel
-    def _dp_runtime(self):
-        if self._dp_rt is not None:
-            return self._dp_rt
-        if self.data_parallel in (None, False, "", "0", "off"):
-            return None
-        from ..parallel import runtime_for
-        self._dp_rt = runtime_for(self.data_parallel)
-        return self._dp_rt
 
     # ------------------------------------------------------------------ model
-    def _learning_rate_value(self):
-        lr = self.learning_rate
-        return float(lr(1.0)) if callable(lr) else float(lr)
-
     def setup_model(self):
         if not sp.is_box(self.action_space):
             raise ValueError("SAC needs a continuous (Box) action space")
@@ -343,15 +287,9 @@ class SAC(CheckpointMixin):
     # ------------------------------------------------------------------ learn
     def learn(self, total_timesteps, callback=None, log_interval=4, tb_log_name="SAC", reset_num_timesteps=True,
               replay_wrapper=None):
-        if self.env is None:
+        if self.env is None:      # (this class's own wording, ahead of the shared check)
             raise ValueError("learn() needs an environment: pass env to the constructor / load() or call set_env")
-        total_timesteps = int(total_timesteps)
-        if reset_num_timesteps:
-            self.num_timesteps = 0
-        # a model restored from a checkpoint continues in place (sb/checkpoint.py): the loop counter, the learning-rate
-        # schedule's reference and the statistics stand where the saved run left them
-        resume = self._take_resume(reset_num_timesteps)
-        self._schedule_total = total_timesteps if resume is None else (resume["schedule_total"] or total_timesteps)
+        total_timesteps, resume = self._begin_learn(total_timesteps, reset_num_timesteps)
         rt, dp = self._dp_rt, self._dp
         W = 1 if rt is None else rt.world
         lead = rt is None or rt.rank == 0
@@ -511,24 +449,6 @@ class SAC(CheckpointMixin):
         callback.on_training_end()
 
     # ------------------------------------------------------------------ parameters / persistence
-    def get_parameter_list(self):
-        return self.engine.param_names()
-
-    def get_parameters(self):
-        return self.engine.get_parameters()
-
-    def load_parameters(self, load_path_or_dict, exact_match=True):
-        params = load_path_or_dict
-        if isinstance(params, str):
-            _, params = save_util.load_from_zip(params)
-        elif isinstance(params, (list, tuple)):
-            params = dict(zip(self.get_parameter_list(), params))
-        known = set(self.get_parameter_list())
-        unknown = [k for k in params if k not in known]
-        if unknown:
-            raise RuntimeError("load_parameters: unknown parameter(s) %s" % unknown[:5])
-        self.engine.set_parameters(params, exact_match=exact_match)
-
     def _data(self):
         return {
             "learning_rate": self._learning_rate_value(), "buffer_size": self.buffer_size,
@@ -544,9 +464,14 @@ class SAC(CheckpointMixin):
     def _save_zip(self, save_path):
         return save_util.save_to_zip(save_path, self._data(), self.get_parameters())
 
-    def _restored_norm_stamp(self):
-        """The host wrapper and the device hold the same restored statistics: `_sync_norm_stats` pushes again only once
-        they have moved (a push rewrites the device's copy, and a frozen wrapper would never have pushed)."""
+    def _host_state(self, include_replay):
+        return dict(super()._host_state(include_replay), ent_init=self._ent_init)
+
+    def _restore_host_state(self, st):
+        super()._restore_host_state(st)
+        self._ent_init = st["ent_init"]
+        # the host wrapper and the device hold the same restored statistics: `_sync_norm_stats` pushes again only once
+        # they have moved (a push rewrites the device's copy, and a frozen wrapper would never have pushed)
         vn = self._vec_normalize_env
         if vn is not None:
             self._norm_stamp = (id(vn.obs_rms), float(vn.obs_rms.count), id(vn.ret_rms), float(vn.ret_rms.count),
@@ -570,15 +495,5 @@ class SAC(CheckpointMixin):
                 setattr(model, k, data[k])
         if isinstance(data.get("learning_rate"), (int, float)):
             model.learning_rate = float(data["learning_rate"])
-        model.policy_kwargs = dict(model.policy_kwargs or {})
         model.target_entropy = float(np.asarray(model.target_entropy)) if model.target_entropy != "auto" else "auto"
-        for k, v in kwargs.items():
-            setattr(model, k, v)
-        model.observation_space, model.action_space = data.get("observation_space"), data.get("action_space")
-        if env is not None:
-            model.set_env(env)
-        if model.observation_space is None or model.action_space is None:
-            raise ValueError("the zip holds no readable spaces; pass env=")
-        model.setup_model()
-        model.load_parameters(params)
-        return model
+        return model._finish_load(data, params, env, kwargs)

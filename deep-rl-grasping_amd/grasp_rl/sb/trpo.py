@@ -19,11 +19,12 @@ Scope: the actor-critic ``MlpPolicy`` (two tanh towers, ``net_arch=[dict(vf=[...
 of any rank flattened in C order and not divided by 255, one environment (GRL_NUM_ENVS does not fan a TRPO env out).  GAIL and data
 parallelism are not defined for TRPO.  Everything else says what it refuses.  ``save_checkpoint`` / ``load_checkpoint`` -- or
 GRL_CHECKPOINT_STATE=1 behind ``save`` / ``load`` -- keep the full training state next to the zip, and
-``learn(n, reset_num_timesteps=False)`` on a restored model continues the batch that was in progress, as PPO2 does (ppo2.py).
+``learn(n, reset_num_timesteps=False)`` on a restored model continues the batch that was in progress.  The policy this class
+accepts, acting, the frame of ``learn`` and the host half of a checkpoint are ``OnPolicyModel`` (on_policy.py), shared with ``PPO2``.
 
 VecNormalize works on the host by default; ``device_norm=True`` (GRL_DEVICE_NORM=1 / auto; unset means off) keeps its observation
-statistics on the device while ``learn`` runs, exactly as ``PPO2(device_norm=...)`` does (ppo2.py): one ``engine.observe`` per
-env step and per reset, ``step`` / ``finish`` on the rows it normalised, rewards on the host.
+statistics on the device while ``learn`` runs (``OnPolicyModel``, the same code as for ``PPO2(device_norm=...)``): one
+``engine.observe`` per env step and per reset, ``step`` / ``finish`` on the rows it normalised, rewards on the host.
 """
 import os
 import time
@@ -36,15 +37,13 @@ from ..engine import TrpoEngine
 from ..init import init_ppo_parameters
 from . import logger
 from . import save_util
-from . import spaces as sp
-from .callbacks import as_callback
-from .ppo2 import PPO2, _device_norm_setting, _normalize_kwargs, _safe_mean, explained_variance
-from .vec_env import DummyVecEnv, VecEnv, unwrap_vec_normalize
+from .base import device_norm_setting
+from .on_policy import OnPolicyModel, _normalize_kwargs, _safe_mean, explained_variance
 
 VF_BATCH = 128      # trpo_mpi.py: dataset.iterbatches(..., batch_size=128, include_final_partial_batch=False)
 
 
-class TRPO(PPO2):
+class TRPO(OnPolicyModel):
     _engine_factory = staticmethod(lambda cfg, trpo, device: TrpoEngine(cfg, trpo, device=device))
 
     def __init__(self, policy, env, gamma=0.99, timesteps_per_batch=1024, max_kl=0.01, cg_iters=10, lam=0.98, entcoeff=0.0,
@@ -62,7 +61,7 @@ class TRPO(PPO2):
             raise NotImplementedError("TRPO: the GAIL arguments %s are not implemented (no adversary on the device)" % sorted(gail))
         if os.environ.get("GRL_DATA_PARALLEL") not in (None, "", "0", "off"):
             raise NotImplementedError("TRPO: data_parallel is not implemented (one replica, one environment)")
-        self.device_norm = _device_norm_setting(device_norm)
+        self.device_norm = device_norm_setting(device_norm, unset=False)
         self.policy, self.policy_kwargs = policy, ({} if policy_kwargs is None else dict(policy_kwargs))
         self.gamma, self.timesteps_per_batch, self.max_kl, self.cg_iters = gamma, int(timesteps_per_batch), max_kl, int(cg_iters)
         self.lam, self.entcoeff, self.cg_damping, self.vf_stepsize, self.vf_iters = lam, entcoeff, cg_damping, vf_stepsize, int(vf_iters)
@@ -87,32 +86,14 @@ class TRPO(PPO2):
             self.setup_model()
 
     # ------------------------------------------------------------------ env
-    def set_env(self, env):
-        if env is not None and not isinstance(env, VecEnv) and not hasattr(env, "num_envs"):
-            env = DummyVecEnv([lambda: env])
-        if env is not None:
-            if env.num_envs != 1:
-                raise ValueError("Error: the model requires a non vectorized environment or a single vectorized environment.")
-            if self.observation_space is not None and tuple(env.observation_space.shape) != tuple(self.observation_space.shape):
-                raise ValueError("observation space of the new env does not match the model")
-            self.observation_space, self.action_space = env.observation_space, env.action_space
-            self.n_envs = 1
-            self._vec_normalize_env = unwrap_vec_normalize(env)
-        self.env = env
+    def _training_env(self, env):      # (GRL_NUM_ENVS does not fan a TRPO env out)
+        if env.num_envs != 1:
+            raise ValueError("Error: the model requires a non vectorized environment or a single vectorized environment.")
+        return env
 
     # ------------------------------------------------------------------ model
-    def _net_arch(self):
-        try:
-            return super()._net_arch()
-        except NotImplementedError as e:
-            raise NotImplementedError(str(e).replace("PPO2:", "TRPO:")) from None
-
     def setup_model(self):
-        if not sp.is_box(self.action_space):
-            raise NotImplementedError("TRPO: %s action spaces are not implemented (Box only; Discrete / MultiDiscrete are refused)"
-                                      % type(self.action_space).__name__)
-        if not sp.is_box(self.observation_space) or len(tuple(self.observation_space.shape)) < 1:
-            raise ValueError("Box observations expected, got %s" % (self.observation_space,))
+        self._check_spaces()
         if not 1 <= self.timesteps_per_batch <= 65536:
             raise NotImplementedError("TRPO: timesteps_per_batch must be 1..65536, got %d" % self.timesteps_per_batch)
         if not 1 <= self.cg_iters <= 64:
@@ -120,8 +101,6 @@ class TRPO(PPO2):
         if not 0 <= self.vf_iters <= _capi.PPO_MAX_EPOCHS:
             raise NotImplementedError("TRPO: vf_iters must be 0..%d, got %d" % (_capi.PPO_MAX_EPOCHS, self.vf_iters))
         pi, vf = self._net_arch()
-        self._obs_dim = int(np.prod(tuple(self.observation_space.shape)))
-        self._act_dim = int(np.prod(tuple(self.action_space.shape)))
         self.n_batch = self.timesteps_per_batch
         cfg, trpo = _capi.make_trpo_config(self._obs_dim, self._act_dim, timesteps_per_batch=self.timesteps_per_batch, pi_layers=pi,
                                            vf_layers=vf, gamma=self.gamma, lam=self.lam, max_kl=self.max_kl, cg_iters=self.cg_iters,
@@ -138,29 +117,11 @@ class TRPO(PPO2):
 
     # ------------------------------------------------------------------ learn
     def learn(self, total_timesteps, callback=None, log_interval=100, tb_log_name="TRPO", reset_num_timesteps=True):
-        if self.env is None:
-            raise ValueError("learn() needs an environment")
-        total_timesteps = int(total_timesteps)
-        if reset_num_timesteps:
-            self.num_timesteps = 0
-        resume = self._take_resume(reset_num_timesteps)      # a restored model continues in place (sb/checkpoint.py)
-        self._schedule_total = total_timesteps if resume is None else (resume["schedule_total"] or total_timesteps)
-        device_norm = self._resolve_device_norm(callback)      # (decided from the callback the USER handed over)
-        callback = as_callback(callback)
-        callback.init_callback(self)
-        writer = logger.SummaryWriter(self.tensorboard_log, tb_log_name) if self.tensorboard_log else None
-        try:
-            self._attach_device_norm(device_norm, upload=resume is None)      # restored: the device holds the statistics already
-            self._learn_loop(total_timesteps, callback, log_interval, writer, None, resume)
-        finally:
-            self._detach_device_norm()
-            if writer is not None:
-                writer.close()
-        return self
+        return self._learn(total_timesteps, callback, log_interval, tb_log_name, reset_num_timesteps)
 
     # ------------------------------------------------------------------ checkpoint / resume (sb/checkpoint.py)
     def _host_extra(self):
-        """What this class carries beside PPO2's host state: the episode statistics of the log line and oldpi/* of the zip (the
+        """What this class carries beside the shared host state: the episode statistics of the log line and oldpi/* of the zip (the
         device's snapshot lives in scratch a checkpoint does not hold, so it is fetched here)."""
         old = self._oldpi
         if self._updated:
@@ -175,7 +136,7 @@ class TRPO(PPO2):
         self.episodes_so_far = extra["episodes_so_far"]
         self._oldpi, self._updated = extra["oldpi"], False
 
-    def _learn_loop(self, total_timesteps, callback, log_interval, writer, lr_fn, resume=None):
+    def _learn_loop(self, total_timesteps, callback, log_interval, writer, resume=None):
         eng, T = self.engine, self.timesteps_per_batch
         saved, finished, written, closed = None, False, 0, 0
         episode_start = np.ones(1, np.float32)
@@ -186,7 +147,7 @@ class TRPO(PPO2):
             obs = np.asarray(self.env.reset(), np.float32)
             end = total_timesteps
         else:
-            # the restored batch goes on (ppo2.py: _resumed_start): the generator's counters are the saved run's, and the run
+            # the restored batch goes on (on_policy.py: _resumed_start): the generator's counters are the saved run's, and the run
             # ends where its timesteps_so_far has grown by total_timesteps; episode_start is 1 at the seam
             obs, (written, closed, finished), saved = self._resumed_start(resume)
             st = resume["loop"] or {}
@@ -296,8 +257,9 @@ class TRPO(PPO2):
         params = load_path_or_dict
         if isinstance(params, str):
             _, params = save_util.load_from_zip(params)
-        # (a zip carries oldpi/* behind model/*: the engine keeps the old policy only for the length of an update)
-        super().load_parameters(OrderedDict((n, a) for n, a in params.items() if not n.startswith("oldpi/")), exact_match=exact_match)
+        if isinstance(params, dict):      # a zip carries oldpi/* behind model/*: the engine keeps the old policy only for the length of an update
+            params = OrderedDict((n, a) for n, a in params.items() if not n.startswith("oldpi/"))
+        super().load_parameters(params, exact_match=exact_match)
 
     def _save_zip(self, save_path):
         data = {k: getattr(self, k) for k in self._SAVED}
@@ -322,27 +284,7 @@ class TRPO(PPO2):
         for k, v in data.items():
             if k in cls._SAVED and (v is not None or k in ("expert_dataset", "seed")):
                 setattr(model, k, v)
-        model.policy_kwargs = dict(model.policy_kwargs or {})
-        for k, v in kwargs.items():
-            setattr(model, k, v)
-        model._rng = np.random.RandomState(model.seed)
-        model.observation_space, model.action_space = data.get("observation_space"), data.get("action_space")
-        if env is not None:
-            model.set_env(env)
-        if model.observation_space is None or model.action_space is None:
-            raise ValueError("the zip holds no readable spaces; pass env=")
+        model._finish_load(data, params, env, kwargs)
         old = OrderedDict(("model/" + n[len("oldpi/"):], a) for n, a in params.items() if n.startswith("oldpi/"))
-        params = OrderedDict((n, a) for n, a in params.items() if not n.startswith("oldpi/"))
-        if "net_arch" not in model.policy_kwargs:      # the towers as the parameters describe them
-            def widths(nm):
-                out, l = [], 0
-                while "model/%s_fc%d/w:0" % (nm, l) in params:
-                    out.append(int(params["model/%s_fc%d/w:0" % (nm, l)].shape[1]))
-                    l += 1
-                return out
-            if (widths("pi"), widths("vf")) != ([64, 64], [64, 64]):
-                model.policy_kwargs["net_arch"] = [dict(vf=widths("vf"), pi=widths("pi"))]
-        model.setup_model()
-        model.load_parameters(params)
         model._oldpi = old if old else None
         return model
