@@ -81,7 +81,8 @@ static int check_cfg(const grl_config* c, bool trpo_call = false) {
   if (c->extractor == GRL_EXTRACTOR_MLP) {
     if (c->obs_dim < 1) return fail(GRL_ERR_INVALID, "obs_dim must be >= 1 for the MLP extractor");
   } else {
-    if (c->img_hw != 64) return fail(GRL_ERR_INVALID, "only 64x64 images (camera_info.yaml) are supported");
+    if (c->img_hw < 36 || c->img_hw > 128)
+      return fail(GRL_ERR_INVALID, "img_hw " + std::to_string(c->img_hw) + ": square images of 36x36 to 128x128 (camera_info.yaml) are supported");
     if (c->obs_channels < 1 || c->obs_channels > 8) return fail(GRL_ERR_INVALID, "obs_channels out of range");
     if (c->extractor == GRL_EXTRACTOR_AUGMENTED && (c->n_direct < 0 || c->n_direct > 64))
       return fail(GRL_ERR_INVALID, "n_direct out of range");

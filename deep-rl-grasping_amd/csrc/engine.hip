@@ -228,6 +228,29 @@ struct ConvGeom {
   int LY() const { return ldy ? ldy : Cout; }
 };
 
+// Layer l of the Nature-CNN (8x8 stride 4 | 4x4 stride 2 | 3x3 stride 1, TF 'VALID') over a square image of side hw
+static ConvGeom cnn_geom(int l, int C_img, int hw) {
+  const int o1 = (hw - 8) / 4 + 1, o2 = (o1 - 4) / 2 + 1, o3 = o2 - 2;
+  ConvGeom g;
+  if (l == 0) g = {hw, hw, C_img, 8, 8, 4, 0, o1, o1, 32};
+  else if (l == 1) g = {o1, o1, 32, 4, 4, 2, 0, o2, o2, 64};
+  else g = {o2, o2, 64, 3, 3, 1, 0, o3, o3, 64};
+  return g;
+}
+
+// What the SAC plans take from the image size: the output sides of the three convolutions, their pixel counts and the input
+// width of the extractor's dense layer (64x64: 15 / 6 / 4, 225 / 36 / 16, 1024)
+struct SacGeom {
+  int o1 = 0, o2 = 0, o3 = 0;
+  int p1 = 0, p2 = 0, p3 = 0;
+  int K = 0;
+  void from(const ConvGeom* cg) {
+    o1 = cg[0].OH; o2 = cg[1].OH; o3 = cg[2].OH;
+    p1 = o1 * o1; p2 = o2 * o2; p3 = o3 * o3;
+    K = cg[2].Cout * p3;
+  }
+};
+
 struct ConvFwdTabs {
   int32_t* tab_i = nullptr;   // [M]
   int32_t* tab_r = nullptr;   // [K+1] (extra entry for the bias row of the weight gradient)
@@ -345,6 +368,7 @@ struct grl_ctx {
   bool cnn = false;
   int C_img = 0, hw = 0, img_elems = 0, F = 0, Fc = 0, ldf = 0, A = 0, L = 0, B = 0, NA = 0;
   int hid[GRL_MAX_LAYERS];
+  SacGeom geo;        // SAC on images: what the plans take from img_hw (SacPlanner::shapes)
 
   // parameter layout
   std::vector<Var> vars;
@@ -637,7 +661,7 @@ struct grl_ctx {
       e.w[l] = add_var(scope + "/" + n[l] + "/w:0", {cs[l][0], cs[l][1], cs[l][2], cs[l][3]}, trainable);
       e.b[l] = add_var(scope + "/" + n[l] + "/b:0", {1, cs[l][3], 1, 1}, trainable);
     }
-    e.fw = add_var(scope + "/" + n[3] + "/w:0", {1024, 512}, trainable);
+    e.fw = add_var(scope + "/" + n[3] + "/w:0", {geo.K, 512}, trainable);
     e.fb = add_var(scope + "/" + n[3] + "/b:0", {512}, trainable);
   }
 
@@ -1233,7 +1257,7 @@ struct grl_ctx {
       return p;
     };
     std::vector<IgemmProb> light;
-    for (int n = 0; n < 2; ++n) light.push_back(shape(1024 + 1, 512, B, 1));
+    for (int n = 0; n < 2; ++n) light.push_back(shape(geo.K + 1, 512, B, 1));
     const MlpP* ms[4] = {&m_pi, &m_vf, &m_qf1, &m_qf2};
     for (const MlpP* m : ms) {
       int d = m->in_dim;
@@ -1568,14 +1592,6 @@ struct grl_ctx {
   int run_ops(std::vector<Op>& ops);
   int capture(std::vector<std::vector<Op>*> seq, hipGraphExec_t* out);
 };
-
-static ConvGeom cnn_geom(int l, int C_img) {
-  ConvGeom g;
-  if (l == 0) g = {64, 64, C_img, 8, 8, 4, 0, 15, 15, 32};
-  else if (l == 1) g = {15, 15, 32, 4, 4, 2, 0, 6, 6, 64};
-  else g = {6, 6, 64, 3, 3, 1, 0, 4, 4, 64};
-  return g;
-}
 
 // --------------------------------------------------------------------------------------------------
 int grl_ctx::plan() {

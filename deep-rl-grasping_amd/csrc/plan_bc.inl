@@ -38,6 +38,7 @@ struct BcPlanner {
   const int Bb;                         // bc_batch
   const bool cnn;
   const int A, L, F, Fc, ldf, hw, C_img, img_elems;
+  const SacGeom& geo;                   // the handle's image geometry (SacPlanner::shapes)
   const int* const hid;
   Arena& wk;                            // the handle's work arena, standing in for the session buffer while the plan is built
   const float* const P;
@@ -58,7 +59,7 @@ struct BcPlanner {
 
   BcPlanner(grl_ctx& ctx, BcPlan& plan)
       : h(ctx), p(plan), c(ctx.cfg), Bb(plan.cfg.batch), cnn(ctx.cnn), A(ctx.A), L(ctx.L), F(ctx.F), Fc(ctx.Fc), ldf(ctx.ldf), hw(ctx.hw),
-        C_img(ctx.C_img), img_elems(ctx.img_elems), hid(ctx.hid), wk(ctx.wk), P(ctx.params) {
+        C_img(ctx.C_img), img_elems(ctx.img_elems), geo(ctx.geo), hid(ctx.hid), wk(ctx.wk), P(ctx.params) {
     nd = cnn && c.extractor == GRL_EXTRACTOR_AUGMENTED ? c.n_direct : 0;
   }
 
@@ -79,13 +80,13 @@ struct BcPlanner {
     feat = wk.f32((int64_t)Bb * ldf);   // (row padding [F, ldf) stays zero: grl_bc_begin clears the whole buffer)
     if (cnn) {
       x_obs = wk.f32((int64_t)Bb * img_elems);
-      a1 = wk.f32((int64_t)Bb * 225 * ld1);
-      a2 = wk.f32((int64_t)Bb * 36 * 64);
-      a3 = wk.f32((int64_t)Bb * 16 * 64);
+      a1 = wk.f32((int64_t)Bb * geo.p1 * ld1);
+      a2 = wk.f32((int64_t)Bb * geo.p2 * 64);
+      a3 = wk.f32((int64_t)Bb * geo.p3 * 64);
       dfeat = wk.f32((int64_t)Bb * ldf);
-      g3 = wk.f32((int64_t)Bb * 16 * 64);
-      g2 = wk.f32((int64_t)Bb * 36 * 64);
-      g1 = wk.f32((int64_t)Bb * 225 * ld1);    // (pixels of row / column 14, which no window of conv2 covers, stay zero)
+      g3 = wk.f32((int64_t)Bb * geo.p3 * 64);
+      g2 = wk.f32((int64_t)Bb * geo.p2 * 64);
+      g1 = wk.f32((int64_t)Bb * geo.p1 * ld1);    // (pixels that no window of conv2 covers -- 64x64: row / column 14 -- stay zero)
     }
     act = wk.f32((int64_t)Bb * A);
     det = wk.f32((int64_t)Bb * A);
@@ -113,7 +114,7 @@ struct BcPlanner {
   void forward() {
     if (!cnn) return;
     for (int l = 0; l < 3; ++l) {
-      cg[l] = cnn_geom(l, C_img);
+      cg[l] = cnn_geom(l, C_img, hw);
       if (l == 0) cg[l].ldy = ld1;
       if (l == 1) cg[l].ldx = ld1;
       ft[l] = h.conv_fwd_tabs(cg[l], Bb);
@@ -130,7 +131,7 @@ struct BcPlanner {
       ca.B = Bb; ca.n_nets = 1;
       const int Ci = C_img;
       Op op; op.tag = "conv_stack_fwd";
-      op.flops = op.flops_exec = 2.0 * Bb * (225.0 * 32 * 64 * Ci + 36.0 * 64 * 512 + 16.0 * 64 * 576);
+      op.flops = op.flops_exec = 2.0 * Bb * ((double)geo.p1 * 32 * 64 * Ci + (double)geo.p2 * 64 * 512 + (double)geo.p3 * 64 * 576);
       op.run = [ca, Ci](hipStream_t s) { launch_conv_stack_fwd(Ci, ca, s); };
       fwd.push_back(op);
     } else {
@@ -138,7 +139,7 @@ struct BcPlanner {
       for (int l = 0; l < 3; ++l)
         h.add_launch(fwd, tags[l], 0, {h.conv_fwd(io[l], ft[l], cg[l], P + h.ex[0].w[l], P + h.ex[0].b[l], io[l + 1], ACT_RELU, 0.f)});
     }
-    h.add_launch(fwd, "fc_fwd", 0, {h.dense_fwd(a3, 1024, 1024, nullptr, 0, 0, Bb, P + h.ex[0].fw, 512, P + h.ex[0].fb, feat, ldf, ACT_RELU)});
+    h.add_launch(fwd, "fc_fwd", 0, {h.dense_fwd(a3, geo.K, geo.K, nullptr, 0, 0, Bb, P + h.ex[0].fw, 512, P + h.ex[0].fb, feat, ldf, ACT_RELU)});
   }
 
   // per-layer route of the head: dense forward launches, the loss launch, the closing launch
@@ -168,7 +169,7 @@ struct BcPlanner {
       h.add_launch(bwd, "heads_bwd", 1, {h.dense_bwd({{gPI.g[l], hid[l], hid[l], P + h.m_pi.w[l]}}, Bb, 0, hid[l - 1], gPI.g[l - 1], hid[l - 1], hPI.z[l - 1])});
     if (!cnn) return;
     h.add_launch(bwd, "heads_dfeat", 1, {h.dense_bwd({{gPI.g[0], hid[0], hid[0], P + h.m_pi.w[0]}}, Bb, 0, Fc, dfeat, ldf, feat)});
-    h.add_launch(bwd, "fc_bwd", 1, {h.dense_bwd({{dfeat, ldf, 512, P + h.ex[0].fw}}, Bb, 0, 1024, g3, 1024, a3)});
+    h.add_launch(bwd, "fc_bwd", 1, {h.dense_bwd({{dfeat, ldf, 512, P + h.ex[0].fw}}, Bb, 0, geo.K, g3, geo.K, a3)});
     std::vector<ConvBwdClass> bc3 = h.conv_bwd_tabs_exact(cg[2], Bb, nullptr);
     std::vector<ConvBwdClass> bc2 = h.conv_bwd_tabs_exact(cg[1], Bb, nullptr);
     std::vector<IgemmProb> p3, p2;
@@ -192,9 +193,9 @@ struct BcPlanner {
         slab(q);
         h.add_wgrad(wgc, q, h.ex[0].w[l], 0, cg[l].K(), h.ex[0].b[l]);
       }
-      IgemmProb q = h.dense_wgrad(a3, 1024, 1024, true, dfeat, ldf, 512, Bb, nullptr, 1);
+      IgemmProb q = h.dense_wgrad(a3, geo.K, geo.K, true, dfeat, ldf, 512, Bb, nullptr, 1);
       slab(q);
-      h.add_wgrad(wg, q, h.ex[0].fw, 0, 1024, h.ex[0].fb);
+      h.add_wgrad(wg, q, h.ex[0].fw, 0, geo.K, h.ex[0].fb);
     }
     for (int l = 0; l < L; ++l) {
       IgemmProb q = l == 0 ? h.dense_wgrad(feat, ldf, F, true, gPI.g[0], hid[0], hid[0], Bb, nullptr, 1, (int)rup(F, 4))

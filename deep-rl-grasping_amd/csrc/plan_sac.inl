@@ -35,6 +35,7 @@ struct SacPlanner {
   // the handle's shapes (written by shapes()), work arena and switches under the names every step uses
   bool& cnn;
   int &A, &L, &B, &NA, &hw, &C_img, &img_elems, &F, &Fc, &ldf;
+  SacGeom& geo;                                     // o1 / o2 / o3, their squares and the dense K of the handle's image size
   int* const hid;
   Arena& wk;
   const Switches& sw;
@@ -87,7 +88,7 @@ struct SacPlanner {
 
   explicit SacPlanner(grl_ctx& ctx)
       : h(ctx), c(ctx.cfg), cnn(ctx.cnn), A(ctx.A), L(ctx.L), B(ctx.B), NA(ctx.NA), hw(ctx.hw), C_img(ctx.C_img), img_elems(ctx.img_elems),
-        F(ctx.F), Fc(ctx.Fc), ldf(ctx.ldf), hid(ctx.hid), wk(ctx.wk), sw(ctx.sw) {}
+        F(ctx.F), Fc(ctx.Fc), ldf(ctx.ldf), geo(ctx.geo), hid(ctx.hid), wk(ctx.wk), sw(ctx.sw) {}
 
   void shapes() {
     cnn = c.extractor != GRL_EXTRACTOR_MLP;
@@ -99,11 +100,28 @@ struct SacPlanner {
       C_img = c.obs_channels - (nd > 0 ? 1 : 0);
       img_elems = hw * hw * C_img;
       F = 512 + nd; Fc = 512;
+      for (int l = 0; l < 3; ++l) cg[l] = cnn_geom(l, C_img, hw);
+      cg[0].ldy = cg[1].ldx = ld1;
+      geo.from(cg);
     } else {
       C_img = 0; img_elems = c.obs_dim; F = c.obs_dim; Fc = 0;
     }
     ldf = (int)rup(F, 4);
     h.build_layout();
+  }
+
+  // The addressing tables hold 32-bit element offsets, and the GEMM kernels reach their operands through buffer descriptors
+  // with 32-bit byte offsets below 2 GiB (igemm2.h: i2_rsrc; beyond it a load returns zeros): the largest buffer a table
+  // walks -- an image buffer, the a1 / g1 pair, for the minibatch and for the acting pass -- must stay below 2^31 bytes.
+  int fits() const {
+    if (!cnn) return GRL_OK;
+    const int64_t rows = std::max(B, std::max(NA, 64));
+    const int64_t per_row = std::max<int64_t>({(int64_t)hw * hw * c.obs_channels, (int64_t)geo.p1 * ld1, (int64_t)geo.p2 * 64, (int64_t)geo.K});
+    if (4 * rows * per_row >= ((int64_t)1 << 31))
+      return fail(GRL_ERR_INVALID, "SAC: " + std::to_string(hw) + "x" + std::to_string(hw) + " images at batch_size " + std::to_string(B) + " / act_batch " +
+                                       std::to_string(NA) + " need a buffer of " + std::to_string(4 * rows * per_row) +
+                                       " bytes: tables and buffer descriptors hold 32-bit offsets (fewer than 2^31 bytes per buffer)");
+    return GRL_OK;
   }
 
   void arenas() {
@@ -168,11 +186,11 @@ struct SacPlanner {
       // read once) instead of two half-empty ones.  The target network's buffer keeps the stride (columns 32..63 idle)
       // so that one set of conv2 tables serves all three.
       ld1 = 64;
-      float* a1_pair = wk.f32((int64_t)B * 225 * 64);
+      float* a1_pair = wk.f32((int64_t)B * geo.p1 * 64);
       for (int n = 0; n < 3; ++n) {
-        a1[n] = n < 2 ? a1_pair + 32 * n : wk.f32((int64_t)B * 225 * 64);
-        a2[n] = wk.f32((int64_t)B * 36 * 64);
-        a3[n] = wk.f32((int64_t)B * 16 * 64);
+        a1[n] = n < 2 ? a1_pair + 32 * n : wk.f32((int64_t)B * geo.p1 * 64);
+        a2[n] = wk.f32((int64_t)B * geo.p2 * 64);
+        a3[n] = wk.f32((int64_t)B * geo.p3 * 64);
       }
     }
     h.act = wk.f32((int64_t)B * A); h.rew = wk.f32(B); h.done = wk.f32(B);
@@ -220,11 +238,11 @@ struct SacPlanner {
       h.zero_once.push_back({dls, (size_t)B * ld_dm * 4});
     }
     if (cnn) {
-      float* g1_pair = wk.f32((int64_t)B * 225 * 64);
+      float* g1_pair = wk.f32((int64_t)B * geo.p1 * 64);
       for (int n = 0; n < 2; ++n) {
         dfeat[n] = wk.f32((int64_t)B * ldf);
-        g3[n] = wk.f32((int64_t)B * 16 * 64);
-        g2[n] = wk.f32((int64_t)B * 36 * 64);
+        g3[n] = wk.f32((int64_t)B * geo.p3 * 64);
+        g2[n] = wk.f32((int64_t)B * geo.p2 * 64);
         g1[n] = g1_pair + 32 * n;
       }
     }
@@ -286,7 +304,7 @@ struct SacPlanner {
     ca.nets[0].x = ca.nets[1].x = obs;
     const int Ci = C_img;
     Op op; op.tag = "conv_stack_fwd";
-    op.flops = op.flops_exec = 2.0 * B * 3 * (225.0 * 32 * 64 * Ci + 36.0 * 64 * 512 + 16.0 * 64 * 576);
+    op.flops = op.flops_exec = 2.0 * B * 3 * ((double)geo.p1 * 32 * 64 * Ci + (double)geo.p2 * 64 * 512 + (double)geo.p3 * 64 * 576);
     op.run = [ca, Ci](hipStream_t s) { launch_conv_stack_fwd(Ci, ca, s); };
     return op;
   }
@@ -325,31 +343,29 @@ struct SacPlanner {
   // =============================================================== forward through the three CNNs: observations -> feat
   void forward() {
     if (!cnn) return;
-    for (int l = 0; l < 3; ++l) {
-      cg[l] = cnn_geom(l, C_img);
-      if (l == 0) cg[l].ldy = ld1;
-      if (l == 1) cg[l].ldx = ld1;
-      ft[l] = h.conv_fwd_tabs(cg[l], B);
-    }
+    for (int l = 0; l < 3; ++l) ft[l] = h.conv_fwd_tabs(cg[l], B);     // (cg: shapes())
     const float* const xin[3] = {h.x_obs, h.x_obs, h.x_next};
     // tensor groups whose 16-byte stores leave write-through (store_drain.h; GRL_TUNE store_drain=<mask>, bits outside SD_ALL
     // are ignored).  The buffer instruction takes 32-bit byte offsets: the largest buffers of the groups -- an image buffer, the
     // a1 / g1 pair -- must stay below SD_MAX_BYTES, else every group keeps plain stores and the plan dump says why.
     {
-      const int64_t largest = 4 * std::max<int64_t>((int64_t)B * img_elems, (int64_t)B * 225 * 64);
-      const int asked = sw.get(Sw::store_drain) & SD_ALL;
+      const int64_t largest = 4 * std::max<int64_t>((int64_t)B * img_elems, (int64_t)B * geo.p1 * 64);
+      // (SD_A12 belongs to the forward stack, which runs 64x64 images only: other sizes do not take that bit)
+      const int asked = sw.get(Sw::store_drain) & (hw == 64 ? SD_ALL : SD_ALL & ~SD_A12);
       store_drain = largest < SD_MAX_BYTES ? asked : 0;
       plan_note("grl plan: store_drain   mask %d (1 a1+a2, 2 a3 [per-layer route], 4 g1+g2, 8 weight-gradient slabs, 16 riders' images)%s\n", store_drain,
                 store_drain != asked ? "  [asked for more: a buffer of this batch reaches 2 GiB, all stores plain]" : "");
     }
     // the stack for 1 / 2 / 4 image channels; GRL_TUNE conv_stack=0 or any other channel count: a launch per layer
-    // (GRL_NO_V2: the scalar-gather fallback test runs the per-layer launches on igemm_kernel)
+    // (GRL_NO_V2: the scalar-gather fallback test runs the per-layer launches on igemm_kernel).  conv_stack.h is built around
+    // 15x15 / 6x6 / 4x4: every other image size runs the per-layer launches whatever GRL_TUNE says (and with it conv_stack_bwd)
     conv_stack = conv_stack_ok(C_img) && hw == 64 && sw.get(Sw::conv_stack) != 0 && !sw.get(Sw::GRL_NO_V2);
+    if (hw != 64) plan_note("grl plan: sac image %dx%d per-layer convolutions (conv_stack is 64x64 only)\n", hw, hw);
     if (conv_stack) forward_stack(xin);
     else forward_layers(xin);
     std::vector<IgemmProb> pr;
     for (int n = 0; n < 3; ++n)
-      pr.push_back(h.dense_fwd(a3[n], 1024, 1024, nullptr, 0, 0, B, P + h.ex[n].fw, 512, P + h.ex[n].fb, h.feat[n], ldf, ACT_RELU));
+      pr.push_back(h.dense_fwd(a3[n], geo.K, geo.K, nullptr, 0, 0, B, P + h.ex[n].fw, 512, P + h.ex[n].fb, h.feat[n], ldf, ACT_RELU));
     h.add_launch(h.ops_grads, "fc_fwd", 0, pr);
   }
 
@@ -665,9 +681,9 @@ struct SacPlanner {
     std::vector<ConvBwdClass> bc3 = h.conv_bwd_tabs_exact(cg[2], B, nullptr);
     std::vector<ConvBwdClass> bc2 = h.conv_bwd_tabs_exact(cg[1], B, &untouched);
     if (!untouched.empty())   // input pixels of conv2 that no output window covers (row / column 14): their gradient is zero
-      for (int n = 0; n < 2; ++n) h.zero_once.push_back({g1[n], (size_t)(((int64_t)B * 225 - 1) * ld1 + 32) * 4});
+      for (int n = 0; n < 2; ++n) h.zero_once.push_back({g1[n], (size_t)(((int64_t)B * geo.p1 - 1) * ld1 + 32) * 4});
     for (int n = 0; n < 2; ++n)
-      bwd_pr[0].push_back(h.dense_bwd({{dfeat[n], ldf, 512, P + h.ex[n].fw}}, B, 0, 1024, g3[n], 1024, a3[n]));
+      bwd_pr[0].push_back(h.dense_bwd({{dfeat[n], ldf, 512, P + h.ex[n].fw}}, B, 0, geo.K, g3[n], geo.K, a3[n]));
     for (int n = 0; n < 2; ++n)
       for (auto& cl : bc3) bwd_pr[1].push_back(h.conv_bwd(g3[n], cl, cg[2], P + h.ex[n].w[2], g2[n], a2[n]));
     for (int n = 0; n < 2; ++n)
@@ -725,9 +741,9 @@ struct SacPlanner {
         h.add_wgrad(wgc[2], p, h.ex[n].w[2], 0, cg[2].K(), h.ex[n].b[2]);
       }
       {
-        IgemmProb p = h.dense_wgrad(a3[n], 1024, 1024, true, dfeat[n], ldf, 512, B, nullptr, 1);
+        IgemmProb p = h.dense_wgrad(a3[n], geo.K, geo.K, true, dfeat[n], ldf, 512, B, nullptr, 1);
         p.c = wk.f32(p.slab_stride * p.split);
-        h.add_wgrad(wg, p, h.ex[n].fw, 0, 1024, h.ex[n].fb);
+        h.add_wgrad(wg, p, h.ex[n].fw, 0, geo.K, h.ex[n].fb);
       }
     }
   }
@@ -826,7 +842,7 @@ struct SacPlanner {
       }
       ba.B = B; ba.n_nets = 2;
       Op op; op.tag = "conv_stack_bwd";
-      op.flops = op.flops_exec = 2.0 * B * 2 * (36.0 * 64 * 512 + 16.0 * 64 * 576);
+      op.flops = op.flops_exec = 2.0 * B * 2 * ((double)geo.p2 * 64 * 512 + (double)geo.p3 * 64 * 576);
       op.run = [ba](hipStream_t s) { launch_conv_stack_bwd(ba, s); };
       bwd.push_back(op);
     } else if (cnn) {
@@ -987,6 +1003,7 @@ struct SacPlanner {
     //   middle: body(f), heads[tick, counter += 1; images(t+1) -> other] | reduce + Adam + extras(t+1) [rng_img += 1]
     //   last  : body(f), heads[tick, counter += 1]                        | reduce + Adam (counter += 1)
     // (the emulation build has no 16-byte form: its riders walk the rows element by element)
+    if (cnn && hw != 64 && x_obs_b) plan_note("grl plan: gather_ride  off for %dx%d images (it needs the forward stack's slot): multi-update calls run the prefetch form\n", hw, hw);
     if (!x_obs_b || kit.stack < 0 || !have_wgrad_conv_b || conv_stack_bwd || !(pre.g2.vec4 || !elem_vec4_built()) || B % GATHER_RIDE_ROWS != 0) return GRL_OK;
     int ride_rows = sw.get(Sw::ride_rows);
     if (!gather_ride_rows_built(ride_rows)) ride_rows = GATHER_RIDE_ROWS;
@@ -1073,9 +1090,9 @@ struct SacPlanner {
     float* fc_parts = nullptr;
     int fc_split = 0;
     if (cnn) {
-      float* const aa1 = wk.f32((int64_t)NA * 225 * 32);
-      float* const aa2 = wk.f32((int64_t)NA * 36 * 64);
-      float* const aa3 = wk.f32((int64_t)NA * 16 * 64);
+      float* const aa1 = wk.f32((int64_t)NA * geo.p1 * 32);
+      float* const aa2 = wk.f32((int64_t)NA * geo.p2 * 64);
+      float* const aa3 = wk.f32((int64_t)NA * geo.p3 * 64);
       float* io[4] = {ax, aa1, aa2, aa3};
       if (conv_stack) {     // one workgroup per observation walks conv1 -> conv2 -> conv3 (round 4: three launches, 4.9 + 9.2 + 9.2 us)
         ConvStackArgs ca;
@@ -1097,7 +1114,7 @@ struct SacPlanner {
         }
       }
       if (mfma_heads) {
-        IgemmProb p = h.dense_fwd(aa3, 1024, 1024, nullptr, 0, 0, NA, P + h.ex[0].fw, 512, nullptr, nullptr, 512, ACT_NONE);
+        IgemmProb p = h.dense_fwd(aa3, geo.K, geo.K, nullptr, 0, 0, NA, P + h.ex[0].fw, 512, nullptr, nullptr, 512, ACT_NONE);
         h.set_split(p, AM_MAXP);       // one tile walking 32 slabs (13.6 us for 16 rows) -> 4 x the tiles, 8 slabs each
         fc_split = p.split;
         fc_parts = wk.f32((int64_t)NA * 512 * p.split);
@@ -1105,7 +1122,7 @@ struct SacPlanner {
         h.add_launch(h.ops_act, "act_fc", 0, {p});
       } else {
         h.add_launch(h.ops_act, "act_fc", 0,
-                   {h.dense_fwd(aa3, 1024, 1024, nullptr, 0, 0, NA, P + h.ex[0].fw, 512, P + h.ex[0].fb, h.afeat, ldf, ACT_RELU)});
+                   {h.dense_fwd(aa3, geo.K, geo.K, nullptr, 0, 0, NA, P + h.ex[0].fw, 512, P + h.ex[0].fb, h.afeat, ldf, ACT_RELU)});
       }
     }
     // the policy head: one launch (act_heads_kernel) for layer widths it covers, else a launch per layer + the output launch.
@@ -1178,15 +1195,15 @@ struct SacPlanner {
     if (cnn) {
       h.dbg["x_obs"] = {h.x_obs, (int64_t)B * img_elems};
       h.dbg["x_next"] = {h.x_next, (int64_t)B * img_elems};
-      h.dbg["a1_pi"] = {a1[0], (int64_t)B * 225 * 32};   // (side-by-side layout: the first half of the pair buffer, stride 64)
-      h.dbg["a2_pi"] = {a2[0], (int64_t)B * 36 * 64};
-      h.dbg["a3_pi"] = {a3[0], (int64_t)B * 1024};
-      h.dbg["a1_pair"] = {a1[0], (int64_t)B * 225 * 64};   // [B * 225][pi 0..31 | values_fn 32..63]
-      h.dbg["a2_vf"] = {a2[1], (int64_t)B * 36 * 64};
-      h.dbg["a3_vf"] = {a3[1], (int64_t)B * 1024};
-      h.dbg["g1_vf"] = {g1[1], (int64_t)B * 225 * 32};
-      h.dbg["g2_vf"] = {g2[1], (int64_t)B * 36 * 64};
-      h.dbg["g3_vf"] = {g3[1], (int64_t)B * 1024};
+      h.dbg["a1_pi"] = {a1[0], (int64_t)B * geo.p1 * 32};   // (side-by-side layout: the first half of the pair buffer, stride 64)
+      h.dbg["a2_pi"] = {a2[0], (int64_t)B * geo.p2 * 64};
+      h.dbg["a3_pi"] = {a3[0], (int64_t)B * geo.K};
+      h.dbg["a1_pair"] = {a1[0], (int64_t)B * geo.p1 * 64};   // [B * 225][pi 0..31 | values_fn 32..63]
+      h.dbg["a2_vf"] = {a2[1], (int64_t)B * geo.p2 * 64};
+      h.dbg["a3_vf"] = {a3[1], (int64_t)B * geo.K};
+      h.dbg["g1_vf"] = {g1[1], (int64_t)B * geo.p1 * 32};
+      h.dbg["g2_vf"] = {g2[1], (int64_t)B * geo.p2 * 64};
+      h.dbg["g3_vf"] = {g3[1], (int64_t)B * geo.K};
       h.dbg["dfeat_pi"] = {dfeat[0], (int64_t)B * ldf};
       h.dbg["dfeat_vf"] = {dfeat[1], (int64_t)B * ldf};
     }
@@ -1218,6 +1235,7 @@ struct SacPlanner {
 int grl_ctx::plan_sac() {
   SacPlanner p(*this);
   p.shapes();                // shapes + parameter layout
+  if (int e = p.fits()) return e;
   p.arenas();                // state, gradient, replay and work arena (the carving order is the checkpoint format)
   if (int e = p.gather()) return e;
   p.forward();               // conv stack or a launch per layer, fc_fwd

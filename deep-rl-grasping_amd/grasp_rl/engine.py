@@ -281,7 +281,7 @@ class SacEngine:
                 continue
             arr = np.asarray(params[name], dtype=np.float32)
             if int(arr.size) != numel:
-                raise GrlError("%s: expected %d values, got shape %s" % (name, numel, arr.shape))
+                raise GrlError("%s: expected shape %s (%d values), got shape %s" % (name, tuple(shape), numel, arr.shape))
             self.be.write(self._view(off, numel, shape), arr.reshape(shape))
         self.be.synchronize()
 

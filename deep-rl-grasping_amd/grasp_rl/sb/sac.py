@@ -158,14 +158,20 @@ class SAC(BaseModel):
                 raise ValueError("MlpPolicy expects vector observations, got shape %s" % (obs_shape,))
             cfg = _capi.make_config("mlp", obs_dim=obs_shape[0], **kw)
         else:
-            if len(obs_shape) != 3 or obs_shape[0] != 64 or obs_shape[1] != 64:
-                raise ValueError("CnnPolicy expects 64x64xC image observations, got %s" % (obs_shape,))
+            if len(obs_shape) != 3:
+                raise ValueError("CnnPolicy expects HxWxC image observations, got %s" % (obs_shape,))
+            if obs_shape[0] != obs_shape[1]:
+                raise ValueError("CnnPolicy expects square images: height %d and width %d differ (observation space %s)"
+                                 % (obs_shape[0], obs_shape[1], obs_shape))
+            if not 36 <= obs_shape[0] <= 128:
+                raise ValueError("CnnPolicy expects square images of 36x36 to 128x128, got %dx%d (observation space %s)"
+                                 % (obs_shape[0], obs_shape[1], obs_shape))
             if not sp.has_finite_bounds(self.observation_space) or np.any(self.observation_space.low != 0) \
                     or np.any(self.observation_space.high != 255):
                 raise NotImplementedError("image observation spaces other than Box(0, 255) are not implemented")
             if self.replay_rgb_u8 and obs_shape[2] - (1 if n_direct > 0 else 0) != 4:
                 raise ValueError("replay_rgb_u8 needs RGB-D observations (R, G, B, depth [+ pad channel])")
-            cfg = _capi.make_config(extractor, obs_channels=obs_shape[2], n_direct=n_direct,
+            cfg = _capi.make_config(extractor, obs_channels=obs_shape[2], n_direct=n_direct, img_hw=obs_shape[0],
                                     replay_rgb_u8=self.replay_rgb_u8, **kw)
         self._extractor = extractor
         if self.seed is not None and hasattr(self.action_space, "seed"):     # BaseRLModel.set_random_seed: action_space.seed(seed)

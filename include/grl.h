@@ -63,7 +63,11 @@ extern "C" {
 
 typedef struct grl_config {
   int32_t extractor;      /* GRL_EXTRACTOR_*                                                    */
-  int32_t img_hw;         /* 64 (config/camera_info.yaml:1-2)                                   */
+  int32_t img_hw;         /* side of the square camera image, 36 .. 128 (config/camera_info.yaml:1-2: 64).  64 runs the
+                             sample-local convolution stack, every other size one implicit-GEMM launch per layer; the
+                             extractor's dense kernel is [64 * o3 * o3, 512] with o1 = (hw - 8) / 4 + 1, o2 = (o1 - 4) / 2 + 1,
+                             o3 = o2 - 2 (TF 'VALID', divisions floor).  grl_query_sizes / grl_create refuse a size
+                             outside the range, and a size x batch whose largest buffer reaches 2^31 bytes          */
   int32_t obs_channels;   /* channels of the env observation: 2 depth, 5 RGB-D (robot.py:223-228) */
   int32_t n_direct;       /* direct features carried in the last channel (augmented only)       */
   int32_t obs_dim;        /* vector observation size (MLP extractor only).  DQN / BDQ handles: any size -- an image
