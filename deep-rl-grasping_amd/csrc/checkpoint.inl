@@ -11,9 +11,12 @@
 // lives and dies with the handle (act_done_seen against act_done_host), or belongs to a data-parallel connection, which is
 // set up anew after a restart (dp_*).  The prioritised-replay state is all in the replay arena (PerArgs holds addresses and
 // configuration constants only).
+// Shared with ppo_checkpoint.inl: CfgField (the row type of every field table), CfgBlock (a configuration struct of the handle with
+// its table: written, compared and hashed field by field), state_write_head / state_read_head (the header and the grl_config).
 
+struct CfgField { const char* name; size_t off, size; };
 #define GRL_CFG_FIELD(f) {#f, offsetof(grl_config, f), sizeof(((grl_config*)nullptr)->f)}
-static const struct { const char* name; size_t off, size; } k_cfg_fields[] = {
+static const CfgField k_cfg_fields[] = {
   GRL_CFG_FIELD(extractor), GRL_CFG_FIELD(img_hw), GRL_CFG_FIELD(obs_channels), GRL_CFG_FIELD(n_direct), GRL_CFG_FIELD(obs_dim),
   GRL_CFG_FIELD(act_dim), GRL_CFG_FIELD(n_layers), GRL_CFG_FIELD(layers), GRL_CFG_FIELD(batch_size), GRL_CFG_FIELD(act_batch),
   GRL_CFG_FIELD(replay_capacity), GRL_CFG_FIELD(normalize), GRL_CFG_FIELD(gamma), GRL_CFG_FIELD(lr), GRL_CFG_FIELD(tau),
@@ -31,14 +34,72 @@ static const struct { const char* name; size_t off, size; } k_cfg_fields[] = {
 // blobs of this layout existed, enters only when set: a blob written before the field existed hashes as it did then (its
 // configuration bytes hold zeros there) and is still accepted by a handle without layer normalisation.  The ae_* fields
 // (the auto-encoder's network, appended later still) follow the same rule: all zero -- the shipped network, cfg_ae_default in plan_ae.inl -- they stay out.
+static uint64_t fnv1a(uint64_t hsh, const char* p, size_t n) {
+  for (size_t k = 0; k < n; ++k) hsh = (hsh ^ (uint8_t)p[k]) * 0x100000001b3ull;
+  return hsh;
+}
 static uint64_t cfg_hash(const grl_config& c) {
   uint64_t hsh = 0xcbf29ce484222325ull;
   for (const auto& f : k_cfg_fields) {
     if (f.off == offsetof(grl_config, q_layer_norm) && c.q_layer_norm == 0) continue;
     if (f.off >= offsetof(grl_config, ae_kernel) && cfg_ae_default(c)) continue;
-    for (size_t k = 0; k < f.size; ++k) hsh = (hsh ^ ((const uint8_t*)&c)[f.off + k]) * 0x100000001b3ull;
+    hsh = fnv1a(hsh, (const char*)&c + f.off, f.size);
   }
   return hsh;
+}
+
+struct CfgBlock {
+  const CfgField* field; int n;
+  const char* base; size_t bytes;      // the handle's struct
+  const char* type;
+  // field by field into zeroed storage: the blob holds no padding bytes of the caller's struct
+  char* write(char* p) const {
+    memset(p, 0, bytes);
+    for (int f = 0; f < n; ++f) memcpy(p + field[f].off, base + field[f].off, field[f].size);
+    return p + bytes;
+  }
+  // refuses, by the name of the first field that differs, a block at `blob` that is not the handle's
+  int differs(const char* blob) const {
+    for (int f = 0; f < n; ++f)
+      if (memcmp(blob + field[f].off, base + field[f].off, field[f].size) != 0)
+        return fail(GRL_ERR_INVALID, std::string("state blob was written for another configuration: ") + type + "." + field[f].name + " differs");
+    return GRL_OK;
+  }
+  uint64_t hash(uint64_t hsh) const {
+    for (int f = 0; f < n; ++f) hsh = fnv1a(hsh, base + field[f].off, field[f].size);
+    return hsh;
+  }
+};
+static CfgBlock cfg_block(const grl_ctx* h) {
+  return {k_cfg_fields, (int)(sizeof(k_cfg_fields) / sizeof(k_cfg_fields[0])), (const char*)&h->cfg, sizeof(grl_config), "grl_config"};
+}
+
+// header + the zeroed grl_config of a blob of `total` bytes; returns where the next section starts
+static char* state_write_head(const grl_ctx* h, char* p, uint64_t hash, int64_t replay_pos, int64_t replay_size, size_t total) {
+  grl_state_header hd;
+  memset(&hd, 0, sizeof(hd));
+  hd.magic = GRL_STATE_MAGIC; hd.version = grl_version(); hd.layout = GRL_STATE_LAYOUT;
+  hd.config_bytes = (int32_t)sizeof(grl_config); hd.config_hash = hash;
+  hd.replay_pos = replay_pos; hd.replay_size = replay_size; hd.total_bytes = total;
+  memcpy(p, &hd, sizeof(hd));
+  return cfg_block(h).write(p + sizeof(hd));
+}
+// The header of a blob of n bytes, checked (magic, versions, size of its grl_config, length: at least `tail` bytes behind the
+// configuration, and what the header says), and its grl_config into zeroed `c`.  short_cfg: a blob written before the ae_* fields
+// were appended holds the struct up to them -- they read as zeros, the shipped network.  *p: where the next section starts.
+static int state_read_head(const char** p, size_t n, bool short_cfg, size_t tail, grl_state_header& hd, grl_config& c) {
+  if (n < sizeof(hd)) return fail(GRL_ERR_INVALID, "state blob is truncated (no header)");
+  memcpy(&hd, *p, sizeof(hd)); *p += sizeof(hd);
+  if (hd.magic != GRL_STATE_MAGIC) return fail(GRL_ERR_INVALID, "not a grl state blob (wrong magic)");
+  if (hd.version != grl_version())
+    return fail(GRL_ERR_INVALID, "state blob written by library version " + std::to_string(hd.version) + ", this is " + std::to_string(grl_version()));
+  if (hd.layout != GRL_STATE_LAYOUT) return fail(GRL_ERR_INVALID, "state blob has layout version " + std::to_string(hd.layout) + ", expected " + std::to_string(GRL_STATE_LAYOUT));
+  const size_t csz = (size_t)hd.config_bytes;
+  if (csz != sizeof(grl_config) && !(short_cfg && csz == offsetof(grl_config, ae_kernel))) return fail(GRL_ERR_INVALID, "state blob holds a grl_config of another size");
+  if (n < sizeof(hd) + csz + tail || hd.total_bytes != n) return fail(GRL_ERR_INVALID, "state blob is truncated (" + std::to_string(n) + " of " + std::to_string(hd.total_bytes) + " bytes)");
+  memset(&c, 0, sizeof(c));
+  memcpy(&c, *p, csz); *p += csz;
+  return GRL_OK;
 }
 
 struct StateHost {     // follows the header and the grl_config in the blob
@@ -64,17 +125,7 @@ int64_t grl_state_export(grl_handle h, void* host_buf, size_t cap) {
   const size_t total = state_bytes_now(h);
   if (cap < total) return fail(GRL_ERR_INVALID, "state buffer too small: " + std::to_string(total) + " bytes needed");
   HIPCHK(hipStreamSynchronize(h->stream));
-  char* p = (char*)host_buf;
-  grl_state_header hd;
-  memset(&hd, 0, sizeof(hd));
-  hd.magic = GRL_STATE_MAGIC; hd.version = grl_version(); hd.layout = GRL_STATE_LAYOUT;
-  hd.config_bytes = (int32_t)sizeof(grl_config); hd.config_hash = cfg_hash(h->cfg);
-  hd.replay_pos = h->rp_pos; hd.replay_size = h->rp_size; hd.total_bytes = total;
-  memcpy(p, &hd, sizeof(hd)); p += sizeof(hd);
-  grl_config c;                      // field by field into zeroed storage: the blob holds no padding bytes of the caller's struct
-  memset(&c, 0, sizeof(c));
-  for (const auto& f : k_cfg_fields) memcpy((char*)&c + f.off, (const char*)&h->cfg + f.off, f.size);
-  memcpy(p, &c, sizeof(c)); p += sizeof(c);
+  char* p = state_write_head(h, (char*)host_buf, cfg_hash(h->cfg), h->rp_pos, h->rp_size, total);
   StateHost sh;
   memset(&sh, 0, sizeof(sh));
   sh.n_parity = h->n_parity; sh.ob_n = h->ob_n; sh.ob_n_prev = h->ob_n_prev; sh.ob_elems = h->ob_elems;
@@ -91,23 +142,10 @@ int grl_state_import(grl_handle h, const void* host_buf, size_t n) {
   if (!h || !host_buf) return fail(GRL_ERR_INVALID, "null argument");
   const char* p = (const char*)host_buf;
   grl_state_header hd;
-  if (n < sizeof(hd)) return fail(GRL_ERR_INVALID, "state blob is truncated (no header)");
-  memcpy(&hd, p, sizeof(hd)); p += sizeof(hd);
-  if (hd.magic != GRL_STATE_MAGIC) return fail(GRL_ERR_INVALID, "not a grl state blob (wrong magic)");
-  if (hd.version != grl_version())
-    return fail(GRL_ERR_INVALID, "state blob written by library version " + std::to_string(hd.version) + ", this is " + std::to_string(grl_version()));
-  if (hd.layout != GRL_STATE_LAYOUT) return fail(GRL_ERR_INVALID, "state blob has layout version " + std::to_string(hd.layout) + ", expected " + std::to_string(GRL_STATE_LAYOUT));
-  // (a blob written before the ae_* fields were appended holds the struct up to them: they read as zeros, the shipped network)
-  const size_t csz = (size_t)hd.config_bytes;
-  if (csz != sizeof(grl_config) && csz != offsetof(grl_config, ae_kernel)) return fail(GRL_ERR_INVALID, "state blob holds a grl_config of another size");
-  const size_t fixed = sizeof(hd) + csz + sizeof(StateHost);
-  if (n < fixed || hd.total_bytes != n) return fail(GRL_ERR_INVALID, "state blob is truncated (" + std::to_string(n) + " of " + std::to_string(hd.total_bytes) + " bytes)");
   grl_config c;
-  memset(&c, 0, sizeof(c));
-  memcpy(&c, p, csz); p += csz;
-  for (const auto& f : k_cfg_fields)
-    if (memcmp((const char*)&c + f.off, (const char*)&h->cfg + f.off, f.size) != 0)
-      return fail(GRL_ERR_INVALID, std::string("state blob was written for another configuration: grl_config.") + f.name + " differs");
+  if (int e = state_read_head(&p, n, true, sizeof(StateHost), hd, c)) return e;
+  const size_t fixed = (size_t)(p - (const char*)host_buf) + sizeof(StateHost);
+  if (int e = cfg_block(h).differs((const char*)&c)) return e;
   if (hd.config_hash != cfg_hash(h->cfg)) return fail(GRL_ERR_INVALID, "state blob is damaged (configuration hash)");
   StateHost sh;
   memcpy(&sh, p, sizeof(sh)); p += sizeof(sh);

@@ -1507,6 +1507,86 @@ struct grl_ctx {
     }
   }
 
+  // ---------------------------------------------------------------- launch constructors the plans share
+  // the slab reduction over `n` tiles of `d` (+ the loss workgroup where has_loss); apply: Adam + Polyak where the sums are formed
+  static Op reduce_op(const char* tag, const ReduceDesc* d, const int2* tiles, int n, const LossArgs& la, int has_loss, const AdamArgs& aa,
+                      int apply) {
+    Op op; op.tag = tag;
+    op.run = [d, tiles, n, la, has_loss, aa, apply](hipStream_t s) {
+      hipLaunchKernelGGL(reduce_slabs_kernel, dim3(n + has_loss), dim3(256), 0, s, d, tiles, n, la, has_loss, aa, apply);
+    };
+    return op;
+  }
+  // ... closing a backward pass that only sums: the descriptors listed in `reduces` (marked for 16-byte accesses before they go
+  // up) and their tiles into the work arena.  Without the apply flag the kernel uses nothing of its AdamArgs: the empty struct.
+  struct SumPlan { Op op; ReduceDesc* descs; const int2* tiles; int n; };
+  SumPlan close_reduction() {
+    const std::vector<int2> rt = reduce_tiles();
+    ReduceDesc* d = upload_vec(wk, reduces);
+    const int2* tiles = upload_vec(wk, rt);
+    LossArgs none;
+    memset(&none, 0, sizeof(none));
+    return {reduce_op("reduce_slabs", d, tiles, (int)rt.size(), none, 0, AdamArgs{}, 0), d, tiles, (int)rt.size()};
+  }
+  // Adam over the whole trainable range as a launch of its own; the arguments are formed when it runs (scaled: with the call's
+  // grad_scale, else 1)
+  Op adam_op(const char* tag, float eps, bool polyak, bool scaled) {
+    grl_ctx* self = this;
+    Op op; op.tag = tag;
+    op.run = [self, eps, polyak, scaled](hipStream_t s) {
+      const AdamArgs aa = self->adam_args(scaled ? self->grad_scale : 1.f, polyak, eps);
+      const int blocks = (int)std::min<int64_t>(2048, (self->n_train + 255) / 256);
+      hipLaunchKernelGGL(adam_polyak_kernel, dim3(blocks), dim3(256), 0, s, aa);
+    };
+    return op;
+  }
+  // Weight + bias gradients of one stack of dense layers over `rows` rows -- L hidden layers (activations z, gradients gz), then
+  // its output layer where n_out > 0 -- as problems of one launch: the slabs from the work arena, their sums into `dst` (nullptr:
+  // the gradient bucket).  An input whose rows are padded to a multiple of 4 floats carries the padding columns along: every
+  // problem then fits the vectorised weight-gradient kernel; their slab rows are never reduced.
+  void add_stack_wgrads(std::vector<IgemmProb>& wg, const float* x, int ldx, int kin, float* const* z, float* const* gz, const int* width, int L,
+                        const float* gout, int ld_gout, int n_out, const int64_t* w, const int64_t* b, int rows, float* dst = nullptr) {
+    auto layer = [&](const float* g, int ldg, int n, int64_t woff, int64_t boff) {
+      IgemmProb p = dense_wgrad(x, ldx, kin, true, g, ldg, n, rows, nullptr, 1, ldx >= (int)rup(kin, 4) ? (int)rup(kin, 4) : kin);
+      p.c = wk.f32(p.slab_stride * p.split);
+      add_wgrad(wg, p, woff, 0, kin, boff, dst);
+    };
+    for (int l = 0; l < L; ++l) {
+      layer(gz[l], width[l], width[l], w[l], b[l]);
+      x = z[l]; ldx = kin = width[l];
+    }
+    if (n_out > 0) layer(gout, ld_gout, n_out, w[L], b[L]);
+  }
+  // Clip + Adam over a tile table of the trainable variables (q_wide_kernels.h): q_sumsq, then q_clip_adam; returns the tile count.
+  //   one_run  every tile names the whole run of partial sums: ONE norm over the bucket (PPO2) instead of one per variable
+  //   scaled   data parallel: the sum of the replicas is clipped at clip / grad_scale and Adam's grad_scale brings it back
+  int add_clip_adam(std::vector<Op>& ops, const std::vector<VarSeg>& segs, float clip, float eps, bool one_run, bool scaled) {
+    std::vector<QwTile> tl = qw_build_tiles(segs.data(), (int)segs.size());
+    if (one_run)
+      for (auto& t : tl) { t.p0 = 0; t.np = (int32_t)tl.size(); }
+    const QwTile* d_tl = upload_vec(wk, tl);
+    const int n_tl = (int)tl.size();
+    float* part = wk.f32(n_tl);
+    float* g = grads;
+    grl_ctx* self = this;
+    Op op; op.tag = "q_sumsq";
+    op.run = [g, d_tl, n_tl, part](hipStream_t s) { launch_q_sumsq(g, d_tl, n_tl, part, s); };
+    ops.push_back(op);
+    Op oa; oa.tag = "q_clip_adam";
+    oa.run = [self, g, d_tl, n_tl, part, clip, eps, scaled](hipStream_t s) {
+      const float scale = scaled ? self->grad_scale : 1.f;
+      launch_q_clip_adam(g, d_tl, n_tl, part, scaled ? clip / scale : clip, self->adam_args(scale, false, eps), s);
+    };
+    ops.push_back(oa);
+    return n_tl;
+  }
+  std::vector<VarSeg> trainable_segs() const {
+    std::vector<VarSeg> segs;
+    for (auto& v : vars)
+      if (v.trainable) segs.push_back({v.off, v.numel});
+    return segs;
+  }
+
   void alloc_head(HeadAct& h, int rows, int n_out, int out_dim) {
     for (int l = 0; l < L; ++l) h.z[l] = wk.f32((int64_t)rows * hid[l]);
     for (int k = 0; k < n_out; ++k) h.out[k] = wk.f32((int64_t)rows * out_dim);

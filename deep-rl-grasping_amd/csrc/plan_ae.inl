@@ -383,26 +383,10 @@ int grl_ctx::plan_ae() {
     add_launch(ops_ae, "ae_wgrad_small", 2, rest);
     add_launch(ops_ae, "ae_wgrad_dense", 2, wgd);
   }
-  {
-    std::vector<int2> rt = reduce_tiles();
-    d_reduces = upload_vec(wk, reduces);
-    int2* d_rt = upload_vec(wk, rt);
-    const int ntiles = (int)rt.size();
-    ReduceDesc* dr = d_reduces;
-    LossArgs none;
-    memset(&none, 0, sizeof(none));
-    elem("reduce_slabs", [=](hipStream_t s) {
-      hipLaunchKernelGGL(reduce_slabs_kernel, dim3(ntiles), dim3(256), 0, s, dr, d_rt, ntiles, none, 0, AdamArgs{}, 0);
-    });
-  }
-  {
-    grl_ctx* self = this;
-    elem("adam", [self](hipStream_t s) {
-      const AdamArgs aa = self->adam_args(1.f, false, 1e-7f);   // Keras epsilon
-      const int blocks = (int)std::min<int64_t>(2048, (self->n_train + 255) / 256);
-      hipLaunchKernelGGL(adam_polyak_kernel, dim3(blocks), dim3(256), 0, s, aa);
-    });
-  }
+  const SumPlan sum = close_reduction();
+  d_reduces = sum.descs;
+  ops_ae.push_back(sum.op);
+  ops_ae.push_back(adam_op("adam", 1e-7f, false, false));   // Keras epsilon
   // =============================================================== encode path (batch NA) on the trained weights
   {
     ex_in = wk.f32((int64_t)NA * 4096);
@@ -709,26 +693,10 @@ int grl_ctx::plan_ae_general(const AeNet& net) {
     launch(ops_ae, "ae_wgrad_small", 2, rest, "wgrad");
     launch(ops_ae, "ae_wgrad_dense", 2, wgd, "");
   }
-  {
-    std::vector<int2> rt = reduce_tiles();
-    d_reduces = upload_vec(wk, reduces);
-    int2* d_rt = upload_vec(wk, rt);
-    const int ntiles = (int)rt.size();
-    ReduceDesc* dr = d_reduces;
-    LossArgs none;
-    memset(&none, 0, sizeof(none));
-    elem(ops_ae, "reduce_slabs", [=](hipStream_t s) {
-      hipLaunchKernelGGL(reduce_slabs_kernel, dim3(ntiles), dim3(256), 0, s, dr, d_rt, ntiles, none, 0, AdamArgs{}, 0);
-    });
-  }
-  {
-    grl_ctx* self = this;
-    elem(ops_ae, "adam", [self](hipStream_t s) {
-      const AdamArgs aa = self->adam_args(1.f, false, 1e-7f);   // Keras epsilon
-      const int blocks = (int)std::min<int64_t>(2048, (self->n_train + 255) / 256);
-      hipLaunchKernelGGL(adam_polyak_kernel, dim3(blocks), dim3(256), 0, s, aa);
-    });
-  }
+  const SumPlan sum = close_reduction();
+  d_reduces = sum.descs;
+  ops_ae.push_back(sum.op);
+  ops_ae.push_back(adam_op("adam", 1e-7f, false, false));   // Keras epsilon
   // =============================================================== encode path (batch NA) on the trained weights
   {
     ex_in = wk.f32((int64_t)NA * 4096);

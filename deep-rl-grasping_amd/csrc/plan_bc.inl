@@ -218,18 +218,7 @@ struct BcPlanner {
 
   // slabs -> the gradient bucket (sums in slab order), then Adam over the trained range
   void reduce_and_apply() {
-    std::vector<int2> rt = h.reduce_tiles();          // (marks the 16-byte-eligible descriptors: before the upload)
-    const ReduceDesc* dr = h.upload_vec(wk, h.reduces);
-    const int2* d_rt = h.upload_vec(wk, rt);
-    const int ntiles = (int)rt.size();
-    LossArgs la;
-    memset(&la, 0, sizeof(la));
-    const AdamArgs none = h.adam_args(1.f, true);     // (not applied: the launch only sums)
-    Op op; op.tag = "reduce_slabs";
-    op.run = [dr, d_rt, ntiles, la, none](hipStream_t s) {
-      hipLaunchKernelGGL(reduce_slabs_kernel, dim3(ntiles), dim3(256), 0, s, dr, d_rt, ntiles, la, 0, none, 0);
-    };
-    tail.push_back(op);
+    tail.push_back(h.close_reduction().op);            // (into the session buffer: it stands in for the work arena here)
     BcAdamArgs aa{h.params, h.grads, p.m, p.v, p.n_bc, p.dev, p.cfg.adam_eps};
     const int blocks = (int)std::min<int64_t>(2048, (p.n_bc + 255) / 256);
     Op oa; oa.tag = "bc_adam";

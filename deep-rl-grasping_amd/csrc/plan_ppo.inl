@@ -3,6 +3,8 @@
 // backward-data / weight-gradient builders of the per-layer Q route, the two towers of a layer level sharing a launch; the slab
 // reduction is reduce_slabs_kernel; the global-norm clip + Adam are q_sumsq_kernel + q_clip_adam_kernel over a tile table whose
 // tiles all name the same run of partial sums.  One lane, no forks: the lists run through run_seq / run_repeated like every plan.
+// Shared: forward / backward take a tower mask and add_gather builds the minibatch gather -- plan_trpo.inl runs all three; the slab
+// reduction, the stack weight gradients, clip + Adam and Adam come from grl_ctx (close_reduction, add_stack_wgrads, add_clip_adam, adam_op).
 //
 //   act path     model.step / model.value / model.predict on act_batch rows: ONE launch (ppo_act_kernel) for observations up to
 //                2048 values and widths up to 256, else dense levels + tanh launches + the output launch + ppo_sample_kernel
@@ -284,25 +286,64 @@ struct PpoPlanner {
   }
 
   // ---------------- one minibatch update
-  void add_reduce(const float* src, int splits, int64_t slab_stride, int64_t off, int n) {
-    ReduceDesc rd;
-    memset(&rd, 0, sizeof(rd));
-    rd.src = src; rd.splits = splits; rd.slab_stride = slab_stride; rd.dst = h.grads + off; rd.n = n;
-    h.reduces.push_back(rd);
+  // the minibatch PpoDev.cursor names: its rows of the rollout into mb_* (plan_trpo.inl: the value fit's minibatches)
+  void add_gather(std::vector<Op>& ops) {
+    PpoGatherArgs g;
+    memset(&g, 0, sizeof(g));
+    g.perm = h.ppo_perm; g.dev = h.ppo_dev; g.sc = h.sc;
+    g.r_obs = h.pr_obs; g.ldo = ldo; g.r_act = h.pr_act; g.r_oldv = h.pr_val; g.r_oldnlp = h.pr_nlp; g.r_adv = h.pr_adv; g.r_ret = h.pr_ret;
+    g.x = mb_x; g.act = mb_act; g.oldv = mb_oldv; g.oldnlp = mb_oldnlp; g.adv = mb_adv; g.ret = mb_ret;
+    g.mb = B; g.A = A;
+    Op op; op.tag = "ppo_gather";
+    op.run = [g](hipStream_t s) { launch_ppo_gather(g, s); };
+    ops.push_back(op);
+  }
+  // Backward of the towers in `towers` (as forward) over `rows` rows of x, activations in act, output gradients in gr.  Backward-data
+  // level by level from the outputs down, the towers of a level sharing a launch `tag`_bwd (the gradient w.r.t. a layer's OUTPUT,
+  // then tanh_bwd turns it, in place, into the gradient w.r.t. its pre-activation; nothing flows into the observations); the
+  // weight gradients of every layer as ONE launch `tag`_wgrad; their slabs -- and the dls_blocks partial sums of d logstd in `dls`,
+  // if any -- summed into the bucket-shaped dst by a reduction launch of its own.  Returns that launch's descriptors.
+  ReduceDesc* backward(std::vector<Op>& ops, const std::string& tag, int towers, int rows, const float* x, const PpoActs& act, const PpoActs& gr,
+                       float* dst, const float* dls, int dls_blocks) {
+    auto on = [&](int tw) { return ((towers >> tw) & 1) != 0; };
+    const int depth = std::max(on(0) ? T[0].L() : 0, on(1) ? T[1].L() : 0);
+    for (int s = 0; s < depth; ++s) {
+      std::vector<IgemmProb> pr;
+      std::vector<TanhDesc> td;
+      for (int tw = 0; tw < 2; ++tw) {
+        const int l = T[tw].L() - 1 - s;
+        if (!on(tw) || l < 0) continue;
+        const grl_ctx::BwdPart above = s == 0 ? grl_ctx::BwdPart{gr.out[tw], gr.ld_out[tw], T[tw].out, P + T[tw].w[l + 1]}
+                                              : grl_ctx::BwdPart{gr.z[tw][l + 1], T[tw].width[l + 1], T[tw].width[l + 1], P + T[tw].w[l + 1]};
+        pr.push_back(h.dense_bwd({above}, rows, 0, T[tw].width[l], gr.z[tw][l], T[tw].width[l], nullptr));
+        TanhDesc d;
+        memset(&d, 0, sizeof(d));
+        d.z = act.z[tw][l]; d.dz = gr.z[tw][l]; d.H = T[tw].width[l];
+        td.push_back(d);
+      }
+      h.add_launch(ops, tag + "_bwd", 1, pr);
+      add_tanh(ops, "ppo_tanh_bwd", true, td, rows);
+    }
+    h.reduces.clear();      // (every backward has a reduction launch of its own)
+    std::vector<IgemmProb> wg;
+    for (int tw = 0; tw < 2; ++tw)
+      if (on(tw))
+        h.add_stack_wgrads(wg, x, ldo, od, act.z[tw], gr.z[tw], T[tw].width.data(), T[tw].L(), gr.out[tw], gr.ld_out[tw], T[tw].out, T[tw].w, T[tw].b,
+                           rows, dst);
+    h.add_launch(ops, tag + "_wgrad", 2, wg);
+    if (dls) {
+      ReduceDesc rd;
+      memset(&rd, 0, sizeof(rd));
+      rd.src = dls; rd.splits = dls_blocks; rd.slab_stride = A; rd.dst = dst + logstd_off; rd.n = A;
+      h.reduces.push_back(rd);
+    }
+    const grl_ctx::SumPlan sum = h.close_reduction();
+    ops.push_back(sum.op);
+    return sum.descs;
   }
   void update() {
     std::vector<Op>& ops = h.ops_ppo_update;
-    {
-      PpoGatherArgs g;
-      memset(&g, 0, sizeof(g));
-      g.perm = h.ppo_perm; g.dev = h.ppo_dev; g.sc = h.sc;
-      g.r_obs = h.pr_obs; g.ldo = ldo; g.r_act = h.pr_act; g.r_oldv = h.pr_val; g.r_oldnlp = h.pr_nlp; g.r_adv = h.pr_adv; g.r_ret = h.pr_ret;
-      g.x = mb_x; g.act = mb_act; g.oldv = mb_oldv; g.oldnlp = mb_oldnlp; g.adv = mb_adv; g.ret = mb_ret;
-      g.mb = B; g.A = A;
-      Op op; op.tag = "ppo_gather";
-      op.run = [g](hipStream_t s) { launch_ppo_gather(g, s); };
-      ops.push_back(op);
-    }
+    add_gather(ops);
     forward(ops, mb_x, B, act_mb, "ppo_fwd");
     {
       PpoLossArgs a;
@@ -317,85 +358,15 @@ struct PpoPlanner {
       op.run = [a](hipStream_t s) { launch_ppo_loss(a, s); };
       ops.push_back(op);
     }
-    // backward-data, level by level from the outputs down (the gradient w.r.t. a layer's OUTPUT, then tanh_bwd turns it, in place,
-    // into the gradient w.r.t. its pre-activation); nothing flows into the observations
-    for (int s = 0; s < std::max(T[0].L(), T[1].L()); ++s) {
-      std::vector<IgemmProb> pr;
-      std::vector<TanhDesc> td;
-      for (int tw = 0; tw < 2; ++tw) {
-        const int l = T[tw].L() - 1 - s;
-        if (l < 0) continue;
-        const grl_ctx::BwdPart above = s == 0 ? grl_ctx::BwdPart{g_mb.out[tw], g_mb.ld_out[tw], T[tw].out, P + T[tw].w[l + 1]}
-                                              : grl_ctx::BwdPart{g_mb.z[tw][l + 1], T[tw].width[l + 1], T[tw].width[l + 1], P + T[tw].w[l + 1]};
-        pr.push_back(h.dense_bwd({above}, B, 0, T[tw].width[l], g_mb.z[tw][l], T[tw].width[l], nullptr));
-        TanhDesc d;
-        memset(&d, 0, sizeof(d));
-        d.z = act_mb.z[tw][l]; d.dz = g_mb.z[tw][l]; d.H = T[tw].width[l];
-        td.push_back(d);
-      }
-      h.add_launch(ops, "ppo_bwd", 1, pr);
-      add_tanh(ops, "ppo_tanh_bwd", true, td, B);
-    }
-    // weight gradients of every layer of both towers as one launch (inputs whose rows are padded to 4 floats carry the padding along)
-    std::vector<IgemmProb> wg;
-    auto wgrad = [&](const float* x, int ldx, int kin, const float* g, int ldg, int n, int64_t woff, int64_t boff) {
-      IgemmProb p = h.dense_wgrad(x, ldx, kin, true, g, ldg, n, B, nullptr, 1, ldx >= (int)rup(kin, 4) ? (int)rup(kin, 4) : kin);
-      p.c = h.wk.f32(p.slab_stride * p.split);
-      h.add_wgrad(wg, p, woff, 0, kin, boff);
-    };
-    for (int tw = 0; tw < 2; ++tw) {
-      const float* x = mb_x; int ldx = ldo, k = od;
-      for (int l = 0; l < T[tw].L(); ++l) {
-        wgrad(x, ldx, k, g_mb.z[tw][l], T[tw].width[l], T[tw].width[l], T[tw].w[l], T[tw].b[l]);
-        x = act_mb.z[tw][l]; ldx = k = T[tw].width[l];
-      }
-      wgrad(x, ldx, k, g_mb.out[tw], g_mb.ld_out[tw], T[tw].out, T[tw].w[T[tw].L()], T[tw].b[T[tw].L()]);
-    }
-    h.add_launch(ops, "ppo_wgrad", 2, wg);
-    add_reduce(dls_slab, nblk, A, logstd_off, A);      // d logstd is in the bucket before the norm is formed
-    {
-      std::vector<int2> rt = h.reduce_tiles();
-      h.d_reduces = h.upload_vec(h.wk, h.reduces);
-      int2* d_rt = h.upload_vec(h.wk, rt);
-      const int ntiles = (int)rt.size();
-      ReduceDesc* dr = h.d_reduces;
-      LossArgs none;
-      memset(&none, 0, sizeof(none));
-      Op op; op.tag = "reduce_slabs";
-      op.run = [dr, d_rt, ntiles, none](hipStream_t s) {
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3(ntiles), dim3(256), 0, s, dr, d_rt, ntiles, none, 0, AdamArgs{}, 0);
-      };
-      ops.push_back(op);
-    }
+    // (d logstd is in the bucket before the norm is formed)
+    h.d_reduces = backward(ops, "ppo", 3, B, mb_x, act_mb, g_mb, h.grads, dls_slab, nblk);
     // clip_by_global_norm + Adam: the tiles of q_wide_kernels.h with ONE run of partial sums for all of them -- every tile adds all
     // partials in index order and forms clip / max(||g||, clip) over the whole bucket (TF-Adam, epsilon from grl_ppo_config)
-    grl_ctx* self = &h;
-    const float eps = pc.adam_eps;
     if (pc.max_grad_norm > 0.f) {
-      std::vector<VarSeg> segs;
-      for (auto& v : h.vars)
-        if (v.trainable) segs.push_back({v.off, v.numel});
-      std::vector<QwTile> tl = qw_build_tiles(segs.data(), (int)segs.size());
-      for (auto& t : tl) { t.p0 = 0; t.np = (int32_t)tl.size(); }
-      const QwTile* d_tl = h.upload_vec(h.wk, tl);
-      const int n_tl = (int)tl.size();
-      float* part = h.wk.f32(n_tl);
-      float* g = h.grads; const float clip = pc.max_grad_norm;
-      Op op; op.tag = "q_sumsq";
-      op.run = [g, d_tl, n_tl, part](hipStream_t s) { launch_q_sumsq(g, d_tl, n_tl, part, s); };
-      ops.push_back(op);
-      Op oa; oa.tag = "q_clip_adam";
-      oa.run = [self, g, d_tl, n_tl, part, clip, eps](hipStream_t s) { launch_q_clip_adam(g, d_tl, n_tl, part, clip, self->adam_args(1.f, false, eps), s); };
-      ops.push_back(oa);
-      plan_note("grl plan: ppo apply     q_sumsq + q_clip_adam over %d tiles sharing one run of partial sums (global norm %g)\n", n_tl, clip);
+      const int n_tl = h.add_clip_adam(ops, h.trainable_segs(), pc.max_grad_norm, pc.adam_eps, true, false);
+      plan_note("grl plan: ppo apply     q_sumsq + q_clip_adam over %d tiles sharing one run of partial sums (global norm %g)\n", n_tl, pc.max_grad_norm);
     } else {
-      Op op; op.tag = "adam";
-      op.run = [self, eps](hipStream_t s) {
-        const AdamArgs aa = self->adam_args(1.f, false, eps);
-        const int blocks = (int)std::min<int64_t>(2048, (self->n_train + 255) / 256);
-        hipLaunchKernelGGL(adam_polyak_kernel, dim3(blocks), dim3(256), 0, s, aa);
-      };
-      ops.push_back(op);
+      ops.push_back(h.adam_op("adam", pc.adam_eps, false, false));
     }
   }
 

@@ -656,44 +656,24 @@ struct QPlanner {
   // weight gradients (not here when the chained backward has formed them)
   void weight_grads() {
     std::vector<IgemmProb> wg;
-    // (inputs whose rows are padded to a multiple of 4 floats -- the observations, ldf -- carry the padding columns along:
-    //  every problem then fits the vectorised weight-gradient kernel; their slab rows are never reduced)
-    auto wgrad = [&](const float* x, int ldx, int kin, const float* g, int ldg, int n, int64_t woff, int64_t boff) {
-      IgemmProb p = h.dense_wgrad(x, ldx, kin, true, g, ldg, n, B, nullptr, 1, ldx >= (int)rup(kin, 4) ? (int)rup(kin, 4) : kin);
-      p.c = h.wk.f32(p.slab_stride * p.split);
-      h.add_wgrad(wg, p, woff, 0, kin, boff);
-    };
-    QIn in{h.feat[0], ldf, c.obs_dim}, trunk_end = in;
+    // the trunk (no output layer) reads the observations, every tower the trunk's end
+    const QIn obs{h.feat[0], ldf, c.obs_dim}, trunk_end = Lc > 0 ? QIn{net[0].trunk.z[Lc - 1], hdim, hdim} : obs;
     for (int i = 0; i < on.n_stacks(); ++i) {
       const QStack& T = on.stack(i);
       const QStackAct &a = net[0].stack(i), &g = gact.stack(i);
-      if (i > 0) in = trunk_end;
-      for (int l = 0; l < T.L(); ++l) {
-        wgrad(in.x, in.ld, in.k, g.z[l], T.width[l], T.width[l], T.w[l], T.b[l]);
-        in = QIn{a.z[l], T.width[l], T.width[l]};
-      }
-      if (i == 0) trunk_end = in;
-      else wgrad(in.x, in.ld, in.k, g.out, g.ld_out, T.out, T.w[T.L()], T.b[T.L()]);
+      const QIn& in = i == 0 ? obs : trunk_end;
+      h.add_stack_wgrads(wg, in.x, in.ld, in.k, a.z.data(), g.z.data(), T.width.data(), T.L(), g.out, g.ld_out, T.out, T.w.data(), T.b.data(), B);
     }
     h.add_launch(h.ops_grads, "q_wgrad", 2, wg);
   }
 
   // =============================================================== slab reduction, then clip + Adam as launches of their own
   void reduction() {
-    std::vector<int2> rt = h.reduce_tiles();
-    h.d_reduces = h.upload_vec(h.wk, h.reduces);
-    int2* d_rt = h.upload_vec(h.wk, rt);
-    const int ntiles = (int)rt.size();
-    ReduceDesc* dr = h.d_reduces;
-    Op op; op.tag = "reduce_slabs";
-    LossArgs none;
-    memset(&none, 0, sizeof(none));
-    op.run = [dr, d_rt, ntiles, none](hipStream_t s) {
-      hipLaunchKernelGGL(reduce_slabs_kernel, dim3(ntiles), dim3(256), 0, s, dr, d_rt, ntiles, none, 0, AdamArgs{}, 0);
-    };
-    h.ops_grads.push_back(op);
+    const grl_ctx::SumPlan sum = h.close_reduction();
+    h.d_reduces = sum.descs;
+    h.ops_grads.push_back(sum.op);
     // (the in-graph exchange publishes from this reduction: capi.inl, grl_allreduce_connect)
-    h.red_all.tiles = d_rt; h.red_all.n = ntiles; h.red_all.has_loss = 0;
+    h.red_all.tiles = sum.tiles; h.red_all.n = sum.n; h.red_all.has_loss = 0;
     AdamArgs& ab = h.adam_base;
     memset(&ab, 0, sizeof(ab));
     ab.params = h.params; ab.grads = h.grads; ab.m = h.adam_m; ab.v = h.adam_v; ab.n_train = h.n_train; ab.sc = h.sc;
@@ -701,26 +681,13 @@ struct QPlanner {
     memset(&h.loss_args, 0, sizeof(h.loss_args));
   }
   void apply() {
-    std::vector<VarSeg> segs;      // the trainable variables
-    for (auto& v : h.vars)
-      if (v.trainable) segs.push_back({v.off, v.numel});
+    const std::vector<VarSeg> segs = h.trainable_segs();
     float* g = h.grads; const float clip = c.q_grad_clip;
     grl_ctx* self = &h;
     if (r.wide && clip > 0.f) {
       // wide handle: clip_by_norm (one workgroup per variable) + Adam become two launches over a tile table (q_wide_kernels.h).
       // Data parallel: as below, the sum of the replicas is clipped at clip / grad_scale and Adam's 1 / W brings it back.
-      const std::vector<QwTile> tl = qw_build_tiles(segs.data(), (int)segs.size());
-      const QwTile* d_tl = h.upload_vec(h.wk, tl);
-      const int n_tl = (int)tl.size();
-      float* part = h.wk.f32(n_tl);
-      Op op; op.tag = "q_sumsq";
-      op.run = [g, d_tl, n_tl, part](hipStream_t s) { launch_q_sumsq(g, d_tl, n_tl, part, s); };
-      h.ops_apply.push_back(op);
-      Op oa; oa.tag = "q_clip_adam";
-      oa.run = [self, g, d_tl, n_tl, part, clip](hipStream_t s) {
-        launch_q_clip_adam(g, d_tl, n_tl, part, clip / self->grad_scale, self->adam_args(self->grad_scale, false), s);
-      };
-      h.ops_apply.push_back(oa);
+      const int n_tl = h.add_clip_adam(h.ops_apply, segs, clip, 1e-8f, false, true);
       plan_note("grl plan: q_wide        apply: q_sumsq + q_clip_adam, %d tiles of <= %d floats over %zu variables; q_l0: %d partial sums (B %d, K %d)\n",
                 n_tl, QW_TILE, segs.size(), std::max(1, q_l0_split), B, c.obs_dim);
       return;
@@ -736,13 +703,7 @@ struct QPlanner {
       };
       h.ops_apply.push_back(op);
     }
-    Op op; op.tag = "adam";
-    op.run = [self](hipStream_t s) {
-      const AdamArgs aa = self->adam_args(self->grad_scale, false);
-      const int blocks = (int)std::min<int64_t>(2048, (self->n_train + 255) / 256);
-      hipLaunchKernelGGL(adam_polyak_kernel, dim3(blocks), dim3(256), 0, s, aa);
-    };
-    h.ops_apply.push_back(op);
+    h.ops_apply.push_back(h.adam_op("adam", 1e-8f, false, true));
   }
 
   // =============================================================== full updates: reduction + clip + Adam as one launch

@@ -903,14 +903,7 @@ struct SacPlanner {
 
   // the slab reduction over `n` tiles (+ the loss workgroup), optionally applying Adam + Polyak where the sums are formed
   Op reduce_op(const char* tag, const int2* tiles, int n, int loss, int apply) const {
-    Op op; op.tag = tag;
-    const ReduceDesc* d = dr;
-    const LossArgs la = h.loss_args;
-    const AdamArgs ad = aa;
-    op.run = [d, tiles, n, la, loss, ad, apply](hipStream_t s) {
-      hipLaunchKernelGGL(reduce_slabs_kernel, dim3(n + loss), dim3(256), 0, s, d, tiles, n, la, loss, ad, apply);
-    };
-    return op;
+    return grl_ctx::reduce_op(tag, dr, tiles, n, h.loss_args, loss, aa, apply);
   }
 
   // =============================================================== reductions: the one that ends the gradient computation (the
@@ -1036,14 +1029,8 @@ struct SacPlanner {
 
   // =============================================================== apply (a launch of its own: split API, exchanged gradients)
   void apply() {
-    Op op; op.tag = "adam_polyak";
+    Op op = h.adam_op("adam_polyak", 1e-8f, true, true);
     op.bytes = (double)h.n_train * 4 * 7 + (double)h.n_polyak * 4 * 2;
-    grl_ctx* self = &h;
-    op.run = [self](hipStream_t s) {
-      const AdamArgs aa = self->adam_args(self->grad_scale, true);
-      const int blocks = (int)std::min<int64_t>(2048, (self->n_train + 255) / 256);
-      hipLaunchKernelGGL(adam_polyak_kernel, dim3(blocks), dim3(256), 0, s, aa);
-    };
     h.ops_apply.push_back(op);
   }
 

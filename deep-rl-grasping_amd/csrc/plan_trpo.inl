@@ -4,6 +4,7 @@
 // backward-data and weight gradients are dense_fwd / dense_bwd / dense_wgrad, the slab reduction reduce_slabs_kernel, the value
 // fit's Adam adam_polyak_kernel over the whole bucket (the policy entries of the gradient bucket are never written: moments that
 // stay zero give a step of exactly zero).  One lane, no forks: the lists run through run_seq / run_repeated.
+// Shared: every forward, every backward (BWD_T, BWD_F, BWD_vf) and the value fit's gather are PpoPlanner's, called with a tower mask.
 //
 // Vectors of the policy step (g, r, p, x, z, fullstep, theta_old) are laid out like the gradient bucket, the entries of the value
 // variables held at zero: dot products over the whole bucket are dot products over the policy variables, and a tangent weight
@@ -75,53 +76,6 @@ struct TrpoPlanner {
     vpart = wk.f32((int64_t)nvb * 2); vpart2 = wk.f32(nvb);
   }
 
-  // ---------------- backward of tower tw over `rows` rows: data gradients level by level, weight gradients, slabs summed into dst
-  void backward(std::vector<Op>& ops, const std::string& tag, int tw, int rows, const float* xin, const PpoActs& act, const PpoActs& gr,
-                float* dst, const float* dls, int dls_blocks) {
-    const PpoTowerP& tt = pp.T[tw];
-    for (int s = 0; s < tt.L(); ++s) {
-      const int l = tt.L() - 1 - s;
-      const grl_ctx::BwdPart above = s == 0 ? grl_ctx::BwdPart{gr.out[tw], gr.ld_out[tw], tt.out, P + tt.w[l + 1]}
-                                            : grl_ctx::BwdPart{gr.z[tw][l + 1], tt.width[l + 1], tt.width[l + 1], P + tt.w[l + 1]};
-      h.add_launch(ops, tag + "_bwd", 1, {h.dense_bwd({above}, rows, 0, tt.width[l], gr.z[tw][l], tt.width[l], nullptr)});
-      TanhDesc d;
-      memset(&d, 0, sizeof(d));
-      d.z = act.z[tw][l]; d.dz = gr.z[tw][l]; d.H = tt.width[l];
-      pp.add_tanh(ops, "ppo_tanh_bwd", true, {d}, rows);
-    }
-    std::vector<IgemmProb> wg;
-    h.reduces.clear();      // (every backward of this plan has a reduction launch of its own)
-    auto wgrad = [&](const float* xi, int ldx, int kin, const float* gg, int ldg, int N, int64_t woff, int64_t boff) {
-      IgemmProb q = h.dense_wgrad(xi, ldx, kin, true, gg, ldg, N, rows, nullptr, 1, ldx >= (int)rup(kin, 4) ? (int)rup(kin, 4) : kin);
-      q.c = h.wk.f32(q.slab_stride * q.split);
-      h.add_wgrad(wg, q, woff, 0, kin, boff, dst);
-    };
-    const float* xi = xin; int ldx = ldo, k = od;
-    for (int l = 0; l < tt.L(); ++l) {
-      wgrad(xi, ldx, k, gr.z[tw][l], tt.width[l], tt.width[l], tt.w[l], tt.b[l]);
-      xi = act.z[tw][l]; ldx = k = tt.width[l];
-    }
-    wgrad(xi, ldx, k, gr.out[tw], gr.ld_out[tw], tt.out, tt.w[tt.L()], tt.b[tt.L()]);
-    h.add_launch(ops, tag + "_wgrad", 2, wg);
-    if (dls) {
-      ReduceDesc rd;
-      memset(&rd, 0, sizeof(rd));
-      rd.src = dls; rd.splits = dls_blocks; rd.slab_stride = A; rd.dst = dst + pp.logstd_off; rd.n = A;
-      h.reduces.push_back(rd);
-    }
-    std::vector<int2> rt = h.reduce_tiles();
-    const ReduceDesc* dr = h.upload_vec(h.wk, h.reduces);
-    const int2* d_rt = h.upload_vec(h.wk, rt);
-    const int ntiles = (int)rt.size();
-    LossArgs none;
-    memset(&none, 0, sizeof(none));
-    Op op; op.tag = "reduce_slabs";
-    op.run = [dr, d_rt, ntiles, none](hipStream_t s) {
-      hipLaunchKernelGGL(reduce_slabs_kernel, dim3(ntiles), dim3(256), 0, s, dr, d_rt, ntiles, none, 0, AdamArgs{}, 0);
-    };
-    ops.push_back(op);
-  }
-
   TrpoVecArgs vec() const {
     TrpoVecArgs a;
     memset(&a, 0, sizeof(a));
@@ -177,7 +131,7 @@ struct TrpoPlanner {
       op.run = [a](hipStream_t s) { launch_trpo_tan(a, s); };
       fvp.push_back(op);
     }
-    backward(fvp, "trpo_fvp", 0, NF, xf, act_F, g_F, z, nullptr, 0);
+    pp.backward(fvp, "trpo_fvp", 1, NF, xf, act_F, g_F, z, nullptr, 0);
     add_vec(fvp, "trpo_fvp_fin", TRPO_V_FVP_FIN, vec());
   }
 
@@ -206,7 +160,7 @@ struct TrpoPlanner {
     ops.insert(ops.end(), fwd_T.begin(), fwd_T.end());
     add_loss(ops, 0);
     add_scal(ops, TRPO_SC_BEFORE, 0, lpart, nblk_T);
-    backward(ops, "trpo_g", 0, T, h.pr_obs, act_T, g_T, g, dls_T, nblk_T);
+    pp.backward(ops, "trpo_g", 1, T, h.pr_obs, act_T, g_T, g, dls_T, nblk_T);
     gather_fisher(ops);
     add_vec(ops, "trpo_cg_init", TRPO_V_CG_INIT, vec());
     add_scal(ops, TRPO_SC_CG, 0, vpart, nvb);
@@ -247,17 +201,7 @@ struct TrpoPlanner {
 
   void value_fit() {
     std::vector<Op>& ops = h.ops_trpo_vf;
-    {
-      PpoGatherArgs ga;
-      memset(&ga, 0, sizeof(ga));
-      ga.perm = h.ppo_perm; ga.dev = h.ppo_dev; ga.sc = h.sc;
-      ga.r_obs = h.pr_obs; ga.ldo = ldo; ga.r_act = h.pr_act; ga.r_oldv = h.pr_val; ga.r_oldnlp = h.pr_nlp; ga.r_adv = h.pr_adv; ga.r_ret = h.pr_ret;
-      ga.x = pp.mb_x; ga.act = pp.mb_act; ga.oldv = pp.mb_oldv; ga.oldnlp = pp.mb_oldnlp; ga.adv = pp.mb_adv; ga.ret = pp.mb_ret;
-      ga.mb = B; ga.A = A;
-      Op op; op.tag = "ppo_gather";
-      op.run = [ga](hipStream_t s) { launch_ppo_gather(ga, s); };
-      ops.push_back(op);
-    }
+    pp.add_gather(ops);
     pp.forward(ops, pp.mb_x, B, pp.act_mb, "trpo_vf_fwd", 2);
     {
       const float* v = pp.act_mb.out[1]; const float* ret = pp.mb_ret; float* dv = pp.g_mb.out[1];
@@ -266,16 +210,8 @@ struct TrpoPlanner {
       op.run = [v, ldv, ret, dv, lddv, mb, dev](hipStream_t s) { launch_trpo_vf_loss(v, ldv, ret, dv, lddv, mb, dev, s); };
       ops.push_back(op);
     }
-    backward(ops, "trpo_vf", 1, B, pp.mb_x, pp.act_mb, pp.g_mb, h.grads, nullptr, 0);
-    grl_ctx* self = &h;
-    const float eps = tc.adam_eps;
-    Op op; op.tag = "adam";
-    op.run = [self, eps](hipStream_t s) {
-      const AdamArgs aa = self->adam_args(1.f, false, eps);
-      const int blocks = (int)std::min<int64_t>(2048, (self->n_train + 255) / 256);
-      hipLaunchKernelGGL(adam_polyak_kernel, dim3(blocks), dim3(256), 0, s, aa);
-    };
-    ops.push_back(op);
+    pp.backward(ops, "trpo_vf", 2, B, pp.mb_x, pp.act_mb, pp.g_mb, h.grads, nullptr, 0);
+    ops.push_back(h.adam_op("adam", tc.adam_eps, false, false));
   }
 
   void debug_views() {

@@ -15,47 +15,32 @@
 // or TRPO's scratch between the launches of one update (theta_old, the CG vectors, the line-search words): an update is never
 // interrupted.
 
+// Shared (checkpoint.inl): state_write_head / state_read_head for the header and the grl_config, CfgBlock for the second block.
+
 #define GRL_PCFG_FIELD(f) {#f, offsetof(grl_ppo_config, f), sizeof(((grl_ppo_config*)nullptr)->f)}
-static const struct { const char* name; size_t off, size; } k_pcfg_fields[] = {
+static const CfgField k_pcfg_fields[] = {
   GRL_PCFG_FIELD(n_envs), GRL_PCFG_FIELD(n_steps), GRL_PCFG_FIELD(n_vf_layers), GRL_PCFG_FIELD(vf_layers), GRL_PCFG_FIELD(lam),
   GRL_PCFG_FIELD(clip_range), GRL_PCFG_FIELD(clip_range_vf), GRL_PCFG_FIELD(ent_coef), GRL_PCFG_FIELD(vf_coef),
   GRL_PCFG_FIELD(max_grad_norm), GRL_PCFG_FIELD(adam_eps), GRL_PCFG_FIELD(norm_eps64),
 };
 #undef GRL_PCFG_FIELD
 #define GRL_TCFG_FIELD(f) {#f, offsetof(grl_trpo_config, f), sizeof(((grl_trpo_config*)nullptr)->f)}
-static const struct { const char* name; size_t off, size; } k_tcfg_fields[] = {
+static const CfgField k_tcfg_fields[] = {
   GRL_TCFG_FIELD(n_steps), GRL_TCFG_FIELD(n_vf_layers), GRL_TCFG_FIELD(vf_layers), GRL_TCFG_FIELD(cg_iters), GRL_TCFG_FIELD(ls_steps),
   GRL_TCFG_FIELD(fvp_stride), GRL_TCFG_FIELD(vf_batch), GRL_TCFG_FIELD(lam), GRL_TCFG_FIELD(max_kl), GRL_TCFG_FIELD(cg_damping),
   GRL_TCFG_FIELD(ent_coef), GRL_TCFG_FIELD(adam_eps), GRL_TCFG_FIELD(norm_eps64),
 };
 #undef GRL_TCFG_FIELD
 
-// the second configuration block of the handle: its bytes, size and field table
-struct PpoCfg2 {
-  const char* type; const char* base; size_t bytes;
-  const char* fname[16]; size_t off[16], size[16]; int n;
-};
-static PpoCfg2 ppo_cfg2(const grl_ctx* h) {
-  PpoCfg2 q;
-  memset(&q, 0, sizeof(q));
-  if (h->cfg.algo == GRL_ALGO_TRPO) {
-    q.type = "grl_trpo_config"; q.base = (const char*)&h->tcfg; q.bytes = sizeof(grl_trpo_config);
-    for (const auto& f : k_tcfg_fields) { q.fname[q.n] = f.name; q.off[q.n] = f.off; q.size[q.n] = f.size; ++q.n; }
-  } else {
-    q.type = "grl_ppo_config"; q.base = (const char*)&h->pcfg; q.bytes = sizeof(grl_ppo_config);
-    for (const auto& f : k_pcfg_fields) { q.fname[q.n] = f.name; q.off[q.n] = f.off; q.size[q.n] = f.size; ++q.n; }
-  }
-  return q;
+// the second configuration block of the handle
+static CfgBlock ppo_cfg2(const grl_ctx* h) {
+  if (h->cfg.algo == GRL_ALGO_TRPO)
+    return {k_tcfg_fields, (int)(sizeof(k_tcfg_fields) / sizeof(CfgField)), (const char*)&h->tcfg, sizeof(grl_trpo_config), "grl_trpo_config"};
+  return {k_pcfg_fields, (int)(sizeof(k_pcfg_fields) / sizeof(CfgField)), (const char*)&h->pcfg, sizeof(grl_ppo_config), "grl_ppo_config"};
 }
 
 // cfg_hash of the grl_config, continued over the fields of the second block in field order
-static uint64_t ppo_cfg_hash(const grl_ctx* h) {
-  uint64_t hsh = cfg_hash(h->cfg);
-  const PpoCfg2 q = ppo_cfg2(h);
-  for (int f = 0; f < q.n; ++f)
-    for (size_t k = 0; k < q.size[f]; ++k) hsh = (hsh ^ (uint8_t)q.base[q.off[f] + k]) * 0x100000001b3ull;
-  return hsh;
-}
+static uint64_t ppo_cfg_hash(const grl_ctx* h) { return ppo_cfg2(h).hash(cfg_hash(h->cfg)); }
 
 struct PpoStateHost {      // follows the header and the two configuration blocks in the blob
   int32_t written, closed, finished;      // ppo_stepped, ppo_closed, ppo_finished
@@ -82,21 +67,8 @@ int64_t grl_ppo_state_export(grl_handle h, void* host_buf, size_t cap) {
   const size_t total = ppo_state_bytes_now(h);
   if (cap < total) return fail(GRL_ERR_INVALID, "state buffer too small: " + std::to_string(total) + " bytes needed");
   HIPCHK(hipStreamSynchronize(h->stream));
-  char* p = (char*)host_buf;
-  grl_state_header hd;
-  memset(&hd, 0, sizeof(hd));
-  hd.magic = GRL_STATE_MAGIC; hd.version = grl_version(); hd.layout = GRL_STATE_LAYOUT;
-  hd.config_bytes = (int32_t)sizeof(grl_config); hd.config_hash = ppo_cfg_hash(h);
-  hd.total_bytes = total;      // (replay_pos / replay_size stay 0: a rollout has a cursor of its own, below)
-  memcpy(p, &hd, sizeof(hd)); p += sizeof(hd);
-  grl_config c;                      // field by field into zeroed storage: the blob holds no padding bytes of the caller's structs
-  memset(&c, 0, sizeof(c));
-  for (const auto& f : k_cfg_fields) memcpy((char*)&c + f.off, (const char*)&h->cfg + f.off, f.size);
-  memcpy(p, &c, sizeof(c)); p += sizeof(c);
-  const PpoCfg2 q = ppo_cfg2(h);
-  memset(p, 0, q.bytes);
-  for (int f = 0; f < q.n; ++f) memcpy(p + q.off[f], q.base + q.off[f], q.size[f]);
-  p += q.bytes;
+  // (replay_pos / replay_size stay 0: a rollout has a cursor of its own, below)
+  char* p = ppo_cfg2(h).write(state_write_head(h, (char*)host_buf, ppo_cfg_hash(h), 0, 0, total));
   PpoStateHost sh;
   memset(&sh, 0, sizeof(sh));
   sh.written = h->ppo_stepped; sh.closed = h->ppo_closed; sh.finished = h->ppo_finished ? 1 : 0;
@@ -112,30 +84,17 @@ int grl_ppo_state_import(grl_handle h, const void* host_buf, size_t n) {
   if (!host_buf) return fail(GRL_ERR_INVALID, "null argument");
   const char* p = (const char*)host_buf;
   grl_state_header hd;
-  if (n < sizeof(hd)) return fail(GRL_ERR_INVALID, "state blob is truncated (no header)");
-  memcpy(&hd, p, sizeof(hd)); p += sizeof(hd);
-  if (hd.magic != GRL_STATE_MAGIC) return fail(GRL_ERR_INVALID, "not a grl state blob (wrong magic)");
-  if (hd.version != grl_version())
-    return fail(GRL_ERR_INVALID, "state blob written by library version " + std::to_string(hd.version) + ", this is " + std::to_string(grl_version()));
-  if (hd.layout != GRL_STATE_LAYOUT) return fail(GRL_ERR_INVALID, "state blob has layout version " + std::to_string(hd.layout) + ", expected " + std::to_string(GRL_STATE_LAYOUT));
-  if ((size_t)hd.config_bytes != sizeof(grl_config)) return fail(GRL_ERR_INVALID, "state blob holds a grl_config of another size");
-  if (n < sizeof(hd) + sizeof(grl_config) || hd.total_bytes != n)
-    return fail(GRL_ERR_INVALID, "state blob is truncated (" + std::to_string(n) + " of " + std::to_string(hd.total_bytes) + " bytes)");
   grl_config c;
-  memcpy(&c, p, sizeof(c)); p += sizeof(c);
+  if (int e = state_read_head(&p, n, false, 0, hd, c)) return e;
   // the kind of handle first: the second configuration block of the other kind has another shape
   auto kind = [](int algo) { return algo == GRL_ALGO_PPO ? "a PPO handle" : algo == GRL_ALGO_TRPO ? "a TRPO handle" : "a handle that keeps no rollout (grl_state_export)"; };
   if (c.algo != h->cfg.algo)
     return fail(GRL_ERR_INVALID, std::string("state blob was written by ") + kind(c.algo) + ", this is " + kind(h->cfg.algo));
-  const PpoCfg2 q = ppo_cfg2(h);
+  const CfgBlock q = ppo_cfg2(h);
   const size_t fixed = sizeof(hd) + sizeof(grl_config) + q.bytes + sizeof(PpoStateHost);
   if (n < fixed) return fail(GRL_ERR_INVALID, "state blob is truncated (" + std::to_string(n) + " bytes, " + std::to_string(fixed) + " before the observed rows)");
-  for (const auto& f : k_cfg_fields)
-    if (memcmp((const char*)&c + f.off, (const char*)&h->cfg + f.off, f.size) != 0)
-      return fail(GRL_ERR_INVALID, std::string("state blob was written for another configuration: grl_config.") + f.name + " differs");
-  for (int f = 0; f < q.n; ++f)
-    if (memcmp(p + q.off[f], q.base + q.off[f], q.size[f]) != 0)
-      return fail(GRL_ERR_INVALID, std::string("state blob was written for another configuration: ") + q.type + "." + q.fname[f] + " differs");
+  if (int e = cfg_block(h).differs((const char*)&c)) return e;
+  if (int e = q.differs(p)) return e;
   p += q.bytes;
   if (hd.config_hash != ppo_cfg_hash(h)) return fail(GRL_ERR_INVALID, "state blob is damaged (configuration hash)");
   PpoStateHost sh;
