@@ -958,6 +958,7 @@ int grl_ppo_step(grl_handle h, const float* obs, const float* done, const float*
   if (int e = ppo_receive(h, h->NA, out_act, out_val, out_nlp)) return e;
   h->ppo_stepped += 1;
   h->ppo_finished = false;
+  h->ppo_held = h->gail_rewritten = false;      // (a GAIL session: the last full rollout is being overwritten)
   return GRL_OK;
 }
 
@@ -983,7 +984,7 @@ int grl_ppo_finish(grl_handle h, const float* last_obs, const float* last_done) 
   // (the staging buffer of ppo_send is reused by the next call: wait for its copy, as every per-step call does)
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
-  h->ppo_finished = true;
+  h->ppo_finished = h->ppo_held = true;
   return GRL_OK;
 }
 
@@ -1580,6 +1581,7 @@ int64_t grl_debug_store(grl_handle h, const char* name, const float* in, int64_t
     if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(GRL_ERR_HIP, "sync failed");
     if (hipMemcpy(&h->ppo_dev->slot, &cl, 4, hipMemcpyHostToDevice) != hipSuccess) return fail(GRL_ERR_HIP, "copy failed");
     h->ppo_stepped = st; h->ppo_closed = cl; h->ppo_finished = in[2] != 0.f && cl == h->pcfg.n_steps;
+    h->ppo_held = h->ppo_finished; h->gail_rewritten = false;
     return n;
   }
   auto it = h->dbg.find(name);
@@ -1743,6 +1745,197 @@ int grl_bc_end(grl_handle h) {
   if (!h->bc) return fail(GRL_ERR_STATE, "grl_bc_end needs an open session (grl_bc_begin)");
   HIPCHK(hipStreamSynchronize(h->stream));
   h->bc_drop();
+  return GRL_OK;
+}
+
+// ---- GAIL (plan_gail.inl): a session on a TRPO handle, in a buffer of the caller's
+#define GAIL_SESSION(h, what)                                                                                     \
+  do {                                                                                                            \
+    TRPO_ONLY(h, what);                                                                                           \
+    if (!(h)->gail) return fail(GRL_ERR_STATE, what " needs an open session (grl_gail_begin)");                   \
+  } while (0)
+
+static int check_gail(grl_handle h, const grl_gail_config* c) {
+  if (!c || !c->act_low || !c->act_high) return fail(GRL_ERR_INVALID, "null GAIL config or action bounds");
+  if (c->hidden < 1 || c->hidden > 1024) return fail(GRL_ERR_INVALID, "gail: hidden must be 1..1024 (" + std::to_string(c->hidden) + ")");
+  if (c->batch < 1 || c->batch > h->tcfg.n_steps)
+    return fail(GRL_ERR_INVALID, "gail: batch " + std::to_string(c->batch) + " is outside 1.." + std::to_string(h->tcfg.n_steps) + " (the handle's n_steps)");
+  if (!(c->lr > 0.f) || !(c->adam_eps > 0.f) || !std::isfinite(c->entcoeff)) return fail(GRL_ERR_INVALID, "gail: lr and adam_eps must be > 0, entcoeff finite");
+  for (int j = 0; j < h->cfg.act_dim; ++j)
+    if (!(c->act_high[j] > c->act_low[j]) || !std::isfinite(c->act_high[j]) || !std::isfinite(c->act_low[j]))
+      return fail(GRL_ERR_INVALID, "gail: the action bounds must be finite with high > low (dimension " + std::to_string(j) + ")");
+  return GRL_OK;
+}
+
+static void gail_fill(grl_handle h, const grl_gail_config* c, GailPlan& p) {
+  p.cfg = *c;
+  p.low.assign(c->act_low, c->act_low + h->cfg.act_dim);
+  p.high.assign(c->act_high, c->act_high + h->cfg.act_dim);
+  p.cfg.act_low = p.cfg.act_high = nullptr;
+}
+
+int grl_gail_query_sizes(grl_handle h, const grl_gail_config* c, size_t* bytes) {
+  TRPO_ONLY(h, "grl_gail_query_sizes");
+  if (!bytes) return fail(GRL_ERR_INVALID, "null out");
+  if (int e = check_gail(h, c)) return e;
+  std::unique_ptr<GailPlan> p(new GailPlan());
+  gail_fill(h, c, *p);
+  if (int e = h->plan_gail(*p)) return e;
+  for (auto* l : p->launches) delete l;
+  *bytes = p->a.off + 256;
+  return GRL_OK;
+}
+
+static int gail_store_stats(grl_handle h, const double* sum, const double* sumsq, double count) {
+  GailPlan& p = *h->gail;
+  const std::vector<double> cnt((size_t)p.od, count);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpy(p.sum, sum, (size_t)p.od * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(p.sumsq, sumsq, (size_t)p.od * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(p.count, cnt.data(), (size_t)p.od * 8, hipMemcpyHostToDevice));
+  // the float32 mean / std the reward pass reads: the device's own arithmetic (gail_mean_sd), run here on the host
+  std::vector<float> mean((size_t)p.od), sd((size_t)p.od);
+  for (int c = 0; c < p.od; ++c) gail_mean_sd(sum[c], sumsq[c], count, mean[(size_t)c], sd[(size_t)c]);
+  HIPCHK(hipMemcpy(p.mean, mean.data(), (size_t)p.od * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(p.sd, sd.data(), (size_t)p.od * 4, hipMemcpyHostToDevice));
+  return GRL_OK;
+}
+
+int grl_gail_begin(grl_handle h, const grl_gail_config* c, void* buf) {
+  TRPO_ONLY(h, "grl_gail_begin");
+  if (!buf) return fail(GRL_ERR_INVALID, "null buffer");
+  if (h->gail) return fail(GRL_ERR_STATE, "a GAIL session is open on this handle (grl_gail_end)");
+  if (int e = check_gail(h, c)) return e;
+  GailPlan* p = new GailPlan();
+  gail_fill(h, c, *p);
+  p->a.base = (char*)buf;
+  h->gail = p;
+  if (int e = h->plan_gail(*p)) { h->uploads.clear(); h->gail_drop(); return e; }
+  // the whole buffer zero (parameters, moments, row padding), then the tables, the optimiser's words and the statistics' start
+  hipError_t e = hipMemsetAsync(buf, 0, p->a.off, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  for (auto& u : h->uploads)
+    if (e == hipSuccess) e = hipMemcpy(u.dst, u.bytes.data(), u.bytes.size(), hipMemcpyHostToDevice);
+  h->uploads.clear();
+  DevScalars s0;
+  memset(&s0, 0, sizeof(s0));
+  s0.beta1_power = 0.9f; s0.beta2_power = 0.999f; s0.lr = c->lr;
+  if (e == hipSuccess) e = hipMemcpy(p->sc, &s0, sizeof(s0), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { h->gail_drop(); return fail(GRL_ERR_HIP, std::string("gail begin: ") + hipGetErrorString(e)); }
+  const std::vector<double> sum0((size_t)p->od, 0.0), sumsq0((size_t)p->od, 1e-2);
+  if (int e2 = gail_store_stats(h, sum0.data(), sumsq0.data(), 1e-2)) { h->gail_drop(); return e2; }
+  h->gail_rewritten = false;
+  return GRL_OK;
+}
+
+int grl_gail_param_info(grl_handle h, int i, char* name, int cap, int64_t* off, int64_t* numel, int32_t* rows, int32_t* cols) {
+  GAIL_SESSION(h, "grl_gail_param_info");
+  if (i < 0 || i >= 6) return fail(GRL_ERR_INVALID, "gail: parameter index must be 0..5");
+  const GailPlan::Tensor& t = h->gail->tensors[i];
+  if (name && cap > 0) { strncpy(name, t.name, cap - 1); name[cap - 1] = 0; }
+  if (off) *off = t.off;
+  if (numel) *numel = t.numel;
+  if (rows) *rows = t.rows;
+  if (cols) *cols = t.cols;
+  return 6;
+}
+
+int grl_gail_rewards(grl_handle h) {
+  GAIL_SESSION(h, "grl_gail_rewards");
+  if (h->ppo_closed != h->pcfg.n_steps || h->ppo_finished)
+    return fail(GRL_ERR_STATE, "grl_gail_rewards rewrites the rewards of a full rollout that grl_ppo_finish has not closed yet: n_steps slots must be closed");
+  if (h->gail_rewritten) return fail(GRL_ERR_STATE, "grl_gail_rewards: the rewards of this rollout are the discriminator's already");
+  if (int e = h->run_seq("gail_rewards", {&h->gail->ops_rewards})) return e;
+  HIPCHK(hipGetLastError());
+  h->gail_rewritten = true;
+  return GRL_OK;
+}
+
+// a call's index rows on the host: generator rows all present and inside the rollout; expert rows inside the table, -1 only as
+// a tail, at least one row present (bc_check_idx)
+static int gail_check_idx(grl_handle h, const int32_t* gen_idx, const int32_t* exp_idx, int64_t n_rows, int n, std::vector<int>& ne) {
+  GailPlan& p = *h->gail;
+  const int batch = p.cfg.batch, T = h->tcfg.n_steps;
+  const size_t cnt = (size_t)n * batch;
+  p.idx_host.resize(2 * cnt);
+  HIPCHK(hipMemcpyAsync(p.idx_host.data(), gen_idx, cnt * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(p.idx_host.data() + cnt, exp_idx, cnt * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int u = 0; u < n; ++u) {
+    const int32_t* g = p.idx_host.data() + (size_t)u * batch;
+    const int32_t* row = g + cnt;
+    bool tail = false;
+    int n_e = 0;
+    for (int b = 0; b < batch; ++b) {
+      const std::string at = "update " + std::to_string(u) + ", entry " + std::to_string(b);
+      if (g[b] < 0 || g[b] >= T) return fail(GRL_ERR_INVALID, "gail: generator index of " + at + " is outside the rollout (" + std::to_string(g[b]) + ")");
+      if (row[b] < -1 || row[b] >= n_rows) return fail(GRL_ERR_INVALID, "gail: expert index of " + at + " is outside the table (" + std::to_string(row[b]) + ")");
+      if (row[b] == -1) { if (b == 0) return fail(GRL_ERR_INVALID, "gail: expert index of " + at + ": a minibatch needs at least one row"); tail = true; }
+      else if (tail) return fail(GRL_ERR_INVALID, "gail: expert index of " + at + " follows a -1: absent rows must be trailing");
+      else n_e += 1;
+    }
+    ne.push_back(n_e);
+  }
+  return GRL_OK;
+}
+
+int grl_gail_update(grl_handle h, const float* exp_obs, const float* exp_act, int64_t n_rows, const int32_t* gen_idx,
+                    const int32_t* exp_idx, int n_updates) {
+  GAIL_SESSION(h, "grl_gail_update");
+  if (n_updates < 1 || n_updates > GRL_GAIL_MAX_UPDATES) return fail(GRL_ERR_INVALID, "gail: the count of a call must be 1..4096");
+  if (!exp_obs || !exp_act || !gen_idx || !exp_idx || n_rows < 1) return fail(GRL_ERR_INVALID, "gail: null table or indices");
+  if (!h->ppo_held) return fail(GRL_ERR_STATE, "grl_gail_update reads the last finished rollout: none is held (grl_ppo_finish .. the next grl_ppo_step)");
+  GailPlan& p = *h->gail;
+  std::vector<int> ne;
+  if (int e = gail_check_idx(h, gen_idx, exp_idx, n_rows, n_updates, ne)) return e;
+  launch_gail_open(p.dev, exp_obs, exp_act, gen_idx, exp_idx, h->stream);
+  if (int e = h->run_repeated("gail_update", {&p.ops_update}, n_updates)) return e;
+  HIPCHK(hipGetLastError());
+  p.last_n = n_updates;
+  p.last_ne = ne;
+  return GRL_OK;
+}
+
+int grl_gail_get_losses(grl_handle h, float* out, int cap) {
+  GAIL_SESSION(h, "grl_gail_get_losses");
+  GailPlan& p = *h->gail;
+  const int nu = p.last_n, nb = p.nblk;
+  if (!out || cap < nu * GAIL_DIAG) return fail(GRL_ERR_INVALID, "gail: loss buffer too small");
+  std::vector<float> part((size_t)std::max(1, nu * nb * GAIL_DIAG));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (nu) HIPCHK(hipMemcpy(part.data(), p.diag, (size_t)nu * nb * GAIL_DIAG * 4, hipMemcpyDeviceToHost));
+  for (int u = 0; u < nu; ++u) {
+    float s[GAIL_DIAG] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < nb; ++b)      // the per-block sums of the loss launch, in index order
+      for (int k = 0; k < GAIL_DIAG; ++k) s[k] += part[((size_t)u * nb + b) * GAIL_DIAG + k];
+    const float n_g = (float)p.cfg.batch, n_e = (float)p.last_ne[(size_t)u];
+    float* o = out + (size_t)u * GAIL_DIAG;
+    o[0] = s[0] / n_g; o[1] = s[1] / n_e; o[2] = s[2] / (n_g + n_e); o[3] = -p.cfg.entcoeff * o[2]; o[4] = s[4] / n_g; o[5] = s[5] / n_e;
+  }
+  return nu;
+}
+
+int grl_gail_get_stats(grl_handle h, double* sum, double* sumsq, double* count) {
+  GAIL_SESSION(h, "grl_gail_get_stats");
+  if (!sum || !sumsq || !count) return fail(GRL_ERR_INVALID, "null argument");
+  GailPlan& p = *h->gail;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpy(sum, p.sum, (size_t)p.od * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(sumsq, p.sumsq, (size_t)p.od * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(count, p.count, 8, hipMemcpyDeviceToHost));
+  return GRL_OK;
+}
+
+int grl_gail_set_stats(grl_handle h, const double* sum, const double* sumsq, double count) {
+  GAIL_SESSION(h, "grl_gail_set_stats");
+  if (!sum || !sumsq || !(count > 0.0)) return fail(GRL_ERR_INVALID, "gail: null statistics or a count that is not positive");
+  return gail_store_stats(h, sum, sumsq, count);
+}
+
+int grl_gail_end(grl_handle h) {
+  GAIL_SESSION(h, "grl_gail_end");
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->gail_drop();
   return GRL_OK;
 }
 

@@ -4,6 +4,7 @@
 //   plan_ae.inl  (auto-encoder training)              plan_ppo.inl (PPO2: rollout, GAE, clipped update)
 //   plan_trpo.inl (TRPO: CG natural-gradient step, line search, value fit -- over plan_ppo.inl's policy and rollout)
 //   plan_bc.inl  (behaviour-cloning pretraining of a SAC handle's policy, built at grl_bc_begin)
+//   plan_gail.inl (GAIL session of a TRPO handle: discriminator update and its rewards, built at grl_gail_begin)
 //   capi.inl     (extern "C" entry points)
 // The element-wise, replay, prioritised-sampling and exchange kernels are compiled here; the GEMM and head kernels in
 // gemm_fwd.hip / gemm_bwd.hip / gemm_wgrad.hip / heads.hip behind the launchers of launch.h.
@@ -52,6 +53,8 @@
 #define GRL_TRPO_TYPES_ONLY         // (the TRPO kernels in trpo.hip)
 #include "trpo_kernels.h"
 #include "bc_kernels.h"
+#define GRL_GAIL_TYPES_ONLY         // (the GAIL kernels in gail.hip)
+#include "gail_kernels.h"
 
 namespace grl {
 
@@ -353,6 +356,7 @@ struct HeadGrad {
   int ld0 = 0;   // row stride of g[0] (fused heads: the critics' g[0] are column blocks of one buffer)
 };
 struct BcPlan;   // an open behaviour-cloning session (plan_bc.inl)
+struct GailPlan; // an open GAIL session (plan_gail.inl)
 
 }  // namespace grl
 
@@ -506,6 +510,7 @@ struct grl_ctx {
 
   ~grl_ctx() {
     bc_drop();
+    gail_drop();
     if (pin_in) hipHostFree(pin_in);
     if (pin_out) hipHostFree(pin_out);
     if (act_io_host) hipHostFree(act_io_host);
@@ -1540,6 +1545,15 @@ struct grl_ctx {
     };
     return op;
   }
+  // ... over a range, moments and optimiser words of its own (a session's: plan_gail.inl), fixed when the plan is built
+  static Op adam_op(const char* tag, const AdamArgs& aa) {
+    Op op; op.tag = tag;
+    op.run = [aa](hipStream_t s) {
+      const int blocks = (int)std::min<int64_t>(2048, (aa.n_train + 255) / 256);
+      hipLaunchKernelGGL(adam_polyak_kernel, dim3(blocks), dim3(256), 0, s, aa);
+    };
+    return op;
+  }
   // Weight + bias gradients of one stack of dense layers over `rows` rows -- L hidden layers (activations z, gradients gz), then
   // its output layer where n_out > 0 -- as problems of one launch: the slabs from the work arena, their sums into `dst` (nullptr:
   // the gradient bucket).  An input whose rows are padded to a multiple of 4 floats carries the padding columns along: every
@@ -1643,6 +1657,13 @@ struct grl_ctx {
   BcPlan* bc = nullptr;
   int plan_bc(BcPlan& p);
   void bc_drop();
+  // GAIL on a TRPO handle (plan_gail.inl): the open session, built at grl_gail_begin into the caller's buffer.  Host words beside
+  // it, no part of any exported state: a finished full rollout is still in the replay arena (grl_ppo_finish .. the next
+  // grl_ppo_step); the rewards of the rollout being closed are already the discriminator's
+  GailPlan* gail = nullptr;
+  bool ppo_held = false, gail_rewritten = false;
+  int plan_gail(GailPlan& p);
+  void gail_drop();
   int plan_ae_general(const AeNet& net);   // ... of any supported network but the shipped one (GRL_TUNE ae_general=1: that one too)
   int enc_dim = 100;   // floats per image grl_encode returns (auto-encoder handles: their encoding_dim)
   float* ae_x = nullptr;            // [B, 4096] minibatch of depth images (staged per step)
@@ -1686,6 +1707,7 @@ int grl_ctx::plan() {
 #include "plan_ppo.inl"
 #include "plan_trpo.inl"
 #include "plan_bc.inl"
+#include "plan_gail.inl"
 
 int grl_ctx::run_ops(std::vector<Op>& ops) {
   if (!prof) {

@@ -28,6 +28,18 @@ struct PpoActs {        // activations (or their gradients) of both towers for o
   int ld_out[2];
 };
 
+// one tanh launch over the tensors of `descs` (the table goes up through the work arena); shared with plan_gail.inl
+static void add_tanh_op(grl_ctx& h, std::vector<Op>& ops, const char* tag, bool bwd, const std::vector<TanhDesc>& descs, int rows) {
+  if (descs.empty()) return;
+  const TanhDesc* dd = h.upload_vec(h.wk, descs);
+  const int n = (int)descs.size();
+  int max_h = 1;
+  for (auto& d : descs) max_h = std::max(max_h, (int)d.H);
+  Op op; op.tag = tag;
+  op.run = [dd, n, rows, max_h, bwd](hipStream_t s) { bwd ? launch_tanh_bwd(dd, n, rows, max_h, s) : launch_tanh_fwd(dd, n, rows, max_h, s); };
+  ops.push_back(op);
+}
+
 struct PpoPlanner {
   grl_ctx& h;
   const grl_config& c;
@@ -139,14 +151,7 @@ struct PpoPlanner {
 
   // ---------------- forward of both towers over `rows` rows of x: per level one dense launch + one tanh launch, then the outputs
   void add_tanh(std::vector<Op>& ops, const char* tag, bool bwd, const std::vector<TanhDesc>& descs, int rows) {
-    if (descs.empty()) return;
-    const TanhDesc* dd = h.upload_vec(h.wk, descs);
-    const int n = (int)descs.size();
-    int max_h = 1;
-    for (auto& d : descs) max_h = std::max(max_h, (int)d.H);
-    Op op; op.tag = tag;
-    op.run = [dd, n, rows, max_h, bwd](hipStream_t s) { bwd ? launch_tanh_bwd(dd, n, rows, max_h, s) : launch_tanh_fwd(dd, n, rows, max_h, s); };
-    ops.push_back(op);
+    add_tanh_op(h, ops, tag, bwd, descs, rows);
   }
   // (towers: bit 0 pi, bit 1 vf -- plan_trpo.inl runs them apart)
   void forward(std::vector<Op>& ops, const float* x, int rows, const PpoActs& a, const char* tag, int towers = 3) {

@@ -110,6 +110,7 @@ int grl_ppo_state_import(grl_handle h, const void* host_buf, size_t n) {
   // ---- nothing below fails on bad input
   if (nr) HIPCHK(hipMemcpy(h->ppo_obs_n, p, nr, hipMemcpyHostToDevice));
   h->ppo_stepped = sh.written; h->ppo_closed = sh.closed; h->ppo_finished = sh.finished != 0;
+  h->ppo_held = h->ppo_finished; h->gail_rewritten = false;
   h->n_parity = sh.n_parity; h->ppo_observed = sh.ob_n != 0;
   HIPCHK(hipMemcpy(&h->ppo_dev->slot, &sh.closed, 4, hipMemcpyHostToDevice));      // the device mirror follows the blob
   return GRL_OK;

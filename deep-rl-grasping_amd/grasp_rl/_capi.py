@@ -68,6 +68,15 @@ class GrlBcConfig(C.Structure):
 BC_MAX_UPDATES = 65536   # GRL_BC_MAX_UPDATES
 
 
+class GrlGailConfig(C.Structure):
+    """include/grl.h: grl_gail_config -- a GAIL session on a TRPO handle."""
+    _fields_ = [("hidden", C.c_int32), ("batch", C.c_int32), ("entcoeff", C.c_float), ("lr", C.c_float), ("adam_eps", C.c_float),
+                ("act_low", C.c_void_p), ("act_high", C.c_void_p)]
+
+
+GAIL_MAX_UPDATES = 4096  # GRL_GAIL_MAX_UPDATES
+
+
 class GrlSizes(C.Structure):
     _fields_ = [("state_bytes", C.c_size_t), ("grads_bytes", C.c_size_t), ("work_bytes", C.c_size_t),
                 ("replay_bytes", C.c_size_t), ("n_params", C.c_int64), ("n_trainable", C.c_int64)]
@@ -100,6 +109,8 @@ EXPORTS = [
     "grl_ppo_get_metrics",
     "grl_trpo_query_sizes", "grl_trpo_create", "grl_trpo_update", "grl_trpo_get_metrics", "grl_trpo_debug_fvp",
     "grl_bc_query_sizes", "grl_bc_begin", "grl_bc_train", "grl_bc_eval", "grl_bc_get_losses", "grl_bc_end",
+    "grl_gail_query_sizes", "grl_gail_begin", "grl_gail_param_info", "grl_gail_rewards", "grl_gail_update", "grl_gail_get_losses",
+    "grl_gail_get_stats", "grl_gail_set_stats", "grl_gail_end",
 ]
 
 
@@ -210,6 +221,16 @@ def load_library(path=None):
     lib.grl_bc_eval.argtypes = [vp, f32p, f32p, i64, vp, i32]
     lib.grl_bc_get_losses.argtypes = [vp, f32p, i32]
     lib.grl_bc_end.argtypes = [vp]
+    lib.grl_gail_query_sizes.argtypes = [vp, C.POINTER(GrlGailConfig), C.POINTER(C.c_size_t)]
+    lib.grl_gail_begin.argtypes = [vp, C.POINTER(GrlGailConfig), vp]
+    lib.grl_gail_param_info.argtypes = [vp, i32, C.c_char_p, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32)]
+    lib.grl_gail_rewards.argtypes = [vp]
+    lib.grl_gail_update.argtypes = [vp, f32p, f32p, i64, vp, vp, i32]
+    lib.grl_gail_get_losses.argtypes = [vp, f32p, i32]
+    lib.grl_gail_get_stats.argtypes = [vp, dp, dp, C.POINTER(C.c_double)]
+    lib.grl_gail_set_stats.argtypes = [vp, dp, dp, C.c_double]
+    lib.grl_gail_end.argtypes = [vp]
     return lib
 
 

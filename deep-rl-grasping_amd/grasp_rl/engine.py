@@ -998,3 +998,93 @@ class TrpoEngine(PpoEngine):
         self.store("trpo_fvp_in", vec)
         check(self.lib, self.lib.grl_trpo_debug_fvp(self.h))
         return self.fetch("trpo_fvp_out", (int(self.sizes.n_trainable),))
+
+    # ------------------------------------------------------------------ GAIL (grl_gail_*, csrc/plan_gail.inl)
+    LOSS_NAMES = ("generator_loss", "expert_loss", "entropy", "entropy_loss", "generator_acc", "expert_acc")
+
+    def gail_begin(self, hidden, batch, entcoeff, learning_rate, act_low, act_high, adam_epsilon=1e-8, params=None):
+        """Opens a GAIL session: a discriminator of two tanh layers of `hidden` units, `batch` generator rows per update, its own
+        Adam and running statistics, in a buffer of its own.  The parameters start at zero: hand them as `params` (name ->
+        array, the six ``adversary/...`` tensors) or store them with ``gail_set_parameters``."""
+        low = np.ascontiguousarray(act_low, dtype=np.float32).reshape(self.A)
+        high = np.ascontiguousarray(act_high, dtype=np.float32).reshape(self.A)
+        c = _capi.GrlGailConfig(int(hidden), int(batch), float(entcoeff), float(learning_rate), float(adam_epsilon), low.ctypes.data,
+                                high.ctypes.data)
+        nbytes = C.c_size_t()
+        check(self.lib, self.lib.grl_gail_query_sizes(self.h, C.byref(c), C.byref(nbytes)))
+        buf = self.be.alloc_f32(nbytes.value)
+        check(self.lib, self.lib.grl_gail_begin(self.h, C.byref(c), C.c_void_p(self.be.ptr(buf))))
+        table = []
+        for i in range(6):
+            name = C.create_string_buffer(128)
+            off, numel, rows, cols = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
+            check(self.lib, self.lib.grl_gail_param_info(self.h, i, name, 128, C.byref(off), C.byref(numel), C.byref(rows), C.byref(cols)))
+            shape = (rows.value, cols.value) if i % 2 == 0 else (rows.value,)
+            table.append((name.value.decode(), off.value, numel.value, shape))
+        self._gail = {"buf": buf, "batch": int(batch), "keep": None, "table": table}
+        if params is not None:
+            self.gail_set_parameters(params)
+
+    def gail_param_shapes(self):
+        return OrderedDict((name, shape) for name, _, _, shape in self._gail["table"])
+
+    def _gail_block(self, name):
+        n = max(off + numel for _, off, numel, _ in self._gail["table"])
+        return self.fetch(name, ((n + 3) // 4 * 4,))
+
+    def gail_get_parameters(self, block="gail_params"):
+        """name -> array of the six tensors (block: "gail_params", "gail_adam_m", "gail_adam_v" or "gail_grads")."""
+        flat = self._gail_block(block)
+        return OrderedDict((name, flat[off:off + numel].reshape(shape).copy()) for name, off, numel, shape in self._gail["table"])
+
+    def gail_set_parameters(self, params):
+        flat = self._gail_block("gail_params")
+        for name, off, numel, shape in self._gail["table"]:
+            flat[off:off + numel] = np.asarray(params[name], np.float32).reshape(-1)
+        self.store("gail_params", flat)
+
+    def gail_upload(self, obs, act):
+        """(observations, actions) of an expert dataset as float32 device arrays for gail_update: [n, obs_dim], [n, A]."""
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        n = obs.shape[0]
+        act = np.ascontiguousarray(act, dtype=np.float32).reshape(n, self.A)
+        return self.be.to_device(obs.reshape(n, self.obs_dim)), self.be.to_device(act), n
+
+    def gail_rewards(self):
+        """Rewrites the rewards of the full, not yet finished rollout with the discriminator's (one batched pass)."""
+        check(self.lib, self.lib.grl_gail_rewards(self.h))
+
+    def gail_update(self, table, gen_idx, exp_idx):
+        """One discriminator update per row of gen_idx / exp_idx [n_updates, batch] (int32: rows of the last finished rollout;
+        rows of the table, a shorter expert batch ending in -1 entries).  table: what gail_upload returned."""
+        obs, act, n = table
+        b = self._gail["batch"]
+        gi = np.ascontiguousarray(gen_idx, dtype=np.int32).reshape(-1, b)
+        ei = np.ascontiguousarray(exp_idx, dtype=np.int32).reshape(-1, b)
+        if gi.shape != ei.shape:
+            raise GrlError("gail_update: gen_idx and exp_idx must name the same number of updates")
+        dg, de = self.be.to_device(gi), self.be.to_device(ei)
+        p = self.be.ptr
+        self._gail["keep"] = (table, dg, de)      # alive until the stream has consumed them
+        check(self.lib, self.lib.grl_gail_update(self.h, p(obs), p(act), n, C.c_void_p(p(dg)), C.c_void_p(p(de)), gi.shape[0]))
+
+    def gail_losses(self):
+        """[n_updates, 6] of the last gail_update, columns LOSS_NAMES (synchronises)."""
+        out = np.empty((_capi.GAIL_MAX_UPDATES, 6), np.float32)
+        n = check(self.lib, self.lib.grl_gail_get_losses(self.h, out.ctypes.data, out.size))
+        return out[:n].copy()
+
+    def gail_get_stats(self):
+        """(sum [obs_dim], sumsq [obs_dim], count) of the discriminator's input statistics, float64."""
+        s, q, c = np.empty(self.obs_dim, np.float64), np.empty(self.obs_dim, np.float64), C.c_double()
+        check(self.lib, self.lib.grl_gail_get_stats(self.h, s.ctypes.data, q.ctypes.data, C.byref(c)))
+        return s, q, c.value
+
+    def gail_set_stats(self, total, sumsq, count):
+        s = np.ascontiguousarray(total, dtype=np.float64).reshape(self.obs_dim)
+        q = np.ascontiguousarray(sumsq, dtype=np.float64).reshape(self.obs_dim)
+        check(self.lib, self.lib.grl_gail_set_stats(self.h, s.ctypes.data, q.ctypes.data, float(count)))
+
+    def gail_end(self):
+        check(self.lib, self.lib.grl_gail_end(self.h))
+        self._gail = None

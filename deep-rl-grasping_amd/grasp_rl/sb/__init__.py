@@ -3,3 +3,4 @@
 these modules under the import paths the reference's scripts use."""
 from .ppo2 import PPO2  # noqa: E402,F401
 from .trpo import TRPO  # noqa: E402,F401
+from .gail import GAIL  # noqa: E402,F401

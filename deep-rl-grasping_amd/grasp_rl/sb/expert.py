@@ -16,7 +16,8 @@ DEFAULT_IMAGE_FOLDER = "recorded_images"
 class DataLoader:
     """An order over ``indices`` of the dataset's tables, cut into minibatches of ``batch_size`` (the last one may be shorter).
     Iterating yields (observations, actions) like stable-baselines' loader; ``index_rows()`` is the same epoch as the
-    engine takes it: int32 [len(self), batch_size], a shorter last minibatch ending in -1."""
+    engine takes it: int32 [len(self), batch_size], a shorter last minibatch ending in -1; ``next_indices()`` is ``next()``
+    as indices."""
 
     def __init__(self, indices, observations, actions, batch_size, shuffle=True):
         self.indices = np.asarray(indices, np.int64).copy()
@@ -37,20 +38,29 @@ class DataLoader:
         rows.reshape(-1)[:len(order)] = order
         return rows
 
-    def __iter__(self):
+    def _epoch_indices(self):
         order = self._epoch_order()
         for k in range(0, len(order), self.batch_size):
-            ix = order[k:k + self.batch_size]
+            yield order[k:k + self.batch_size]
+
+    def __iter__(self):
+        for ix in self._epoch_indices():
             yield self.observations[ix], self.actions[ix]
 
-    def __next__(self):
+    def next_indices(self):
+        """The table rows of the batch ``__next__`` would hand out (the same ``np.random`` draws, the same cursor): GAIL gathers
+        them on the device."""
         if self._it is None:
-            self._it = iter(self)
+            self._it = self._epoch_indices()
         try:
             return next(self._it)
         except StopIteration:
-            self._it = iter(self)
+            self._it = self._epoch_indices()
             return next(self._it)
+
+    def __next__(self):
+        ix = self.next_indices()
+        return self.observations[ix], self.actions[ix]
 
 
 class ExpertDataset:

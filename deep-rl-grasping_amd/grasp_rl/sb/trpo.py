@@ -16,8 +16,8 @@ re-evaluates only its value afterwards.  Here ``finish`` evaluates V(last observ
 updated policy.
 
 Scope: the actor-critic ``MlpPolicy`` (two tanh towers, ``net_arch=[dict(vf=[...], pi=[...])]``) on ``Box`` actions, observations
-of any rank flattened in C order and not divided by 255, one environment (GRL_NUM_ENVS does not fan a TRPO env out).  GAIL and data
-parallelism are not defined for TRPO.  Everything else says what it refuses.  ``save_checkpoint`` / ``load_checkpoint`` -- or
+of any rank flattened in C order and not divided by 255, one environment (GRL_NUM_ENVS does not fan a TRPO env out).  The GAIL
+keywords and data parallelism are not defined for TRPO; GAIL is a class of its own (gail.py) over the two hooks of ``_learn_loop``.  Everything else says what it refuses.  ``save_checkpoint`` / ``load_checkpoint`` -- or
 GRL_CHECKPOINT_STATE=1 behind ``save`` / ``load`` -- keep the full training state next to the zip, and
 ``learn(n, reset_num_timesteps=False)`` on a restored model continues the batch that was in progress.  The policy this class
 accepts, acting, the frame of ``learn`` and the host half of a checkpoint are ``OnPolicyModel`` (on_policy.py), shared with ``PPO2``.
@@ -136,6 +136,13 @@ class TRPO(OnPolicyModel):
         self.episodes_so_far = extra["episodes_so_far"]
         self._oldpi, self._updated = extra["oldpi"], False
 
+    # the two places where GAIL (gail.py) differs from TRPO inside an iteration; nothing happens here
+    def _before_finish(self, eng, episode_start, ep_rets):
+        """The T slots are closed, GAE is not formed yet."""
+
+    def _after_update(self, eng, iters_so_far):
+        """The policy step and the value fit of iteration ``iters_so_far`` (counted from 0) are enqueued."""
+
     def _learn_loop(self, total_timesteps, callback, log_interval, writer, resume=None):
         eng, T = self.engine, self.timesteps_per_batch
         saved, finished, written, closed = None, False, 0, 0
@@ -209,6 +216,7 @@ class TRPO(OnPolicyModel):
                 break
             lp.update(cur_ep_ret=cur_ep_ret, cur_ep_len=cur_ep_len)
             if not finished:      # (a checkpoint taken in on_rollout_end holds the advantages already)
+                self._before_finish(eng, episode_start, ep_rets)
                 eng.finish(self._rows(obs, 1), episode_start)      # nextvpred = V(obs_T) * (1 - episode_start_T), GAE, tdlamret
                 callback.on_rollout_end()
             finished = False
@@ -219,6 +227,7 @@ class TRPO(OnPolicyModel):
                        if self.vf_iters > 0 and T >= VF_BATCH else None)
             eng.update(vf_perm)
             self._updated = True
+            self._after_update(eng, iters_so_far)
             timesteps_so_far += T
             self.num_timesteps += T
             iters_so_far += 1

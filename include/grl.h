@@ -476,7 +476,7 @@ int grl_trpo_debug_fvp(grl_handle h);
    _export / _import and grl_debug_fetch / _store work as on a PPO handle.  Debug names: those of the PPO rollout, and -- laid out like the gradient bucket ([n_trainable], the
    entries of the value variables 0) -- "trpo_g", "trpo_stepdir", "trpo_fullstep", "trpo_fvp_in", "trpo_fvp_out",
    "trpo_theta_old" (every trainable variable as it was when the update began); "trpo_atarg" [T]; "trpo_mean_old" [T, A] (the
-   old policy's means).  Every other entry point returns
+   old policy's means).  The grl_gail_* calls (below) open a GAIL session on a TRPO handle.  Every other entry point returns
    GRL_ERR_STATE on a TRPO handle before anything moves. */
 
 /* ---- Behaviour-cloning pretraining of a SAC handle's policy from recorded (observation, action) pairs: stable-baselines
@@ -519,6 +519,65 @@ int grl_bc_end(grl_handle h);
    [batch, 64, 64, C_img], vectors [batch, rup(obs_dim, 4)]), "bc_feat" [batch, rup(F, 4)], "bc_act" [batch, act_dim] (expert
    actions as gathered), "bc_mu", "bc_det" [batch, act_dim], "bc_dmu" [batch, rup(act_dim, 4)], "bc_loss" (the loss slots of the
    call), "bc_adam_m", "bc_adam_v" (moments over the trained range, which starts at parameter offset 0). */
+
+/* ---- GAIL on a TRPO handle: the discriminator of stable-baselines 2.10.1 gail/adversary.py (TransitionClassifier, Box
+   actions), its rewards for a rollout, and its update from the last rollout and a table of expert (observation, action) pairs.
+     D(obs, act) = W3 tanh(W2 tanh(W1 [ (obs - mean) / std | act ] + b1) + b2) + b3,   two hidden layers of `hidden` units
+   mean / std are those of common/mpi_running_mean_std.py with epsilon 1e-2: float64 sum (starts at 0), sumsq (1e-2) and count
+   (1e-2); mean = float32(sum / count), std = sqrt(max(float32(sumsq / count) - mean^2, 1e-2)) formed in float32.
+   Over generator logits g (n_g rows) and expert logits e (n_e rows), with ent(x) = (1 - sigmoid(x)) x + softplus(-x):
+     total = mean softplus(g) + mean softplus(-e) - entcoeff * mean over the n_g + n_e logits of ent
+   and the reward of a step is -log(1 - sigmoid(D(obs, clip(act, low, high))) + 1e-8).  The optimiser is TF-1 Adam (beta 0.9 /
+   0.999) with the session's own moments and beta powers.  A session is
+     grl_gail_query_sizes -> (the caller allocates `bytes` of device memory) -> grl_gail_begin -> ... -> grl_gail_end
+   and lives entirely in that buffer: it holds nothing a checkpoint carries, and the handle's own arenas, plan, launch tags and
+   grl_ppo_state_export bytes are what they are without it (the reward pass rewrites the rollout's reward array: that is all).
+   grl_gail_begin zeroes the buffer, sets the statistics to their start values and the optimiser's words, and initialises
+   NOTHING else: the caller stores the six parameter tensors (grl_gail_param_info; grl_debug_store "gail_params").
+   On every handle but a TRPO handle each grl_gail_* call is GRL_ERR_STATE before anything moves; on a TRPO handle without a
+   session so is every call but grl_gail_query_sizes / grl_gail_begin. */
+typedef struct grl_gail_config {
+  int32_t hidden;            /* hidden_size_adversary, 1 .. 1024 */
+  int32_t batch;             /* generator rows of an update (and the most expert rows), 1 .. n_steps */
+  float entcoeff;            /* adversary_entcoeff */
+  float lr, adam_eps;        /* d_stepsize; 1e-8 */
+  const float* act_low;      /* host, [act_dim]: the action space's bounds (high > low in every dimension) */
+  const float* act_high;
+} grl_gail_config;
+int grl_gail_query_sizes(grl_handle h, const grl_gail_config* c, size_t* bytes);
+/* zeroes the buffer, builds the launch plan; synchronises.  GRL_ERR_STATE while a session is open. */
+int grl_gail_begin(grl_handle h, const grl_gail_config* c, void* buf);
+/* tensor i of the six (TF order: adversary/fully_connected{,_1,_2}/{weights,biases}:0): its name, offset and size in floats
+   inside "gail_params" (every tensor starts on a 16-byte boundary) and its shape [rows, cols]; returns 6 */
+int grl_gail_param_info(grl_handle h, int i, char* name, int cap, int64_t* off, int64_t* numel, int32_t* rows, int32_t* cols);
+/* Valid when all n_steps slots are closed and grl_ppo_finish has not run yet, once per rollout (GRL_ERR_STATE otherwise):
+   rewrites the T stored rewards with the discriminator's in ONE batched pass over the rollout (the discriminator is fixed during
+   a rollout, so this equals per-step evaluation); the environment's rewards stay readable as "gail_true_rew".  Stream-ordered,
+   no synchronisation; grl_ppo_finish then forms GAE from the rewritten rewards. */
+int grl_gail_rewards(grl_handle h);
+/* n_updates discriminator updates, back to back on the handle's stream.  exp_obs [n_rows, obs_dim] and exp_act [n_rows,
+   act_dim]: device, float32; gen_idx [n_updates, batch]: device, int32, rows of the last finished rollout, all present (their
+   observations and UNCLIPPED actions are the generator's side); exp_idx [n_updates, batch]: device, int32, rows of the table --
+   a shorter expert batch ends in -1 entries (at least one row present).  The indices are checked on a host copy first (one
+   synchronisation, in front of the updates): GRL_ERR_INVALID names the update and the entry, and nothing moves.  Per update:
+   the statistics take the gathered generator rows, then the expert rows; THEN input, forward, loss and backward at the updated
+   statistics; then one Adam step.  Valid from grl_ppo_finish of a full rollout until the next grl_ppo_step writes a slot,
+   whether or not grl_trpo_update ran in between (GRL_ERR_STATE otherwise).  1 <= n_updates <= 4096. */
+int grl_gail_update(grl_handle h, const float* exp_obs, const float* exp_act, int64_t n_rows, const int32_t* gen_idx,
+                    const int32_t* exp_idx, int n_updates);
+/* host, synchronises: [n_updates, 6] of the last grl_gail_update -- generator_loss, expert_loss, entropy, entropy_loss
+   (= -entcoeff * entropy), generator_acc, expert_acc (the per-block sums of the loss launch, added in index order); returns
+   n_updates, GRL_ERR_INVALID when cap (in floats) is too small */
+int grl_gail_get_losses(grl_handle h, float* out, int cap);
+/* host, synchronise: the float64 statistics, sum / sumsq [obs_dim] and the count */
+int grl_gail_get_stats(grl_handle h, double* sum, double* sumsq, double* count);
+int grl_gail_set_stats(grl_handle h, const double* sum, const double* sumsq, double count);
+/* closes the session (synchronises): the buffer is the caller's again */
+int grl_gail_end(grl_handle h);
+/* Debug names while a session is open: "gail_params", "gail_adam_m", "gail_adam_v", "gail_grads" (laid out as
+   grl_gail_param_info says), "gail_x" [2 batch, rup(obs_dim + act_dim, 4)] (the last update's input: generator rows, then expert
+   rows), "gail_logits" [2 batch], "gail_dlogits" [2 batch, 4] (column 0), "gail_rew_x" [T, rup(obs_dim + act_dim, 4)] and
+   "gail_rew_logits" [T] (the last reward pass), "gail_true_rew" [T]. */
 
 /* debugging / parity: copy a named internal activation of the last update to the host.
    Names: "x_obs","x_next","feat_pi","feat_vf","feat_tgt","mu","log_std","pi","logp","qf1","qf2",
