@@ -1,7 +1,8 @@
 // bc_kernels.h -- the kernels of behaviour-cloning pretraining (SAC.pretrain: plan_bc.inl) that are not GEMMs: the minibatch
-// gather from a caller-owned (observation, action) table, the loss with its output gradient, the launch that closes the loss
-// of an update, and Adam over the trained range.  Everything between them -- the extractor, the dense layers, their backward
-// and weight-gradient launches, the slab reduction -- are the launches of the SAC plan restricted to the policy network.
+// gather from a caller-owned (observation, action) table, the loss with its output gradient, and the launch that closes the
+// loss of an update.  Everything else -- the extractor, the dense layers, their backward and weight-gradient launches, the slab
+// reduction, Adam over the trained range (adam_polyak_kernel on the session's own DevScalars) -- are the launches of the SAC plan
+// restricted to the policy network.
 //
 // One update on n valid rows (stable-baselines 2.10.1, BaseRLModel.pretrain with SAC._get_pretrain_placeholders):
 //   det = tanh(mu(obs));  a_env = low + 0.5 (det + 1)(high - low);  loss = mean over n * A of (a_exp - a_env)^2
@@ -9,7 +10,7 @@
 //   d loss / d mu_j = 2 s_j^2 (det_j - a'_j)(1 - det_j^2) / (n A).
 // Rows whose index is -1 (the tail of a final partial minibatch) contribute nothing to the loss or to any gradient.
 //
-// A session's words live in BcDev (in the caller's BC buffer).  The arrays of a call (table, indices) are written there by
+// A session's words live in BcDev, the optimiser's in a DevScalars behind it (both in the caller's BC buffer).  The arrays of a call (table, indices) are written there by
 // bc_open_kernel, so that the launch list of an update has fixed arguments and a call of n updates repeats ONE list: the
 // gather reads the index row of update `step`, the closing launch writes losses[step] and advances `step`.
 #pragma once
@@ -27,9 +28,6 @@ namespace grl {
 #define BC_LOSS_ROWS 256              /* rows per workgroup of the loss launch: one lane each */
 
 struct BcDev {
-  float beta1_power, beta2_power;     // TF AdamOptimizer non-slot variables of THIS session (start at beta1, beta2)
-  float adam_alpha;                   // lr * sqrt(1 - b2p) / (1 - b1p) of the current update
-  float lr;
   int32_t step;                       // update (batch) of the running call
   int32_t n_valid;                    // rows of the current minibatch whose index is not -1 (written by the gather)
   const float* obs;                   // the call's table [n_rows, obs_size] / [n_rows, A] and index rows [n, batch]
@@ -60,28 +58,12 @@ struct BcLossArgs {
 
 struct BcCloseArgs {
   BcDev* dev;
+  DevScalars* sc;                     // the session's optimiser words
   int batch, A;
   const float* row_loss;
   float* losses;                      // [GRL_BC_MAX_UPDATES]
   int tick;                           // 1: an update (Adam step size + beta powers), 0: evaluation
 };
-
-struct BcAdamArgs {
-  float* params; const float* grads; float* m; float* v;
-  int64_t n;                          // the trained range [0, n) of the parameter block: model/pi without its log-std head
-  const BcDev* dev;
-  float eps;
-};
-
-// rows of minibatch `step` that are present: absent rows are trailing -1 entries, so the first -1 is the count
-__device__ __forceinline__ int bc_count_valid(const int32_t* row, int batch) {
-  int lo = 0, hi = batch;             // row[i] >= 0 for i < lo, row[i] < 0 for i >= hi
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (row[mid] >= 0) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 __global__ void bc_open_kernel(BcDev* dev, const float* obs, const float* act, const int32_t* idx) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -95,7 +77,7 @@ __global__ __launch_bounds__(256) void bc_gather_kernel(BcGatherArgs a) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   const int32_t* row = a.dev->idx + (long)a.dev->step * a.batch;
   const long src = row[b] >= 0 ? row[b] : 0;
-  if (b == 0 && e == 0) a.dev->n_valid = bc_count_valid(row, a.batch);
+  if (b == 0 && e == 0) a.dev->n_valid = rows_present(row, a.batch);
   if (blockIdx.x == 0 && threadIdx.x < a.A) a.act_out[(long)b * a.A + threadIdx.x] = a.dev->act[src * a.A + threadIdx.x];
   if (a.vec_dim > 0) {
     if (e < a.vec_dim) a.x[(long)b * a.ldx + e] = a.dev->obs[src * a.vec_dim + e];
@@ -152,21 +134,8 @@ __global__ __launch_bounds__(64) void bc_close_kernel(BcCloseArgs a) {
   if (threadIdx.x != 0) return;
   BcDev* d = a.dev;
   if (d->step < GRL_BC_MAX_UPDATES) a.losses[d->step] = s / ((float)d->n_valid * (float)a.A);
-  if (a.tick) {
-    d->adam_alpha = d->lr * sqrtf(1.f - d->beta2_power) / (1.f - d->beta1_power);
-    d->beta1_power *= 0.9f;
-    d->beta2_power *= 0.999f;
-  }
+  if (a.tick) adam_tick_device(a.sc);
   d->step += 1;
-}
-
-__global__ __launch_bounds__(256) void bc_adam_kernel(BcAdamArgs a) {
-  const float alpha = a.dev->adam_alpha;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
-    float m = a.m[i], v = a.v[i], p = a.params[i];
-    adam_elem(a.grads[i], p, m, v, alpha, a.eps);
-    a.m[i] = m; a.v[i] = v; a.params[i] = p;
-  }
 }
 
 }  // namespace grl

@@ -1626,12 +1626,86 @@ int grl_profile_dump(grl_handle h, char* buf, int cap) {
   return GRL_OK;
 }
 
-// ---- behaviour-cloning pretraining (plan_bc.inl): a session on a SAC handle, in a buffer of the caller's
+// ---- sessions: behaviour-cloning pretraining on a SAC handle (plan_bc.inl), GAIL on a TRPO handle (plan_gail.inl), each in a
+// buffer of the caller's.  What the two share is written once here; the wording of every message is the entry point's own.
 #define SAC_ONLY(h, what)                                                                                        \
   do {                                                                                                           \
     if (!(h)) return fail(GRL_ERR_INVALID, "null handle");                                                       \
     if ((h)->cfg.algo != GRL_ALGO_SAC) return fail(GRL_ERR_STATE, what " is defined for SAC handles (grl_create)"); \
   } while (0)
+#define GAIL_SESSION(h, what)                                                                                     \
+  do {                                                                                                            \
+    TRPO_ONLY(h, what);                                                                                           \
+    if (!(h)->gail()) return fail(GRL_ERR_STATE, what " needs an open session (grl_gail_begin)");                 \
+  } while (0)
+
+static int check_act_bounds(grl_handle h, const float* low, const float* high, const char* who) {
+  for (int j = 0; j < h->cfg.act_dim; ++j)
+    if (!(high[j] > low[j]) || !std::isfinite(high[j]) || !std::isfinite(low[j]))
+      return fail(GRL_ERR_INVALID, std::string(who) + ": the action bounds must be finite with high > low (dimension " + std::to_string(j) + ")");
+  return GRL_OK;
+}
+
+extern "C++" {      // (two templates; everything here is static anyway)
+// a fresh record of a checked configuration: the bounds copied, the caller's pointers dropped
+template <class Plan, class Config>
+static std::unique_ptr<Session> session_fill(grl_handle h, const Config* c) {
+  std::unique_ptr<Plan> p(new Plan());
+  p->cfg = *c;
+  p->low.assign(c->act_low, c->act_low + h->cfg.act_dim);
+  p->high.assign(c->act_high, c->act_high + h->cfg.act_dim);
+  p->cfg.act_low = p->cfg.act_high = nullptr;
+  return p;
+}
+
+// n index rows of `batch` entries into a table of n_rows: every entry in [-1, n_rows), -1 only as a tail, at least one row present.
+// pre(u, b) may refuse entry b of row u first (nonzero: its error); where(u, b) names the entry, asked only when it is refused
+// (a string per entry in front of every call showed in the GAIL update's time); present: the rows' counts.
+template <class Pre, class Where>
+static int check_tail_rows(const int32_t* rows, int n, int batch, int64_t n_rows, Pre pre, Where where, std::vector<int>* present) {
+  for (int u = 0; u < n; ++u) {
+    const int32_t* row = rows + (size_t)u * batch;
+    bool tail = false;
+    int n_e = 0;
+    for (int b = 0; b < batch; ++b) {
+      if (int e = pre(u, b)) return e;
+      if (row[b] < -1 || row[b] >= n_rows) return fail(GRL_ERR_INVALID, where(u, b) + " is outside the table (" + std::to_string(row[b]) + ")");
+      if (row[b] == -1) { if (b == 0) return fail(GRL_ERR_INVALID, where(u, b) + ": a minibatch needs at least one row"); tail = true; }
+      else if (tail) return fail(GRL_ERR_INVALID, where(u, b) + " follows a -1: absent rows must be trailing");
+      else n_e += 1;
+    }
+    if (present) present->push_back(n_e);
+  }
+  return GRL_OK;
+}
+}  // extern "C++"
+
+// the plan built dry: the bytes a session of this record needs
+static int session_query(grl_handle h, std::unique_ptr<Session> s, size_t* bytes) {
+  if (int e = s->plan(*h)) return e;
+  *bytes = s->a.off + 256;
+  return GRL_OK;
+}
+
+// Installs the record and builds its plan into buf; then the whole buffer zero (parameters, moments, row padding, untouched
+// pixels), the tables and the optimiser's starting words.  On any failure the handle is left without a session.
+static int session_open(grl_handle h, std::unique_ptr<Session> s, void* buf, const float lr, const char* what) {
+  s->a.base = (char*)buf;
+  h->session = std::move(s);
+  Session& p = *h->session;
+  if (int e = p.plan(*h)) { h->uploads.clear(); h->session_drop(); return e; }
+  hipError_t e = hipMemsetAsync(buf, 0, p.a.off, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  for (auto& u : h->uploads)
+    if (e == hipSuccess) e = hipMemcpy(u.dst, u.bytes.data(), u.bytes.size(), hipMemcpyHostToDevice);
+  h->uploads.clear();
+  DevScalars s0;
+  memset(&s0, 0, sizeof(s0));
+  s0.beta1_power = 0.9f; s0.beta2_power = 0.999f; s0.lr = lr;
+  if (e == hipSuccess) e = hipMemcpy(p.sc, &s0, sizeof(s0), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { h->session_drop(); return fail(GRL_ERR_HIP, std::string(what) + " begin: " + hipGetErrorString(e)); }
+  return GRL_OK;
+}
 
 static int check_bc(grl_handle h, const grl_bc_config* c) {
   if (!c || !c->act_low || !c->act_high) return fail(GRL_ERR_INVALID, "null behaviour-cloning config or action bounds");
@@ -1639,81 +1713,41 @@ static int check_bc(grl_handle h, const grl_bc_config* c) {
   if (c->batch > h->cfg.batch_size)
     return fail(GRL_ERR_INVALID, "bc: batch " + std::to_string(c->batch) + " exceeds the handle's batch_size " + std::to_string(h->cfg.batch_size));
   if (!(c->lr > 0.f) || !(c->adam_eps > 0.f)) return fail(GRL_ERR_INVALID, "bc: lr and adam_eps must be > 0");
-  for (int j = 0; j < h->cfg.act_dim; ++j)
-    if (!(c->act_high[j] > c->act_low[j]) || !std::isfinite(c->act_high[j]) || !std::isfinite(c->act_low[j]))
-      return fail(GRL_ERR_INVALID, "bc: the action bounds must be finite with high > low (dimension " + std::to_string(j) + ")");
-  return GRL_OK;
-}
-
-static void bc_fill(grl_handle h, const grl_bc_config* c, BcPlan& p) {
-  p.cfg = *c;
-  p.low.assign(c->act_low, c->act_low + h->cfg.act_dim);
-  p.high.assign(c->act_high, c->act_high + h->cfg.act_dim);
-  p.cfg.act_low = p.cfg.act_high = nullptr;
+  return check_act_bounds(h, c->act_low, c->act_high, "bc");
 }
 
 int grl_bc_query_sizes(grl_handle h, const grl_bc_config* c, size_t* bytes) {
   SAC_ONLY(h, "grl_bc_query_sizes");
   if (!bytes) return fail(GRL_ERR_INVALID, "null out");
   if (int e = check_bc(h, c)) return e;
-  BcPlan p;
-  bc_fill(h, c, p);
-  if (int e = h->plan_bc(p)) return e;
-  for (auto* l : p.launches) delete l;
-  *bytes = p.a.off + 256;
-  return GRL_OK;
+  return session_query(h, session_fill<BcPlan>(h, c), bytes);
 }
 
 int grl_bc_begin(grl_handle h, const grl_bc_config* c, void* buf) {
   SAC_ONLY(h, "grl_bc_begin");
   if (!buf) return fail(GRL_ERR_INVALID, "null buffer");
-  if (h->bc) return fail(GRL_ERR_STATE, "a behaviour-cloning session is open on this handle (grl_bc_end)");
+  if (h->session) return fail(GRL_ERR_STATE, "a behaviour-cloning session is open on this handle (grl_bc_end)");
   if (int e = check_bc(h, c)) return e;
-  BcPlan* p = new BcPlan();
-  bc_fill(h, c, *p);
-  p->a.base = (char*)buf;
-  h->bc = p;
-  if (int e = h->plan_bc(*p)) { h->uploads.clear(); h->bc_drop(); return e; }
-  // the whole buffer zero (moments, row padding, untouched pixels), then the tables and the optimiser's words
-  hipError_t e = hipMemsetAsync(buf, 0, p->a.off, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  for (auto& u : h->uploads)
-    if (e == hipSuccess) e = hipMemcpy(u.dst, u.bytes.data(), u.bytes.size(), hipMemcpyHostToDevice);
-  h->uploads.clear();
-  BcDev d0;
-  memset(&d0, 0, sizeof(d0));
-  d0.beta1_power = 0.9f; d0.beta2_power = 0.999f; d0.lr = c->lr;
-  if (e == hipSuccess) e = hipMemcpy(p->dev, &d0, sizeof(d0), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { h->bc_drop(); return fail(GRL_ERR_HIP, std::string("bc begin: ") + hipGetErrorString(e)); }
-  return GRL_OK;
+  return session_open(h, session_fill<BcPlan>(h, c), buf, c->lr, "bc");
 }
 
-// a call's index rows on the host: every entry in [-1, n_rows), -1 only as a tail, at least one row present
+// a call's index rows on the host, checked before anything moves
 static int bc_check_idx(grl_handle h, const int32_t* idx, int64_t n_rows, int n) {
-  BcPlan& p = *h->bc;
+  BcPlan& p = *h->bc();
   const int batch = p.cfg.batch;
   p.idx_host.resize((size_t)n * batch);
   HIPCHK(hipMemcpyAsync(p.idx_host.data(), idx, p.idx_host.size() * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  for (int u = 0; u < n; ++u) {
-    const int32_t* row = p.idx_host.data() + (size_t)u * batch;
-    bool tail = false;
-    for (int b = 0; b < batch; ++b) {
-      const std::string where = "bc: index row " + std::to_string(u) + ", entry " + std::to_string(b);
-      if (row[b] < -1 || row[b] >= n_rows) return fail(GRL_ERR_INVALID, where + " is outside the table (" + std::to_string(row[b]) + ")");
-      if (row[b] == -1) { if (b == 0) return fail(GRL_ERR_INVALID, where + ": a minibatch needs at least one row"); tail = true; }
-      else if (tail) return fail(GRL_ERR_INVALID, where + " follows a -1: absent rows must be trailing");
-    }
-  }
-  return GRL_OK;
+  return check_tail_rows(p.idx_host.data(), n, batch, n_rows, [](int, int) { return 0; },
+                         [](int u, int b) { return "bc: index row " + std::to_string(u) + ", entry " + std::to_string(b); }, nullptr);
 }
 
 static int bc_run(grl_handle h, const char* what, const float* obs, const float* act, int64_t n_rows, const int32_t* idx, int n, bool train) {
-  if (!h->bc) return fail(GRL_ERR_STATE, std::string(what) + " needs an open session (grl_bc_begin)");
+  if (!h->bc()) return fail(GRL_ERR_STATE, std::string(what) + " needs an open session (grl_bc_begin)");
   if (!obs || !act || !idx || n_rows < 1) return fail(GRL_ERR_INVALID, "bc: null table or indices");
   if (n < 1 || n > GRL_BC_MAX_UPDATES) return fail(GRL_ERR_INVALID, "bc: the count of a call must be 1..65536");
   if (int e = bc_check_idx(h, idx, n_rows, n)) return e;
-  BcPlan& p = *h->bc;
+  BcPlan& p = *h->bc();
   hipLaunchKernelGGL(bc_open_kernel, dim3(1), dim3(1), 0, h->stream, p.dev, obs, act, idx);
   if (int e = h->run_repeated(train ? "bc_train" : "bc_eval", {train ? &p.ops_train : &p.ops_eval}, n)) return e;
   HIPCHK(hipGetLastError());
@@ -1733,27 +1767,21 @@ int grl_bc_eval(grl_handle h, const float* obs, const float* act, int64_t n_rows
 
 int grl_bc_get_losses(grl_handle h, float* out, int cap) {
   SAC_ONLY(h, "grl_bc_get_losses");
-  if (!h->bc) return fail(GRL_ERR_STATE, "grl_bc_get_losses needs an open session (grl_bc_begin)");
-  if (!out || cap < h->bc->last_n) return fail(GRL_ERR_INVALID, "bc: loss buffer too small");
+  BcPlan* p = h->bc();
+  if (!p) return fail(GRL_ERR_STATE, "grl_bc_get_losses needs an open session (grl_bc_begin)");
+  if (!out || cap < p->last_n) return fail(GRL_ERR_INVALID, "bc: loss buffer too small");
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (h->bc->last_n) HIPCHK(hipMemcpy(out, h->bc->losses, (size_t)h->bc->last_n * 4, hipMemcpyDeviceToHost));
-  return h->bc->last_n;
+  if (p->last_n) HIPCHK(hipMemcpy(out, p->losses, (size_t)p->last_n * 4, hipMemcpyDeviceToHost));
+  return p->last_n;
 }
 
 int grl_bc_end(grl_handle h) {
   SAC_ONLY(h, "grl_bc_end");
-  if (!h->bc) return fail(GRL_ERR_STATE, "grl_bc_end needs an open session (grl_bc_begin)");
+  if (!h->bc()) return fail(GRL_ERR_STATE, "grl_bc_end needs an open session (grl_bc_begin)");
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->bc_drop();
+  h->session_drop();
   return GRL_OK;
 }
-
-// ---- GAIL (plan_gail.inl): a session on a TRPO handle, in a buffer of the caller's
-#define GAIL_SESSION(h, what)                                                                                     \
-  do {                                                                                                            \
-    TRPO_ONLY(h, what);                                                                                           \
-    if (!(h)->gail) return fail(GRL_ERR_STATE, what " needs an open session (grl_gail_begin)");                   \
-  } while (0)
 
 static int check_gail(grl_handle h, const grl_gail_config* c) {
   if (!c || !c->act_low || !c->act_high) return fail(GRL_ERR_INVALID, "null GAIL config or action bounds");
@@ -1761,33 +1789,18 @@ static int check_gail(grl_handle h, const grl_gail_config* c) {
   if (c->batch < 1 || c->batch > h->tcfg.n_steps)
     return fail(GRL_ERR_INVALID, "gail: batch " + std::to_string(c->batch) + " is outside 1.." + std::to_string(h->tcfg.n_steps) + " (the handle's n_steps)");
   if (!(c->lr > 0.f) || !(c->adam_eps > 0.f) || !std::isfinite(c->entcoeff)) return fail(GRL_ERR_INVALID, "gail: lr and adam_eps must be > 0, entcoeff finite");
-  for (int j = 0; j < h->cfg.act_dim; ++j)
-    if (!(c->act_high[j] > c->act_low[j]) || !std::isfinite(c->act_high[j]) || !std::isfinite(c->act_low[j]))
-      return fail(GRL_ERR_INVALID, "gail: the action bounds must be finite with high > low (dimension " + std::to_string(j) + ")");
-  return GRL_OK;
-}
-
-static void gail_fill(grl_handle h, const grl_gail_config* c, GailPlan& p) {
-  p.cfg = *c;
-  p.low.assign(c->act_low, c->act_low + h->cfg.act_dim);
-  p.high.assign(c->act_high, c->act_high + h->cfg.act_dim);
-  p.cfg.act_low = p.cfg.act_high = nullptr;
+  return check_act_bounds(h, c->act_low, c->act_high, "gail");
 }
 
 int grl_gail_query_sizes(grl_handle h, const grl_gail_config* c, size_t* bytes) {
   TRPO_ONLY(h, "grl_gail_query_sizes");
   if (!bytes) return fail(GRL_ERR_INVALID, "null out");
   if (int e = check_gail(h, c)) return e;
-  std::unique_ptr<GailPlan> p(new GailPlan());
-  gail_fill(h, c, *p);
-  if (int e = h->plan_gail(*p)) return e;
-  for (auto* l : p->launches) delete l;
-  *bytes = p->a.off + 256;
-  return GRL_OK;
+  return session_query(h, session_fill<GailPlan>(h, c), bytes);
 }
 
 static int gail_store_stats(grl_handle h, const double* sum, const double* sumsq, double count) {
-  GailPlan& p = *h->gail;
+  GailPlan& p = *h->gail();
   const std::vector<double> cnt((size_t)p.od, count);
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(p.sum, sum, (size_t)p.od * 8, hipMemcpyHostToDevice));
@@ -1804,26 +1817,13 @@ static int gail_store_stats(grl_handle h, const double* sum, const double* sumsq
 int grl_gail_begin(grl_handle h, const grl_gail_config* c, void* buf) {
   TRPO_ONLY(h, "grl_gail_begin");
   if (!buf) return fail(GRL_ERR_INVALID, "null buffer");
-  if (h->gail) return fail(GRL_ERR_STATE, "a GAIL session is open on this handle (grl_gail_end)");
+  if (h->session) return fail(GRL_ERR_STATE, "a GAIL session is open on this handle (grl_gail_end)");
   if (int e = check_gail(h, c)) return e;
-  GailPlan* p = new GailPlan();
-  gail_fill(h, c, *p);
-  p->a.base = (char*)buf;
-  h->gail = p;
-  if (int e = h->plan_gail(*p)) { h->uploads.clear(); h->gail_drop(); return e; }
-  // the whole buffer zero (parameters, moments, row padding), then the tables, the optimiser's words and the statistics' start
-  hipError_t e = hipMemsetAsync(buf, 0, p->a.off, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  for (auto& u : h->uploads)
-    if (e == hipSuccess) e = hipMemcpy(u.dst, u.bytes.data(), u.bytes.size(), hipMemcpyHostToDevice);
-  h->uploads.clear();
-  DevScalars s0;
-  memset(&s0, 0, sizeof(s0));
-  s0.beta1_power = 0.9f; s0.beta2_power = 0.999f; s0.lr = c->lr;
-  if (e == hipSuccess) e = hipMemcpy(p->sc, &s0, sizeof(s0), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { h->gail_drop(); return fail(GRL_ERR_HIP, std::string("gail begin: ") + hipGetErrorString(e)); }
-  const std::vector<double> sum0((size_t)p->od, 0.0), sumsq0((size_t)p->od, 1e-2);
-  if (int e2 = gail_store_stats(h, sum0.data(), sumsq0.data(), 1e-2)) { h->gail_drop(); return e2; }
+  if (int e = session_open(h, session_fill<GailPlan>(h, c), buf, c->lr, "gail")) return e;
+  // the statistics' start
+  const int od = h->gail()->od;
+  const std::vector<double> sum0((size_t)od, 0.0), sumsq0((size_t)od, 1e-2);
+  if (int e = gail_store_stats(h, sum0.data(), sumsq0.data(), 1e-2)) { h->session_drop(); return e; }
   h->gail_rewritten = false;
   return GRL_OK;
 }
@@ -1831,7 +1831,7 @@ int grl_gail_begin(grl_handle h, const grl_gail_config* c, void* buf) {
 int grl_gail_param_info(grl_handle h, int i, char* name, int cap, int64_t* off, int64_t* numel, int32_t* rows, int32_t* cols) {
   GAIL_SESSION(h, "grl_gail_param_info");
   if (i < 0 || i >= 6) return fail(GRL_ERR_INVALID, "gail: parameter index must be 0..5");
-  const GailPlan::Tensor& t = h->gail->tensors[i];
+  const GailPlan::Tensor& t = h->gail()->tensors[i];
   if (name && cap > 0) { strncpy(name, t.name, cap - 1); name[cap - 1] = 0; }
   if (off) *off = t.off;
   if (numel) *numel = t.numel;
@@ -1845,38 +1845,28 @@ int grl_gail_rewards(grl_handle h) {
   if (h->ppo_closed != h->pcfg.n_steps || h->ppo_finished)
     return fail(GRL_ERR_STATE, "grl_gail_rewards rewrites the rewards of a full rollout that grl_ppo_finish has not closed yet: n_steps slots must be closed");
   if (h->gail_rewritten) return fail(GRL_ERR_STATE, "grl_gail_rewards: the rewards of this rollout are the discriminator's already");
-  if (int e = h->run_seq("gail_rewards", {&h->gail->ops_rewards})) return e;
+  if (int e = h->run_seq("gail_rewards", {&h->gail()->ops_rewards})) return e;
   HIPCHK(hipGetLastError());
   h->gail_rewritten = true;
   return GRL_OK;
 }
 
-// a call's index rows on the host: generator rows all present and inside the rollout; expert rows inside the table, -1 only as
-// a tail, at least one row present (bc_check_idx)
+// a call's index rows on the host: generator rows all present and inside the rollout; expert rows by check_tail_rows
 static int gail_check_idx(grl_handle h, const int32_t* gen_idx, const int32_t* exp_idx, int64_t n_rows, int n, std::vector<int>& ne) {
-  GailPlan& p = *h->gail;
+  GailPlan& p = *h->gail();
   const int batch = p.cfg.batch, T = h->tcfg.n_steps;
   const size_t cnt = (size_t)n * batch;
   p.idx_host.resize(2 * cnt);
   HIPCHK(hipMemcpyAsync(p.idx_host.data(), gen_idx, cnt * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(p.idx_host.data() + cnt, exp_idx, cnt * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  for (int u = 0; u < n; ++u) {
-    const int32_t* g = p.idx_host.data() + (size_t)u * batch;
-    const int32_t* row = g + cnt;
-    bool tail = false;
-    int n_e = 0;
-    for (int b = 0; b < batch; ++b) {
-      const std::string at = "update " + std::to_string(u) + ", entry " + std::to_string(b);
-      if (g[b] < 0 || g[b] >= T) return fail(GRL_ERR_INVALID, "gail: generator index of " + at + " is outside the rollout (" + std::to_string(g[b]) + ")");
-      if (row[b] < -1 || row[b] >= n_rows) return fail(GRL_ERR_INVALID, "gail: expert index of " + at + " is outside the table (" + std::to_string(row[b]) + ")");
-      if (row[b] == -1) { if (b == 0) return fail(GRL_ERR_INVALID, "gail: expert index of " + at + ": a minibatch needs at least one row"); tail = true; }
-      else if (tail) return fail(GRL_ERR_INVALID, "gail: expert index of " + at + " follows a -1: absent rows must be trailing");
-      else n_e += 1;
-    }
-    ne.push_back(n_e);
-  }
-  return GRL_OK;
+  const int32_t* gen = p.idx_host.data();
+  auto entry = [](int u, int b) { return "update " + std::to_string(u) + ", entry " + std::to_string(b); };
+  return check_tail_rows(gen + cnt, n, batch, n_rows, [&](int u, int b) {
+    const int32_t g = gen[(size_t)u * batch + b];
+    if (g >= 0 && g < T) return 0;
+    return fail(GRL_ERR_INVALID, "gail: generator index of " + entry(u, b) + " is outside the rollout (" + std::to_string(g) + ")");
+  }, [&](int u, int b) { return "gail: expert index of " + entry(u, b); }, &ne);
 }
 
 int grl_gail_update(grl_handle h, const float* exp_obs, const float* exp_act, int64_t n_rows, const int32_t* gen_idx,
@@ -1885,7 +1875,7 @@ int grl_gail_update(grl_handle h, const float* exp_obs, const float* exp_act, in
   if (n_updates < 1 || n_updates > GRL_GAIL_MAX_UPDATES) return fail(GRL_ERR_INVALID, "gail: the count of a call must be 1..4096");
   if (!exp_obs || !exp_act || !gen_idx || !exp_idx || n_rows < 1) return fail(GRL_ERR_INVALID, "gail: null table or indices");
   if (!h->ppo_held) return fail(GRL_ERR_STATE, "grl_gail_update reads the last finished rollout: none is held (grl_ppo_finish .. the next grl_ppo_step)");
-  GailPlan& p = *h->gail;
+  GailPlan& p = *h->gail();
   std::vector<int> ne;
   if (int e = gail_check_idx(h, gen_idx, exp_idx, n_rows, n_updates, ne)) return e;
   launch_gail_open(p.dev, exp_obs, exp_act, gen_idx, exp_idx, h->stream);
@@ -1898,7 +1888,7 @@ int grl_gail_update(grl_handle h, const float* exp_obs, const float* exp_act, in
 
 int grl_gail_get_losses(grl_handle h, float* out, int cap) {
   GAIL_SESSION(h, "grl_gail_get_losses");
-  GailPlan& p = *h->gail;
+  GailPlan& p = *h->gail();
   const int nu = p.last_n, nb = p.nblk;
   if (!out || cap < nu * GAIL_DIAG) return fail(GRL_ERR_INVALID, "gail: loss buffer too small");
   std::vector<float> part((size_t)std::max(1, nu * nb * GAIL_DIAG));
@@ -1918,7 +1908,7 @@ int grl_gail_get_losses(grl_handle h, float* out, int cap) {
 int grl_gail_get_stats(grl_handle h, double* sum, double* sumsq, double* count) {
   GAIL_SESSION(h, "grl_gail_get_stats");
   if (!sum || !sumsq || !count) return fail(GRL_ERR_INVALID, "null argument");
-  GailPlan& p = *h->gail;
+  GailPlan& p = *h->gail();
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(sum, p.sum, (size_t)p.od * 8, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(sumsq, p.sumsq, (size_t)p.od * 8, hipMemcpyDeviceToHost));
@@ -1935,7 +1925,7 @@ int grl_gail_set_stats(grl_handle h, const double* sum, const double* sumsq, dou
 int grl_gail_end(grl_handle h) {
   GAIL_SESSION(h, "grl_gail_end");
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->gail_drop();
+  h->session_drop();
   return GRL_OK;
 }
 

@@ -274,6 +274,15 @@ __device__ __forceinline__ void adam_tick_device(DevScalars* sc) {
   sc->beta1_power *= 0.9f;
   sc->beta2_power *= 0.999f;
 }
+// rows of a session's index row that are present: absent rows are trailing -1 entries, so the first -1 is the count
+__device__ __forceinline__ int rows_present(const int32_t* row, int batch) {
+  int lo = 0, hi = batch;             // row[i] >= 0 for i < lo, row[i] < 0 for i >= hi
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (row[mid] >= 0) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
 // what ONE thread of a gather launch that is not `quiet` leaves in the device scalars.  rng_step itself is advanced by the
 // (single-workgroup) loss reduction later in the update: a counter bumped by the last of these 8192 workgroups would
 // serialise 8192 same-address atomics (~100 us)

@@ -355,8 +355,26 @@ struct HeadGrad {
   float* g[GRL_MAX_LAYERS];
   int ld0 = 0;   // row stride of g[0] (fused heads: the critics' g[0] are column blocks of one buffer)
 };
-struct BcPlan;   // an open behaviour-cloning session (plan_bc.inl)
-struct GailPlan; // an open GAIL session (plan_gail.inl)
+// An open session: a plan of its own on an existing handle, built into a buffer the caller owns (grl_*_begin .. grl_*_end).  The
+// record holds what every session holds; BcPlan (plan_bc.inl, SAC handles) and GailPlan (plan_gail.inl, TRPO handles) add their
+// device pointers and op lists.  grl_ctx::plan_session lends the handle's builders to it, grl_ctx::session_drop ends it.
+struct Session {
+  const char* const prefix;             // of its graph keys and debug views: "bc_", "gail_"
+  std::vector<float> low, high;         // the action space's bounds
+  Arena a;                              // the session buffer
+  DevScalars* sc = nullptr;             // the optimiser's words of THIS session (adam_tick_device, adam_op)
+  std::vector<Launch*> launches;        // the GEMM launches of this plan, owned (the handle's own list is left as it was)
+  std::vector<ReduceDesc> reduces;
+  std::vector<std::string> dbg_names;
+  std::vector<int32_t> idx_host;        // host copy of a call's index rows (checked before anything moves)
+  int last_n = 0;                       // updates / batches the last call left
+  explicit Session(const char* pre) : prefix(pre) {}
+  Session(const Session&) = delete;
+  virtual ~Session() { for (auto* l : launches) delete l; }
+  virtual int plan(grl_ctx& h) = 0;     // builds into `a` (a.base == nullptr: sizes only)
+};
+struct BcPlan;
+struct GailPlan;
 
 }  // namespace grl
 
@@ -509,8 +527,7 @@ struct grl_ctx {
   std::map<std::string, std::pair<const float*, int64_t>> dbg;
 
   ~grl_ctx() {
-    bc_drop();
-    gail_drop();
+    session_drop();
     if (pin_in) hipHostFree(pin_in);
     if (pin_out) hipHostFree(pin_out);
     if (act_io_host) hipHostFree(act_io_host);
@@ -1653,17 +1670,19 @@ struct grl_ctx {
   grl_trpo_config tcfg = {};
   TrpoDev* trpo_dev = nullptr;
   std::vector<Op> ops_trpo_policy, ops_trpo_vf, ops_trpo_fvp;
-  // behaviour-cloning pretraining of a SAC handle (plan_bc.inl): the open session, built at grl_bc_begin into the caller's buffer
-  BcPlan* bc = nullptr;
+  // The open session, built at grl_bc_begin / grl_gail_begin into the caller's buffer: behaviour cloning on a SAC handle
+  // (plan_bc.inl), GAIL on a TRPO handle (plan_gail.inl) -- a handle is one kind, so there is one slot; bc() / gail() are null on
+  // the other kind.  plan_session lends the handle's builders to the session's arena and lists while `build` runs.
+  std::unique_ptr<Session> session;
+  BcPlan* bc() const;
+  GailPlan* gail() const;
+  template <class Build> int plan_session(Session& s, Build build);
+  void session_drop();
   int plan_bc(BcPlan& p);
-  void bc_drop();
-  // GAIL on a TRPO handle (plan_gail.inl): the open session, built at grl_gail_begin into the caller's buffer.  Host words beside
-  // it, no part of any exported state: a finished full rollout is still in the replay arena (grl_ppo_finish .. the next
-  // grl_ppo_step); the rewards of the rollout being closed are already the discriminator's
-  GailPlan* gail = nullptr;
-  bool ppo_held = false, gail_rewritten = false;
   int plan_gail(GailPlan& p);
-  void gail_drop();
+  // Host words of the rollout beside a GAIL session, no part of any exported state: a finished full rollout is still in the replay
+  // arena (grl_ppo_finish .. the next grl_ppo_step); the rewards of the rollout being closed are already the discriminator's
+  bool ppo_held = false, gail_rewritten = false;
   int plan_ae_general(const AeNet& net);   // ... of any supported network but the shipped one (GRL_TUNE ae_general=1: that one too)
   int enc_dim = 100;   // floats per image grl_encode returns (auto-encoder handles: their encoding_dim)
   float* ae_x = nullptr;            // [B, 4096] minibatch of depth images (staged per step)
@@ -1699,6 +1718,37 @@ int grl_ctx::plan() {
   const int e = cfg.algo == GRL_ALGO_SAC ? plan_sac() : (cfg.algo == GRL_ALGO_AE ? plan_ae() : (cfg.algo == GRL_ALGO_PPO ? plan_ppo() : (cfg.algo == GRL_ALGO_TRPO ? plan_trpo() : plan_q())));
   sw.note();
   return e;
+}
+
+// Builds a session's plan into s.a (base == nullptr: sizes only, nothing is recorded for upload).  While `build` runs, the helpers
+// of the handle's own plans -- which carve from `wk`, list their reductions in `reduces` and own their launches in `launches` --
+// work on the session's arena and lists; the handle's are put back before this returns.
+template <class Build>
+int grl_ctx::plan_session(Session& s, Build build) {
+  const bool was_dry = dry;
+  dry = s.a.base == nullptr;
+  std::swap(wk, s.a);
+  std::swap(reduces, s.reduces);
+  const size_t n_launches = launches.size();
+  build();
+  s.launches.assign(launches.begin() + n_launches, launches.end());
+  launches.resize(n_launches);
+  std::swap(reduces, s.reduces);
+  std::swap(wk, s.a);
+  dry = was_dry;
+  return GRL_OK;
+}
+
+// Ends the open session, if any: its debug views, its graphs (by key prefix), the record with its launches
+void grl_ctx::session_drop() {
+  if (!session) return;
+  for (auto& n : session->dbg_names) dbg.erase(n);
+  const std::string pre = session->prefix;
+  for (auto it = graphs.begin(); it != graphs.end();) {
+    if (it->first.compare(0, pre.size(), pre) == 0) { (void)hipGraphExecDestroy(it->second); it = graphs.erase(it); }
+    else ++it;
+  }
+  session.reset();
 }
 
 #include "plan_sac.inl"

@@ -85,16 +85,6 @@ __device__ __forceinline__ float gail_sigmoid(float x) {
   return x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
 }
 
-// rows of the index row that are present: absent rows are trailing -1 entries (bc_count_valid of bc_kernels.h)
-__device__ __forceinline__ int gail_count_valid(const int32_t* row, int batch) {
-  int lo = 0, hi = batch;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (row[mid] >= 0) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 // float32 mean / std of a column from its float64 sums (mpi_running_mean_std.py: every operation rounded, nothing contracted)
 __host__ __device__ __forceinline__ void gail_mean_sd(double sum, double sumsq, double count, float& mean, float& sd) {
 #ifdef __clang__
@@ -176,7 +166,7 @@ __global__ __launch_bounds__(256) void gail_input_kernel(GailInputArgs a) {
     gi = a.dev->gen_idx + u * n_g;
     ei = a.dev->exp_idx + u * n_g;
     e_obs = a.dev->exp_obs; e_act = a.dev->exp_act;
-    n_e = gail_count_valid(ei, n_g);
+    n_e = rows_present(ei, n_g);
     if (c == 0) {
       a.dev->cur = (int32_t)u;
       a.dev->n_e = n_e;

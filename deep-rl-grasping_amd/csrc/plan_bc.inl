@@ -2,32 +2,30 @@
 // part of engine.hip (included there, same translation unit: the plans are methods of grl_ctx).
 //
 // The plan covers NETWORK 0 (model/pi) only, at its own row count bc_batch <= cfg.batch_size, and lives entirely in the session
-// buffer the caller hands to grl_bc_begin: the optimiser's moments and words, the loss slots, the minibatch's activations and
-// gradients, the addressing tables and the slabs.  Nothing of the SAC plan is touched -- its work arena, launch lists, tables
-// and debug views stay as grl_create left them -- and the body of an update is built from the SAC plan's own problem builders
-// and launches (conv_stack_fwd or a launch per layer, fc_fwd, the dense forward / backward-data launches, exact-tap convolution
-// backward, weight gradients into slabs, the ordered slab reduction): no kernel of those changes, and no sum is formed by
-// atomics.  New are the gather from the caller's table, the loss launch, the closing launch and Adam (bc_kernels.h).
+// buffer the caller hands to grl_bc_begin: the session's words (BcDev), the optimiser's words (a DevScalars of its own) and
+// moments, the loss slots, the minibatch's activations and gradients, the addressing tables and the slabs.  The record is a
+// Session (engine.hip): grl_ctx::plan_session lends the handle's builders to it, so nothing of the SAC plan is touched -- its work
+// arena, launch lists, tables and debug views stay as grl_create left them -- and the body of an update is built from the SAC
+// plan's own problem builders and launches (conv_stack_fwd or a launch per layer, fc_fwd, the dense forward / backward-data
+// launches, exact-tap convolution backward, weight gradients into slabs, the ordered slab reduction, adam_op over the trained
+// range): no kernel of those changes, and no sum is formed by atomics.  New are the gather from the caller's table, the loss
+// launch and the closing launch (bc_kernels.h).
 //
 // An update (MLP, two hidden layers: 11 launches; depth CNN with the forward stack: 18):
 //   bc_gather | [conv_stack_fwd | conv1..3_fwd] fc_fwd | heads_fwd x (L + 1) | bc_loss | bc_close |
 //   heads_bwd x L | [heads_dfeat fc_bwd conv3_bwd conv2_bwd] | wgrad_dense [wgrad_small] [wgrad_conv] | reduce_slabs | bc_adam
 // An evaluation batch is the list up to bc_close (bc_loss without d mu, bc_close without the optimiser's tick).
 
-struct grl::BcPlan {
+struct grl::BcPlan : Session {
   grl_bc_config cfg{};
-  std::vector<float> low, high;
-  Arena a;                              // the session buffer
   BcDev* dev = nullptr;
   float *m = nullptr, *v = nullptr, *losses = nullptr;
   int64_t n_bc = 0;                     // trained range [0, n_bc) of the parameter block
   std::vector<Op> ops_train, ops_eval;
-  std::vector<Launch*> launches;        // the GEMM launches of this plan (the handle's own list is left as it was)
-  std::vector<ReduceDesc> reduces;
-  std::vector<std::string> dbg_names;
-  std::vector<int32_t> idx_host;        // host copy of a call's indices (checked before anything moves)
-  int last_n = 0;                       // losses the last call left
+  BcPlan() : Session("bc_") {}
+  int plan(grl_ctx& h) override { return h.plan_bc(*this); }
 };
+inline grl::BcPlan* grl_ctx::bc() const { return cfg.algo == GRL_ALGO_SAC ? static_cast<BcPlan*>(session.get()) : nullptr; }
 
 namespace {
 
@@ -63,9 +61,10 @@ struct BcPlanner {
     nd = cnn && c.extractor == GRL_EXTRACTOR_AUGMENTED ? c.n_direct : 0;
   }
 
-  // the session's state: optimiser words and moments over the trained range, loss slots, the action space's tables
+  // the session's state: its words, the optimiser's words and moments over the trained range, loss slots, the action space's tables
   void state() {
     p.dev = (BcDev*)wk.take(sizeof(BcDev));
+    p.sc = (DevScalars*)wk.take(sizeof(DevScalars));
     p.n_bc = h.m_pi.ow[1];              // model/pi is laid out first and its log-std head last: [0, dense_1/kernel)
     p.m = wk.f32(p.n_bc);
     p.v = wk.f32(p.n_bc);
@@ -155,7 +154,7 @@ struct BcPlanner {
       Op op; op.tag = "bc_loss";
       op.run = [la](hipStream_t s) { hipLaunchKernelGGL(bc_loss_kernel, dim3((la.batch + BC_LOSS_ROWS - 1) / BC_LOSS_ROWS), dim3(BC_LOSS_ROWS), 0, s, la); };
       to.push_back(op);
-      BcCloseArgs ca{p.dev, Bb, A, row_loss, p.losses, train};
+      BcCloseArgs ca{p.dev, p.sc, Bb, A, row_loss, p.losses, train};
       Op oc; oc.tag = "bc_close";
       oc.run = [ca](hipStream_t s) { hipLaunchKernelGGL(bc_close_kernel, dim3(1), dim3(64), 0, s, ca); };
       to.push_back(oc);
@@ -219,11 +218,11 @@ struct BcPlanner {
   // slabs -> the gradient bucket (sums in slab order), then Adam over the trained range
   void reduce_and_apply() {
     tail.push_back(h.close_reduction().op);            // (into the session buffer: it stands in for the work arena here)
-    BcAdamArgs aa{h.params, h.grads, p.m, p.v, p.n_bc, p.dev, p.cfg.adam_eps};
-    const int blocks = (int)std::min<int64_t>(2048, (p.n_bc + 255) / 256);
-    Op oa; oa.tag = "bc_adam";
-    oa.run = [aa, blocks](hipStream_t s) { hipLaunchKernelGGL(bc_adam_kernel, dim3(blocks), dim3(256), 0, s, aa); };
-    tail.push_back(oa);
+    AdamArgs aa;
+    memset(&aa, 0, sizeof(aa));
+    aa.params = h.params; aa.grads = h.grads; aa.m = p.m; aa.v = p.v; aa.n_train = p.n_bc; aa.sc = p.sc;
+    aa.grad_scale = 1.f; aa.eps = p.cfg.adam_eps; aa.target = h.params;
+    tail.push_back(grl_ctx::adam_op("bc_adam", aa));
   }
 
   void assemble() {
@@ -251,16 +250,8 @@ struct BcPlanner {
 
 }  // namespace
 
-// Builds the plan of `p.cfg` into p.a (base == nullptr: sizes only, nothing is recorded for upload).  While it runs, the
-// helpers of the SAC plan -- which carve from `wk`, list their reductions in `reduces` and own their launches in `launches` --
-// work on the session's arena and lists; the handle's are put back before this returns.
 int grl_ctx::plan_bc(BcPlan& p) {
-  const bool was_dry = dry;
-  dry = p.a.base == nullptr;
-  std::swap(wk, p.a);
-  std::swap(reduces, p.reduces);
-  const size_t n_launches = launches.size();
-  {
+  return plan_session(p, [&] {
     BcPlanner b(*this, p);
     b.state();
     b.workspace();
@@ -272,23 +263,5 @@ int grl_ctx::plan_bc(BcPlan& p) {
     b.reduce_and_apply();
     b.assemble();
     if (!dry) b.debug_views();
-  }
-  p.launches.assign(launches.begin() + n_launches, launches.end());
-  launches.resize(n_launches);
-  std::swap(reduces, p.reduces);
-  std::swap(wk, p.a);
-  dry = was_dry;
-  return GRL_OK;
-}
-
-void grl_ctx::bc_drop() {
-  if (!bc) return;
-  for (auto& n : bc->dbg_names) dbg.erase(n);
-  for (auto it = graphs.begin(); it != graphs.end();) {
-    if (it->first.compare(0, 3, "bc_") == 0) { (void)hipGraphExecDestroy(it->second); it = graphs.erase(it); }
-    else ++it;
-  }
-  for (auto* l : bc->launches) delete l;
-  delete bc;
-  bc = nullptr;
+  });
 }

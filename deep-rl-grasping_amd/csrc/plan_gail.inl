@@ -3,6 +3,7 @@
 //   D(obs, act) = W3 tanh(W2 tanh(W1 [ (obs - mean) / std | act ] + b1) + b2) + b3
 // with the running statistics of common/mpi_running_mean_std.py (epsilon 1e-2) and an Adam of its own.
 //
+// The record is a Session (engine.hip; grl_ctx::plan_session lends the handle's builders to it, as for behaviour cloning).
 // Everything of the session lives in the buffer the caller hands to grl_gail_begin: the device words, the optimiser's words and
 // moments, the float64 statistics and their float32 mean / std, the six parameter tensors and their gradient bucket, the loss
 // slots, the inputs, activations and gradients of both passes, the launch tables and the slabs.  Nothing of the TRPO plan is
@@ -17,12 +18,9 @@
 //           index order); the output launch                                                                            (5)
 //     BWD   per level: backward-data + tanh_bwd; weight gradients; reduce_slabs                                        (6)
 
-struct grl::GailPlan {
+struct grl::GailPlan : Session {
   grl_gail_config cfg{};
-  std::vector<float> low, high;
-  Arena a;                              // the session buffer
   GailDev* dev = nullptr;
-  DevScalars* sc = nullptr;
   double *sum = nullptr, *sumsq = nullptr, *count = nullptr;
   float *mean = nullptr, *sd = nullptr;
   float *params = nullptr, *m = nullptr, *v = nullptr, *grads = nullptr, *diag = nullptr, *true_rew = nullptr;
@@ -30,13 +28,11 @@ struct grl::GailPlan {
   int od = 0, nblk = 0;
   struct Tensor { const char* name; int64_t off, numel; int rows, cols; } tensors[6];
   std::vector<Op> ops_rewards, ops_update;
-  std::vector<Launch*> launches;        // the GEMM launches of this plan (the handle's own list is left as it was)
-  std::vector<ReduceDesc> reduces;
-  std::vector<std::string> dbg_names;
-  std::vector<int32_t> idx_host;        // host copy of a call's index rows (checked before anything moves)
-  int last_n = 0;                       // updates the last call left
-  std::vector<int> last_ne;             // ... and their expert row counts
+  std::vector<int> last_ne;             // expert row counts of the last call's updates
+  GailPlan() : Session("gail_") {}
+  int plan(grl_ctx& h) override { return h.plan_gail(*this); }
 };
+inline grl::GailPlan* grl_ctx::gail() const { return cfg.algo == GRL_ALGO_TRPO ? static_cast<GailPlan*>(session.get()) : nullptr; }
 
 namespace {
 
@@ -203,16 +199,8 @@ struct GailPlanner {
 
 }  // namespace
 
-// Builds the plan of `p.cfg` into p.a (base == nullptr: sizes only, nothing is recorded for upload).  While it runs, the helpers
-// of the other plans -- which carve from `wk`, list their reductions in `reduces` and own their launches in `launches` -- work on
-// the session's arena and lists; the handle's are put back before this returns (as plan_bc does).
 int grl_ctx::plan_gail(GailPlan& p) {
-  const bool was_dry = dry;
-  dry = p.a.base == nullptr;
-  std::swap(wk, p.a);
-  std::swap(reduces, p.reduces);
-  const size_t n_launches = launches.size();
-  {
+  return plan_session(p, [&] {
     GailPlanner g(*this, p);
     g.layout();
     g.state();
@@ -220,23 +208,5 @@ int grl_ctx::plan_gail(GailPlan& p) {
     g.rewards();
     g.update();
     if (!dry) g.debug_views();
-  }
-  p.launches.assign(launches.begin() + n_launches, launches.end());
-  launches.resize(n_launches);
-  std::swap(reduces, p.reduces);
-  std::swap(wk, p.a);
-  dry = was_dry;
-  return GRL_OK;
-}
-
-void grl_ctx::gail_drop() {
-  if (!gail) return;
-  for (auto& n : gail->dbg_names) dbg.erase(n);
-  for (auto it = graphs.begin(); it != graphs.end();) {
-    if (it->first.compare(0, 5, "gail_") == 0) { (void)hipGraphExecDestroy(it->second); it = graphs.erase(it); }
-    else ++it;
-  }
-  for (auto* l : gail->launches) delete l;
-  delete gail;
-  gail = nullptr;
+  });
 }

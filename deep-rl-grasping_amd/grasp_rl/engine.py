@@ -626,33 +626,41 @@ class SacEngine:
     def synchronize(self):
         self.be.synchronize()
 
-    # ------------------------------------------------------------------ behaviour cloning (grl_bc_*, csrc/plan_bc.inl)
+    # ------------------------------------------------------------------ sessions: behaviour cloning here (grl_bc_*, csrc/plan_bc.inl), GAIL on TrpoEngine
+    def _act_bounds(self, low, high):
+        return [np.ascontiguousarray(b, dtype=np.float32).reshape(self.A) for b in (low, high)]
+
+    def _session_open(self, cfg_struct, query_fn, begin_fn):
+        nbytes = C.c_size_t()
+        check(self.lib, query_fn(self.h, C.byref(cfg_struct), C.byref(nbytes)))
+        buf = self.be.alloc_f32(nbytes.value)
+        check(self.lib, begin_fn(self.h, C.byref(cfg_struct), C.c_void_p(self.be.ptr(buf))))
+        self._session = {"buf": buf, "batch": int(cfg_struct.batch), "keep": None}
+        return buf
+
+    def _upload_table(self, obs, act, width):
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        act = np.ascontiguousarray(act, dtype=np.float32).reshape(len(obs), self.A)
+        return self.be.to_device(obs.reshape(len(obs), width)), self.be.to_device(act), len(obs)
+
     def bc_begin(self, batch, learning_rate, adam_epsilon, act_low, act_high):
         """Opens a pretraining session at `batch` rows per minibatch (<= the engine's batch_size): fresh Adam moments and
         beta powers, its own buffer.  act_low / act_high: the action space's bounds."""
-        low = np.ascontiguousarray(act_low, dtype=np.float32).reshape(self.A)
-        high = np.ascontiguousarray(act_high, dtype=np.float32).reshape(self.A)
+        low, high = self._act_bounds(act_low, act_high)
         c = _capi.GrlBcConfig(int(batch), float(learning_rate), float(adam_epsilon), low.ctypes.data, high.ctypes.data)
-        nbytes = C.c_size_t()
-        check(self.lib, self.lib.grl_bc_query_sizes(self.h, C.byref(c), C.byref(nbytes)))
-        buf = self.be.alloc_f32(nbytes.value)
-        check(self.lib, self.lib.grl_bc_begin(self.h, C.byref(c), C.c_void_p(self.be.ptr(buf))))
-        self._bc = {"buf": buf, "batch": int(batch), "keep": None}
+        self._session_open(c, self.lib.grl_bc_query_sizes, self.lib.grl_bc_begin)
 
     def bc_upload(self, obs, act):
         """(observations, actions) of a dataset as float32 device arrays for bc_train / bc_eval: [n, obs_size], [n, A]."""
-        obs = np.ascontiguousarray(obs, dtype=np.float32)
-        n = obs.shape[0]
-        act = np.ascontiguousarray(act, dtype=np.float32).reshape(n, self.A)
-        return self.be.to_device(obs.reshape(n, -1)), self.be.to_device(act), n
+        return self._upload_table(obs, act, -1)
 
     def _bc_call(self, fn, table, idx):
         obs, act, n = table
-        idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1, self._bc["batch"])
+        idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1, self._session["batch"])
         di = self.be.to_device(idx)
         p = self.be.ptr
         check(self.lib, fn(self.h, p(obs), p(act), n, C.c_void_p(p(di)), idx.shape[0]))
-        self._bc["keep"] = (table, di)      # alive until the stream has consumed them
+        self._session["keep"] = (table, di)      # alive until the stream has consumed them
 
     def bc_train(self, table, idx):
         """One update per row of idx [n_updates, batch] (int32 rows of the table; a shorter minibatch ends in -1 entries),
@@ -671,7 +679,7 @@ class SacEngine:
 
     def bc_end(self):
         check(self.lib, self.lib.grl_bc_end(self.h))
-        self._bc = None
+        self._session = None
 
     # ------------------------------------------------------------------ inference
     def act(self, obs, deterministic=True, eps=None, raw=False, observed=False):
@@ -1006,49 +1014,40 @@ class TrpoEngine(PpoEngine):
         """Opens a GAIL session: a discriminator of two tanh layers of `hidden` units, `batch` generator rows per update, its own
         Adam and running statistics, in a buffer of its own.  The parameters start at zero: hand them as `params` (name ->
         array, the six ``adversary/...`` tensors) or store them with ``gail_set_parameters``."""
-        low = np.ascontiguousarray(act_low, dtype=np.float32).reshape(self.A)
-        high = np.ascontiguousarray(act_high, dtype=np.float32).reshape(self.A)
-        c = _capi.GrlGailConfig(int(hidden), int(batch), float(entcoeff), float(learning_rate), float(adam_epsilon), low.ctypes.data,
-                                high.ctypes.data)
-        nbytes = C.c_size_t()
-        check(self.lib, self.lib.grl_gail_query_sizes(self.h, C.byref(c), C.byref(nbytes)))
-        buf = self.be.alloc_f32(nbytes.value)
-        check(self.lib, self.lib.grl_gail_begin(self.h, C.byref(c), C.c_void_p(self.be.ptr(buf))))
-        table = []
+        low, high = self._act_bounds(act_low, act_high)
+        c = _capi.GrlGailConfig(int(hidden), int(batch), float(entcoeff), float(learning_rate), float(adam_epsilon), low.ctypes.data, high.ctypes.data)
+        self._session_open(c, self.lib.grl_gail_query_sizes, self.lib.grl_gail_begin)
+        table = self._session["table"] = []
         for i in range(6):
             name = C.create_string_buffer(128)
             off, numel, rows, cols = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
             check(self.lib, self.lib.grl_gail_param_info(self.h, i, name, 128, C.byref(off), C.byref(numel), C.byref(rows), C.byref(cols)))
             shape = (rows.value, cols.value) if i % 2 == 0 else (rows.value,)
             table.append((name.value.decode(), off.value, numel.value, shape))
-        self._gail = {"buf": buf, "batch": int(batch), "keep": None, "table": table}
         if params is not None:
             self.gail_set_parameters(params)
 
     def gail_param_shapes(self):
-        return OrderedDict((name, shape) for name, _, _, shape in self._gail["table"])
+        return OrderedDict((name, shape) for name, _, _, shape in self._session["table"])
 
     def _gail_block(self, name):
-        n = max(off + numel for _, off, numel, _ in self._gail["table"])
+        n = max(off + numel for _, off, numel, _ in self._session["table"])
         return self.fetch(name, ((n + 3) // 4 * 4,))
 
     def gail_get_parameters(self, block="gail_params"):
         """name -> array of the six tensors (block: "gail_params", "gail_adam_m", "gail_adam_v" or "gail_grads")."""
         flat = self._gail_block(block)
-        return OrderedDict((name, flat[off:off + numel].reshape(shape).copy()) for name, off, numel, shape in self._gail["table"])
+        return OrderedDict((name, flat[off:off + numel].reshape(shape).copy()) for name, off, numel, shape in self._session["table"])
 
     def gail_set_parameters(self, params):
         flat = self._gail_block("gail_params")
-        for name, off, numel, shape in self._gail["table"]:
+        for name, off, numel, shape in self._session["table"]:
             flat[off:off + numel] = np.asarray(params[name], np.float32).reshape(-1)
         self.store("gail_params", flat)
 
     def gail_upload(self, obs, act):
         """(observations, actions) of an expert dataset as float32 device arrays for gail_update: [n, obs_dim], [n, A]."""
-        obs = np.ascontiguousarray(obs, dtype=np.float32)
-        n = obs.shape[0]
-        act = np.ascontiguousarray(act, dtype=np.float32).reshape(n, self.A)
-        return self.be.to_device(obs.reshape(n, self.obs_dim)), self.be.to_device(act), n
+        return self._upload_table(obs, act, self.obs_dim)
 
     def gail_rewards(self):
         """Rewrites the rewards of the full, not yet finished rollout with the discriminator's (one batched pass)."""
@@ -1058,14 +1057,14 @@ class TrpoEngine(PpoEngine):
         """One discriminator update per row of gen_idx / exp_idx [n_updates, batch] (int32: rows of the last finished rollout;
         rows of the table, a shorter expert batch ending in -1 entries).  table: what gail_upload returned."""
         obs, act, n = table
-        b = self._gail["batch"]
+        b = self._session["batch"]
         gi = np.ascontiguousarray(gen_idx, dtype=np.int32).reshape(-1, b)
         ei = np.ascontiguousarray(exp_idx, dtype=np.int32).reshape(-1, b)
         if gi.shape != ei.shape:
             raise GrlError("gail_update: gen_idx and exp_idx must name the same number of updates")
         dg, de = self.be.to_device(gi), self.be.to_device(ei)
         p = self.be.ptr
-        self._gail["keep"] = (table, dg, de)      # alive until the stream has consumed them
+        self._session["keep"] = (table, dg, de)      # alive until the stream has consumed them
         check(self.lib, self.lib.grl_gail_update(self.h, p(obs), p(act), n, C.c_void_p(p(dg)), C.c_void_p(p(de)), gi.shape[0]))
 
     def gail_losses(self):
@@ -1087,4 +1086,4 @@ class TrpoEngine(PpoEngine):
 
     def gail_end(self):
         check(self.lib, self.lib.grl_gail_end(self.h))
-        self._gail = None
+        self._session = None

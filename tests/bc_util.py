@@ -329,7 +329,7 @@ def check_refusals_move_nothing(eng, case, other_handles=()):
         begin(eng, case, bc_batch=case["B"] + 1)
     obs, act, n = eng.bc_upload(case["bc_obs"], case["bc_act"])
     with pytest.raises(GrlError, match="needs an open session"):
-        eng._bc = {"batch": case["bc_batch"], "keep": None}
+        eng._session = {"batch": case["bc_batch"], "keep": None}
         eng.bc_train((obs, act, n), case["bc_idx"])
     table = begin(eng, case)
     bad = case["bc_idx"].copy()

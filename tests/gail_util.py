@@ -224,8 +224,8 @@ def begin(eng, c, **over):
 def arenas(eng):
     """raw words of the handle's state, replay and work arenas and of the session buffer"""
     out = [np.array(eng.be.to_host(t), copy=True).view(np.uint32) for t in (eng.state, eng.replay, eng.work)]
-    if getattr(eng, "_gail", None):
-        out.append(np.array(eng.be.to_host(eng._gail["buf"]), copy=True).view(np.uint32))
+    if getattr(eng, "_session", None):
+        out.append(np.array(eng.be.to_host(eng._session["buf"]), copy=True).view(np.uint32))
     return out
 
 
