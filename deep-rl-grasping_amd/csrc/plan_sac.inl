@@ -1202,7 +1202,8 @@ struct SacPlanner {
     h.dbg["v"] = {hVF.out[0], B}; h.dbg["v_tgt"] = {hTGT.out[0], B};
     h.dbg["qf1_pi"] = {hQF1PI.out[0], B}; h.dbg["qf2_pi"] = {hQF2PI.out[0], B};
     h.dbg["rew"] = {h.rew, B}; h.dbg["done"] = {h.done, B}; h.dbg["act"] = {h.act, (int64_t)B * A};
-    h.dbg["dmu"] = {dmu, (int64_t)B * A}; h.dbg["dls"] = {dls, (int64_t)B * A}; h.dbg["da_pi"] = {da_pi, (int64_t)B * A};
+    h.dbg["dmu"] = {dmu, (int64_t)B * ld_dm}; h.dbg["dls"] = {dls, (int64_t)B * ld_dm};   // rows of stride ld_dm (Ap on the fused routes)
+    h.dbg["da_pi"] = {da_pi, (int64_t)B * A};
     h.dbg["grads"] = {h.grads, h.n_train};
     h.dbg["adam_m"] = {h.adam_m, h.n_train};
     h.dbg["adam_v"] = {h.adam_v, h.n_train};

@@ -177,25 +177,26 @@ def rms_update(mean, var, count, x):
     return new_mean, new_var, tot_count
 
 
-def prepare_batch(spec, raw, stats, norm_obs=True, norm_reward=True):
+def prepare_batch(spec, raw, stats, norm_obs=True, norm_reward=True, dtype=torch.float32):
     """raw: dict obs[B,H,W,Cobs]|[B,D], act, rew, next_obs, done.  stats: obs mean/var, ret_var
     (or None for ``normalize: False`` configs); norm_obs / norm_reward are the VecNormalize flags of the same
-    names (both on in the reference, sb_helper.py:117-119).  Returns float32 torch tensors as fed to TF."""
+    names (both on in the reference, sb_helper.py:117-119).  Returns float32 torch tensors as fed to TF; another
+    `dtype` (the float64 run of SacOracle) widens those float32 values before the graph's own /255."""
     obs, nxt, rew = raw["obs"], raw["next_obs"], raw["rew"]
     if stats is not None and norm_obs:
         obs = normalize_obs(obs, stats["mean"], stats["var"], spec.clip_obs, spec.norm_eps)
         nxt = normalize_obs(nxt, stats["mean"], stats["var"], spec.clip_obs, spec.norm_eps)
     if stats is not None and norm_reward:
         rew = normalize_reward(rew, stats["ret_var"], spec.clip_reward, spec.norm_eps)
-    obs = torch.from_numpy(np.asarray(obs, np.float32))
-    nxt = torch.from_numpy(np.asarray(nxt, np.float32))
+    obs = torch.from_numpy(np.asarray(obs, np.float32)).to(dtype)
+    nxt = torch.from_numpy(np.asarray(nxt, np.float32)).to(dtype)
     if spec.extractor != "mlp":          # observation_input(scale=True): Box(0,255) -> /255
         obs = obs / 255.0
         nxt = nxt / 255.0
     return {"obs": obs, "next_obs": nxt,
-            "act": torch.from_numpy(np.asarray(raw["act"], np.float32)),
-            "rew": torch.from_numpy(np.asarray(rew, np.float32)).reshape(-1),
-            "done": torch.from_numpy(np.asarray(raw["done"], np.float32)).reshape(-1)}
+            "act": torch.from_numpy(np.asarray(raw["act"], np.float32)).to(dtype),
+            "rew": torch.from_numpy(np.asarray(rew, np.float32)).reshape(-1).to(dtype),
+            "done": torch.from_numpy(np.asarray(raw["done"], np.float32)).reshape(-1).to(dtype)}
 
 
 # ----------------------------------------------------------------------------- A.2
@@ -329,10 +330,14 @@ def polyak_pairs(spec):
 
 class SacOracle:
     """Holds parameters + the three Adam states; ``step`` = SB ``SAC._train_step`` followed by
-    ``target_update_op`` (A.4), on an already prepared batch."""
+    ``target_update_op`` (A.4), on an already prepared batch.
 
-    def __init__(self, spec, params=None, seed=0):
-        self.spec = spec
+    `dtype`: the type the graph runs in.  torch.float32 (the default) is what TF ran; torch.float64 runs the SAME graph --
+    `actor_fwd`, `critic_fwd`, `forward` -- on the float32 parameters and inputs widened, as the referee where float32
+    autograd is itself ill-conditioned (tests/sac_edge_util.py).  The parameters and the Adam arithmetic stay float32."""
+
+    def __init__(self, spec, params=None, seed=0, dtype=torch.float32):
+        self.spec, self.dtype = spec, dtype
         self.P = OrderedDict((k, np.array(v, np.float32)) for k, v in
                              (params if params is not None else init_params(spec, seed)).items())
         g_pi, g_vf, g_ent = trainable_groups(spec)
@@ -342,7 +347,7 @@ class SacOracle:
     def tensors(self, requires_grad=False):
         T = OrderedDict()
         for k, v in self.P.items():
-            t = torch.from_numpy(np.array(v, np.float32))
+            t = torch.from_numpy(np.array(v, np.float32)).to(self.dtype)
             if requires_grad and not k.startswith("target/"):
                 t.requires_grad_(True)
             T[k] = t
@@ -351,7 +356,8 @@ class SacOracle:
     def forward(self, batch, eps, T=None):
         spec = self.spec
         T = T if T is not None else self.tensors()
-        eps = torch.as_tensor(np.asarray(eps, np.float32))
+        eps = torch.as_tensor(np.asarray(eps, np.float32)).to(self.dtype)
+        batch = {k: v.to(self.dtype) for k, v in batch.items()}
         a = actor_fwd(spec, T, batch["obs"], eps)
         keep = {}
         c = critic_fwd(spec, T, "model/values_fn", batch["obs"], batch["act"], a["pi"], keep)
@@ -405,10 +411,10 @@ class SacOracle:
     def act(self, obs, deterministic=True, eps=None):
         """SB ``policy_tf.step`` (A.3 / call site utils.py:71): obs already normalised."""
         T = self.tensors()
-        obs = torch.as_tensor(np.asarray(obs, np.float32))
+        obs = torch.as_tensor(np.asarray(obs, np.float32)).to(self.dtype)
         if self.spec.extractor != "mlp":
             obs = obs / 255.0
         if eps is None:
             eps = np.zeros((obs.shape[0], self.spec.act_dim), np.float32)
-        a = actor_fwd(self.spec, T, obs, torch.as_tensor(np.asarray(eps, np.float32)))
+        a = actor_fwd(self.spec, T, obs, torch.as_tensor(np.asarray(eps, np.float32)).to(self.dtype))
         return (a["det"] if deterministic else a["pi"]).numpy()
