@@ -189,17 +189,18 @@ static int create_handle(const grl_config* cfg, const grl_ppo_config* ppo, const
                          const grl_trpo_config* trpo = nullptr) {
   if (!bufs || !out || !bufs->state || !bufs->grads || !bufs->work || !bufs->replay)
     return fail(GRL_ERR_INVALID, "null buffers");
-  grl_ctx* h = new grl_ctx();
+  std::unique_ptr<grl_ctx> owner(new grl_ctx());      // released into *out on success: every refusal below destroys it
+  grl_ctx* h = owner.get();
   h->cfg = *cfg;
   if (ppo) h->pcfg = *ppo;
   if (trpo) h->tcfg = *trpo;
   h->st.base = (char*)bufs->state; h->gr.base = (char*)bufs->grads;
   h->wk.base = (char*)bufs->work; h->rp.base = (char*)bufs->replay;
-  if (int e = h->plan()) { delete h; return e; }
+  if (int e = h->plan()) return e;
   h->use_graph = !h->sw.get(Sw::GRL_NO_GRAPH);
   for (auto& u : h->uploads) {
     hipError_t e = hipMemcpy(u.dst, u.bytes.data(), u.bytes.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { delete h; return fail(GRL_ERR_HIP, std::string("table upload: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(GRL_ERR_HIP, std::string("table upload: ") + hipGetErrorString(e));
   }
   h->uploads.clear();
   for (auto& z : h->zero_once) hipMemset(z.first, 0, z.second);
@@ -212,7 +213,7 @@ static int create_handle(const grl_config* cfg, const grl_ppo_config* ppo, const
   s0.beta1_power = 0.9f; s0.beta2_power = 0.999f;
   s0.lr = cfg->lr;
   hipError_t e = hipMemcpy(h->sc, &s0, sizeof(s0), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { delete h; return fail(GRL_ERR_HIP, std::string("scalar init: ") + hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(GRL_ERR_HIP, std::string("scalar init: ") + hipGetErrorString(e));
   if (h->n_mean) {   // RunningMeanStd(): mean 0, var 1, count 1e-4
     std::vector<double> ones((size_t)h->n_elems, 1.0);
     const double c2[2] = {1e-4, 1e-4};
@@ -226,17 +227,17 @@ static int create_handle(const grl_config* cfg, const grl_ppo_config* ppo, const
   }
   if (h->per_on) {
     e = per_start(h);
-    if (e != hipSuccess) { delete h; return fail(GRL_ERR_HIP, std::string("per init: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(GRL_ERR_HIP, std::string("per init: ") + hipGetErrorString(e));
   }
   if (h->ppo_dev) {
     e = hipMemset(h->ppo_dev, 0, sizeof(PpoDev));
-    if (e != hipSuccess) { delete h; return fail(GRL_ERR_HIP, std::string("ppo init: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(GRL_ERR_HIP, std::string("ppo init: ") + hipGetErrorString(e));
   }
   if (h->trpo_dev) {
     e = hipMemset(h->trpo_dev, 0, sizeof(TrpoDev));
-    if (e != hipSuccess) { delete h; return fail(GRL_ERR_HIP, std::string("trpo init: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(GRL_ERR_HIP, std::string("trpo init: ") + hipGetErrorString(e));
   }
-  *out = h;
+  *out = owner.release();
   return GRL_OK;
 }
 
@@ -311,21 +312,13 @@ int grl_set_obs_stats(grl_handle h, const double* mean, const double* var, doubl
   const int nd = h->cnn ? h->F - 512 : 0;
   // The five statistic blocks sit one after the other in the state arena (alignment gaps in between are unused):
   // they are written into a page-locked mirror of that span and leave as ONE asynchronous copy in stream order.
-  // Two mirrors alternate, each guarded by an event, so the host never waits for the GPU here (the learn loop calls
-  // this before every update: a stream synchronisation plus five blocking copies serialised host and device).
+  // Two mirrors alternate (StagingRing), each guarded by an event, so the host never waits for the GPU here (the learn loop
+  // calls this before every update: a stream synchronisation plus five blocking copies serialised host and device).  The
+  // mirrors are zeroed when they are allocated and the gaps are never written: the WHOLE span lands in the state arena.
   char* base = (char*)h->s_mean;
   const size_t span = (size_t)((char*)h->s_ret + 8 - base);
-  if (!h->pin_stats[0]) {
-    for (int k = 0; k < 2; ++k) {
-      HIPCHK(hipHostMalloc((void**)&h->pin_stats[k], span, 0));
-      memset(h->pin_stats[k], 0, span);
-      HIPCHK(hipEventCreateWithFlags(&h->pin_stats_ev[k], hipEventDisableTiming));
-    }
-  }
-  const int k = h->pin_stats_next;
-  h->pin_stats_next ^= 1;
-  if (h->pin_stats_used[k]) HIPCHK(hipEventSynchronize(h->pin_stats_ev[k]));   // the copy issued two calls ago
-  char* pm = h->pin_stats[k];
+  char* pm = nullptr;
+  HIPCHK(h->stats_ring.acquire(span, &pm));      // (waits for the copy issued two calls ago)
   double* m = (double*)pm;
   double* s = (double*)(pm + ((char*)h->s_std - base));
   double* dm = (double*)(pm + ((char*)h->s_dmean - base));
@@ -347,8 +340,7 @@ int grl_set_obs_stats(grl_handle h, const double* mean, const double* var, doubl
   }
   *rs = std::sqrt(ret_var + eps);
   HIPCHK(hipMemcpyAsync(base, pm, span, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipEventRecord(h->pin_stats_ev[k], h->stream));
-  h->pin_stats_used[k] = true;
+  HIPCHK(h->stats_ring.release(h->stream));
   return GRL_OK;
 }
 
@@ -368,9 +360,9 @@ static int copy_from_caller(grl_handle h, void* dst, const void* src, size_t byt
     else (void)hipGetLastError();      // unknown to the runtime: pageable
   }
   if (wait) {
-    if (!h->copy_ev) HIPCHK(hipEventCreateWithFlags(&h->copy_ev, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(h->copy_ev, h->stream));
-    HIPCHK(hipEventSynchronize(h->copy_ev));
+    HIPCHK_AS("hipEventCreateWithFlags(&h->copy_ev, hipEventDisableTiming)", h->copy_ev.create());
+    HIPCHK(hipEventRecord(h->copy_ev.raw(), h->stream));
+    HIPCHK(hipEventSynchronize(h->copy_ev.raw()));
   }
   return GRL_OK;
 }
@@ -428,7 +420,7 @@ static int norm_update_from(grl_handle h, const float* dev_obs, int n) {
   a.s_mean = h->s_mean; a.s_std = h->s_std; a.s_dmean = h->s_dmean; a.s_dstd = h->s_dstd;
   const dim3 grid((unsigned)((h->n_elems + 255) / 256));
   if (h->dp_on) {   // data parallel: the batch moments of all ranks, merged in rank order by every replica (dp_kernels.h)
-    if (h->dp_err_host && *h->dp_err_host) return fail(GRL_ERR_STATE, "an exchange timed out waiting for a peer (the replicas are no longer in step)");
+    if (h->dp_err_host.get() && *h->dp_err_host.get()) return fail(GRL_ERR_STATE, "an exchange timed out waiting for a peer (the replicas are no longer in step)");
     DpNormArgs na = h->dp_norm;
     na.nu = a;
     hipLaunchKernelGGL(dp_norm_moments_kernel, grid, dim3(256), 0, h->stream, na);
@@ -499,19 +491,10 @@ int grl_replay_add_device(grl_handle h, const float* obs, const float* act, cons
 
 // host buffer -> pinned staging -> device (and back): hipMemcpyAsync from pageable memory is a synchronous
 // staged copy; through page-locked buffers the per-call overhead is a host memcpy plus a true async DMA
+// (Pinned::reserve only grows and does not wait: the previous call has finished with both blocks)
 static int pin_reserve(grl_handle h, size_t in_floats, size_t out_floats) {
-  if (in_floats > h->pin_in_n) {
-    if (h->pin_in) hipHostFree(h->pin_in);
-    h->pin_in = nullptr; h->pin_in_n = 0;
-    HIPCHK(hipHostMalloc((void**)&h->pin_in, in_floats * 4, 0));
-    h->pin_in_n = in_floats;
-  }
-  if (out_floats > h->pin_out_n) {
-    if (h->pin_out) hipHostFree(h->pin_out);
-    h->pin_out = nullptr; h->pin_out_n = 0;
-    HIPCHK(hipHostMalloc((void**)&h->pin_out, out_floats * 4, 0));
-    h->pin_out_n = out_floats;
-  }
+  HIPCHK_AS("hipHostMalloc((void**)&h->pin_in, in_floats * 4, 0)", h->pin_in.reserve(in_floats));
+  HIPCHK_AS("hipHostMalloc((void**)&h->pin_out, out_floats * 4, 0)", h->pin_out.reserve(out_floats));
   return GRL_OK;
 }
 
@@ -540,31 +523,8 @@ int grl_replay_add(grl_handle h, const float* obs, const float* act, const float
 // One env step's observations serve three consumers -- the running statistics, the next action and two replay rows
 // (next_obs of this step, obs of the next).  grl_observe uploads them ONCE; grl_act (GRL_ACT_OBSERVED) and
 // grl_replay_add_observed read the device copy.  The small per-step arrays of the latter (actions, rewards, done flags,
-// terminal rows) pass through page-locked staging that the ingest launch reads directly: two buffers used in turn, each
-// guarded by an event.
-static int ob_stage_acquire(grl_handle h, float** pin) {
-  const size_t need = (size_t)h->stg_n * (size_t)(h->ob_elems + h->A + 4);
-  if (h->pin_ob_n < need) {
-    for (int k = 0; k < 2; ++k) {
-      if (h->pin_ob[k]) { HIPCHK(hipStreamSynchronize(h->stream)); hipHostFree(h->pin_ob[k]); h->pin_ob[k] = nullptr; }
-      HIPCHK(hipHostMalloc((void**)&h->pin_ob[k], need * 4, 0));
-      if (!h->pin_ob_ev[k]) HIPCHK(hipEventCreateWithFlags(&h->pin_ob_ev[k], hipEventDisableTiming));
-      h->pin_ob_used[k] = false;
-    }
-    h->pin_ob_n = need;
-  }
-  const int k = h->pin_ob_next;
-  if (h->pin_ob_used[k]) HIPCHK(hipEventSynchronize(h->pin_ob_ev[k]));   // the copies that read it two calls ago
-  *pin = h->pin_ob[k];
-  return GRL_OK;
-}
-static int ob_stage_release(grl_handle h) {
-  const int k = h->pin_ob_next;
-  HIPCHK(hipEventRecord(h->pin_ob_ev[k], h->stream));
-  h->pin_ob_used[k] = true;
-  h->pin_ob_next = k ^ 1;
-  return GRL_OK;
-}
+// terminal rows) pass through page-locked staging that the ingest launch reads directly: grl_ctx::ob_ring, two buffers used in
+// turn, each guarded by an event (StagingRing, host_res.h).
 
 // PPO / TRPO handles with normalize = 2: one upload of the raw rows and ONE launch per env step (ppo_observe_kernel) -- the
 // statistics move (with the flag) and the normalised rows grl_ppo_step / grl_ppo_finish read with obs == NULL are written
@@ -615,18 +575,17 @@ int grl_replay_add_observed(grl_handle h, const float* act, const float* rew, co
   if (!h->ob_latest) return fail(GRL_ERR_STATE, "this handle keeps no observed observations (SAC / DQN / BDQ handles do)");
   if (h->ob_n != n || h->ob_n_prev != n)
     return fail(GRL_ERR_STATE, "grl_replay_add_observed needs two consecutive grl_observe calls of n observations each");
+  for (int j = 0; j < n_term; ++j)     // (checked before the staging slot is taken: a refusal holds nothing and moves nothing)
+    if (term_rows[j] < 0 || term_rows[j] >= n) return fail(GRL_ERR_INVALID, "terminal row out of range");
   float* pin = nullptr;
-  if (int e = ob_stage_acquire(h, &pin)) return e;
+  HIPCHK(h->ob_ring.acquire((size_t)h->stg_n * (size_t)(h->ob_elems + h->A + 4), &pin));   // (waits for the copies that read it two calls ago)
   const int A = h->A;
   memcpy(pin, act, (size_t)n * A * 4);
   memcpy(pin + (size_t)n * A, rew, (size_t)n * 4);
   memcpy(pin + (size_t)n * (A + 1), done, (size_t)n * 4);
   int32_t* rowmap = (int32_t*)(pin + (size_t)n * (A + 2));
   for (int k = 0; k < n; ++k) rowmap[k] = -1;
-  for (int j = 0; j < n_term; ++j) {
-    if (term_rows[j] < 0 || term_rows[j] >= n) { (void)ob_stage_release(h); return fail(GRL_ERR_INVALID, "terminal row out of range"); }
-    rowmap[term_rows[j]] = j;
-  }
+  for (int j = 0; j < n_term; ++j) rowmap[term_rows[j]] = j;
   // (the ingest launch reads actions / rewards / done flags / row map straight from the page-locked buffer: 0.5 KB)
   const size_t small = (size_t)n * (A + 3);
   if (n_term > 0) {
@@ -635,7 +594,7 @@ int grl_replay_add_observed(grl_handle h, const float* act, const float* rew, co
   }
   const int e = replay_add_dev(h, h->ob_prev, pin, pin + (size_t)n * A, h->ob_latest, pin + (size_t)n * (A + 1), n,
                                n_term > 0 ? (const int*)(pin + (size_t)n * (A + 2)) : nullptr, h->ob_term);
-  if (int e2 = ob_stage_release(h)) return e2;    // (the event follows the launch that reads the buffer)
+  HIPCHK(h->ob_ring.release(h->stream));          // (the event follows the launch that reads the buffer)
   return e;
 }
 
@@ -761,7 +720,7 @@ int grl_train_step_per(grl_handle h, int n_steps, double beta, const double* u) 
     // connected handle (grl_allreduce_connect): every rank draws from ITS priority tree (importance weights against its own
     // total and minimum), the gradient sums are exchanged inside the graph, the plan's clip + Adam apply the mean, every rank
     // writes the priorities of its own rows back.  All ranks must call alike, as with grl_train_step_allreduce.
-    if (*h->dp_err_host) return fail(GRL_ERR_STATE, "an exchange timed out waiting for a peer (the replicas are no longer in step)");
+    if (*h->dp_err_host.get()) return fail(GRL_ERR_STATE, "an exchange timed out waiting for a peer (the replicas are no longer in step)");
     h->grad_scale = 1.f / (float)h->dp.world;
     if (!u) {
       if (int e = h->run_repeated("dp_per_rng", {&h->ops_per_rng_g, &h->dp_body_per, &h->ops_dp, &h->ops_per_update}, n_steps)) return e;
@@ -841,13 +800,13 @@ static int act_wait(grl_handle h, unsigned wgs) {
     const unsigned want = h->act_done_seen;
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned spin = 0;; ++spin) {
-      if ((int)(__atomic_load_n(h->act_done_host, __ATOMIC_ACQUIRE) - want) >= 0) { seen = true; break; }
+      if ((int)(__atomic_load_n(h->act_done_host.get(), __ATOMIC_ACQUIRE) - want) >= 0) { seen = true; break; }
       if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
     }
   }
   if (!seen) {
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->act_done_host) h->act_done_seen = __atomic_load_n(h->act_done_host, __ATOMIC_ACQUIRE);
+    if (h->act_done_host.get()) h->act_done_seen = __atomic_load_n(h->act_done_host.get(), __ATOMIC_ACQUIRE);
   }
   HIPCHK(hipGetLastError());
   return GRL_OK;
@@ -857,15 +816,15 @@ static int act_wait(grl_handle h, unsigned wgs) {
 // in coherent host memory the launch reads and writes: the previous call has waited for its launch, so they are free
 // raw: VecNormalize applied on the device; observed: the rows grl_observe uploaded (nothing but the overrides moves)
 static int act_greedy(grl_handle h, const float* obs, int n, const float* explore, float* out, bool raw, bool observed) {
-  if (!h->q_io_host) return fail(GRL_ERR_STATE, "this handle has no act path");
+  if (!h->q_io_host.get()) return fail(GRL_ERR_STATE, "this handle has no act path");
   const int D = h->qD, od = h->cfg.obs_dim;
-  float* io_obs = h->q_io_host; float* io_explore = io_obs + (size_t)h->NA * od; float* io_bins = io_explore + (size_t)h->NA * D;
+  float* io_obs = h->q_io_host.get(); float* io_explore = io_obs + (size_t)h->NA * od; float* io_bins = io_explore + (size_t)h->NA * D;
   if (observed) {}
   else if (h->q_act_fused) memcpy(io_obs, obs, (size_t)n * od * 4);
   else {
     if (int e = pin_reserve(h, (size_t)n * od, 0)) return e;
-    memcpy(h->pin_in, obs, (size_t)n * od * 4);
-    HIPCHK(hipMemcpyAsync(h->stg_obs, h->pin_in, (size_t)n * od * 4, hipMemcpyHostToDevice, h->stream));
+    memcpy(h->pin_in.get(), obs, (size_t)n * od * 4);
+    HIPCHK(hipMemcpyAsync(h->stg_obs, h->pin_in.get(), (size_t)n * od * 4, hipMemcpyHostToDevice, h->stream));
   }
   if (explore) memcpy(io_explore, explore, (size_t)n * D * 4);
   else for (int i = 0; i < n * D; ++i) io_explore[i] = -1.f;
@@ -888,22 +847,22 @@ static int ppo_send(grl_handle h, const float* obs, const float* done, const flo
   // (the previous call synchronised the stream behind its copy: the staging buffer is free)
   // obs == NULL (grl_ppo_step / grl_ppo_finish on the rows grl_observe normalised): done | eps alone travel
   const size_t lo = obs ? 0 : (size_t)NA * ldo;
-  memset(h->pin_in + lo, 0, (n_in - lo) * 4);
-  for (int r = 0; obs && r < n; ++r) memcpy(h->pin_in + (size_t)r * ldo, obs + (size_t)r * od, (size_t)od * 4);
-  if (done) memcpy(h->pin_in + (size_t)NA * ldo, done, (size_t)n * 4);
-  if (eps) memcpy(h->pin_in + (size_t)NA * (ldo + 1), eps, (size_t)n * A * 4);
-  HIPCHK(hipMemcpyAsync(h->ppo_in + lo, h->pin_in + lo, (n_in - lo) * 4, hipMemcpyHostToDevice, h->stream));
+  memset(h->pin_in.get() + lo, 0, (n_in - lo) * 4);
+  for (int r = 0; obs && r < n; ++r) memcpy(h->pin_in.get() + (size_t)r * ldo, obs + (size_t)r * od, (size_t)od * 4);
+  if (done) memcpy(h->pin_in.get() + (size_t)NA * ldo, done, (size_t)n * 4);
+  if (eps) memcpy(h->pin_in.get() + (size_t)NA * (ldo + 1), eps, (size_t)n * A * 4);
+  HIPCHK(hipMemcpyAsync(h->ppo_in + lo, h->pin_in.get() + lo, (n_in - lo) * 4, hipMemcpyHostToDevice, h->stream));
   return GRL_OK;
 }
 // ... and what it returns: action [NA, A] | value [NA] | neglogp [NA]; synchronises
 static int ppo_receive(grl_handle h, int n, float* out_act, float* out_val, float* out_nlp) {
   const int NA = h->NA, A = h->A;
-  HIPCHK(hipMemcpyAsync(h->pin_out, h->ppo_out, (size_t)NA * (A + 2) * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(h->pin_out.get(), h->ppo_out, (size_t)NA * (A + 2) * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
-  if (out_act) memcpy(out_act, h->pin_out, (size_t)n * A * 4);
-  if (out_val) memcpy(out_val, h->pin_out + (size_t)NA * A, (size_t)n * 4);
-  if (out_nlp) memcpy(out_nlp, h->pin_out + (size_t)NA * (A + 1), (size_t)n * 4);
+  if (out_act) memcpy(out_act, h->pin_out.get(), (size_t)n * A * 4);
+  if (out_val) memcpy(out_val, h->pin_out.get() + (size_t)NA * A, (size_t)n * 4);
+  if (out_nlp) memcpy(out_nlp, h->pin_out.get() + (size_t)NA * (A + 1), (size_t)n * 4);
   return GRL_OK;
 }
 #define PPO_ONLY(h, what)                                                                                        \
@@ -1110,9 +1069,9 @@ int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps, 
   const size_t n_in = observed ? 0 : (size_t)n * oe, n_eps = (!q && !deterministic) ? (size_t)n * h->A : 0;
   const size_t n_out = q ? (size_t)n * h->qD * h->qN : (size_t)n * h->A;
   if (int e = pin_reserve(h, n_in, q ? n_out : 0)) return e;
-  if (n_in) memcpy(h->pin_in, obs, n_in * 4);
+  if (n_in) memcpy(h->pin_in.get(), obs, n_in * 4);
   if (n_eps) memcpy(h->a_eps, eps, n_eps * 4);      // (SAC: a_eps / a_out are host memory the launches read and write; the
-  if (n_in) HIPCHK(hipMemcpyAsync(h->stg_obs, h->pin_in, n_in * 4, hipMemcpyHostToDevice, h->stream));   // previous call synchronised)
+  if (n_in) HIPCHK(hipMemcpyAsync(h->stg_obs, h->pin_in.get(), n_in * 4, hipMemcpyHostToDevice, h->stream));   // previous call synchronised)
   if (q) {
     if (int e = h->run_seq("act", {&h->ops_act})) return e;
   } else {
@@ -1123,11 +1082,11 @@ int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps, 
       return e;
   }
   const bool poll = h->act_done_wgs && !h->prof;
-  if (q && !poll) HIPCHK(hipMemcpyAsync(h->pin_out, h->q_aout, n_out * 4, hipMemcpyDeviceToHost, h->stream));
+  if (q && !poll) HIPCHK(hipMemcpyAsync(h->pin_out.get(), h->q_aout, n_out * 4, hipMemcpyDeviceToHost, h->stream));
   // the last launch counts its workgroups into coherent host memory once their actions are out (act_mfma.h) -- on EVERY call,
   // polled or not (a call under grl_profile_enable synchronises the stream instead): the expectation advances with it
   if (int e = act_wait(h, h->act_done_wgs)) return e;
-  memcpy(out, q ? (poll ? h->q_act_host : h->pin_out) : h->a_out, n_out * 4);
+  memcpy(out, q ? (poll ? h->q_act_host.get() : h->pin_out.get()) : h->a_out, n_out * 4);
   return GRL_OK;
 }
 
@@ -1153,28 +1112,20 @@ int grl_allreduce_init(grl_handle h, int rank, int world, void* handle_out) {
   // the data as well unless GRL_TUNE dp_coarse=1: the exchange kernels store it write-through and load it at system scope,
   // so its caching policy costs nothing measurable on one GPU and fine-grained is the conservative choice between GPUs
   e = Switches(SwRead::DP_INIT).get(Sw::dp_coarse) ? hipMalloc(&h->dp_buf, dbytes) : hipExtMallocWithFlags(&h->dp_buf, dbytes, hipDeviceMallocFinegrained);
-  if (e != hipSuccess) {
-    (void)hipFree(h->dp_flags); h->dp_flags = nullptr; h->dp_buf = nullptr;
-    return fail(GRL_ERR_HIP, std::string("exchange buffer: ") + hipGetErrorString(e));
-  }
+  if (e != hipSuccess) { h->dp_buf = nullptr; h->dp_release(); return fail(GRL_ERR_HIP, std::string("exchange buffer: ") + hipGetErrorString(e)); }
   HIPCHK(hipMemset(h->dp_flags, 0, fbytes));
   HIPCHK(hipMemset(h->dp_buf, 0, dbytes));
   for (int k = 0; k < DP_CHANNELS; ++k) {     // the first exchange (epoch 1) uses source buffer 1
     const uint32_t one = 1u;
     HIPCHK(hipMemcpy((char*)h->dp_flags + k * dp_ctl_stride() + offsetof(DpCtl, next_buf), &one, 4, hipMemcpyHostToDevice));
   }
-  if (!h->dp_err_host) {     // page-locked mailbox: a kernel that gives up waiting tells the host without a device read
-    HIPCHK(hipHostMalloc((void**)&h->dp_err_host, 64, 0));
-    memset(h->dp_err_host, 0, 64);      // word 0: error, word 1: wait bound in ms (0 = the captured default; grl_allreduce_set_timeout)
-  }
+  // page-locked mailbox (allocated once, zeroed): a kernel that gives up waiting tells the host without a device read
+  HIPCHK_AS("hipHostMalloc((void**)&h->dp_err_host, 64, 0)", h->dp_err_host.reserve(16));   // word 0: error, word 1: wait bound in ms (0 = the captured default; grl_allreduce_set_timeout)
   HIPCHK(hipDeviceSynchronize());
   hipIpcMemHandle_t mh[2];
   e = hipIpcGetMemHandle(&mh[0], h->dp_flags);
   if (e == hipSuccess) e = hipIpcGetMemHandle(&mh[1], h->dp_buf);
-  if (e != hipSuccess) {
-    (void)hipFree(h->dp_buf); (void)hipFree(h->dp_flags); h->dp_buf = h->dp_flags = nullptr;
-    return fail(GRL_ERR_HIP, std::string("hipIpcGetMemHandle: ") + hipGetErrorString(e));
-  }
+  if (e != hipSuccess) { h->dp_release(); return fail(GRL_ERR_HIP, std::string("hipIpcGetMemHandle: ") + hipGetErrorString(e)); }
   memcpy(handle_out, mh, GRL_ALLREDUCE_HANDLE_BYTES);
   memset(&h->dp, 0, sizeof(h->dp));
   h->dp.rank = rank; h->dp.world = world;
@@ -1194,7 +1145,7 @@ static DpArgs dp_channel(grl_ctx* h, int channel, const std::vector<std::pair<in
   d.n = v;
   d.chunk = rup((v + d.world - 1) / d.world, 4);      // (the last ranks' chunks may be short or empty)
   d.timeout_ticks = (uint64_t)std::max(1, Switches(SwRead::DP_CONNECT).get(Sw::dp_timeout_ms)) * 100000ull;     // 100 MHz wall clock
-  d.host_err = h->dp_err_host;
+  d.host_err = h->dp_err_host.get();
   for (int p = 0; p < d.world; ++p) {
     d.ctl[p] = (DpCtl*)(flags[p] + (size_t)channel * dp_ctl_stride());
     d.src[p] = (float*)data[p];
@@ -1426,14 +1377,10 @@ int grl_allreduce_disconnect(grl_handle h) {
   h->dp_mode = 0;
   for (auto* v : {&h->ops_dp, &h->ops_dp1, &h->dp_body, &h->dp_body_per, &h->ops_dp_overlap}) v->clear();
   for (int one = 0; one < 2; ++one) { h->pf_dp[one].clear(); h->ride_dp[one].clear(); }
-  for (int p = 0; p < 2 * DP_MAX_WORLD; ++p)
-    if (h->dp_peer[p]) { (void)hipIpcCloseMemHandle(h->dp_peer[p]); h->dp_peer[p] = nullptr; }
-  if (h->dp_buf) (void)hipFree(h->dp_buf);
-  if (h->dp_flags) (void)hipFree(h->dp_flags);
-  h->dp_buf = h->dp_flags = nullptr;
+  h->dp_release();
   memset(&h->dp, 0, sizeof(h->dp));
   memset(&h->dp_norm, 0, sizeof(h->dp_norm));
-  if (h->dp_err_host) *h->dp_err_host = 0u;
+  if (h->dp_err_host.get()) *h->dp_err_host.get() = 0u;
   return GRL_OK;
 }
 
@@ -1459,8 +1406,8 @@ int grl_allreduce_set_mode(grl_handle h, int mode) {
 int grl_allreduce_set_timeout(grl_handle h, int ms) {
   NOT_ON_PPO(h, "grl_allreduce_set_timeout");
   if (!h || ms < 0) return fail(GRL_ERR_INVALID, "bad argument");
-  if (!h->dp_err_host) return fail(GRL_ERR_STATE, "call grl_allreduce_init first");
-  __atomic_store_n(h->dp_err_host + 1, (uint32_t)ms, __ATOMIC_RELEASE);     // read by the waiting kernels (dp_wait_all)
+  if (!h->dp_err_host.get()) return fail(GRL_ERR_STATE, "call grl_allreduce_init first");
+  __atomic_store_n(h->dp_err_host.get() + 1, (uint32_t)ms, __ATOMIC_RELEASE);     // read by the waiting kernels (dp_wait_all)
   return GRL_OK;
 }
 
@@ -1470,7 +1417,7 @@ int grl_train_step_allreduce(grl_handle h, int n_steps, const int64_t* idx, cons
   if (!h->dp_on) return fail(GRL_ERR_STATE, "call grl_allreduce_init / grl_allreduce_connect first");
   if ((idx == nullptr) != (eps == nullptr)) return fail(GRL_ERR_INVALID, "idx and eps must both be given or both be NULL");
   if (h->rp_size < 1) return fail(GRL_ERR_STATE, "replay buffer is empty");
-  if (*h->dp_err_host) return fail(GRL_ERR_STATE, "an exchange timed out waiting for a peer (the replicas are no longer in step)");
+  if (*h->dp_err_host.get()) return fail(GRL_ERR_STATE, "an exchange timed out waiting for a peer (the replicas are no longer in step)");
   // one-shot (every rank adds all contributions itself: one kernel and one flag round less, (W - 1) n bytes per rank
   // instead of 2 (W - 1) / W n) pays for W <= 2
   const bool qh = h->cfg.algo != GRL_ALGO_SAC;
@@ -1513,9 +1460,9 @@ int grl_allreduce_status(grl_handle h, int64_t* exchanges, int* error) {
     for (int p = 0; p < h->dp.world; ++p) plan_note(" %u", c[k].ready[p]);
     plan_note(" done");
     for (int p = 0; p < h->dp.world; ++p) plan_note(" %u", c[k].done[p]);
-    plan_note(" mailbox %u\n", h->dp_err_host ? *h->dp_err_host : 0u);
+    plan_note(" mailbox %u\n", h->dp_err_host.get() ? *h->dp_err_host.get() : 0u);
   }
-  int err = h->dp_err_host ? (int)*h->dp_err_host : 0;
+  int err = h->dp_err_host.get() ? (int)*h->dp_err_host.get() : 0;
   for (int k = 0; k < DP_CHANNELS; ++k) err |= (int)c[k].error;
   if (error) *error = err;
   if (err) return fail(GRL_ERR_STATE, "an exchange timed out waiting for a peer (the replicas are no longer in step)");
@@ -1551,13 +1498,13 @@ int grl_encode(grl_handle h, const float* depth, int n, float* out) {
   if (n > h->NA) return fail(GRL_ERR_INVALID, "n exceeds act_batch");
   const size_t ed = (size_t)h->enc_dim;      // 100 for the shipped encoder; an auto-encoder handle's own encoding_dim
   if (int e = pin_reserve(h, (size_t)n * 4096, (size_t)n * ed)) return e;
-  memcpy(h->pin_in, depth, (size_t)n * 4096 * 4);
-  HIPCHK(hipMemcpyAsync(h->ex_in, h->pin_in, (size_t)n * 4096 * 4, hipMemcpyHostToDevice, h->stream));
+  memcpy(h->pin_in.get(), depth, (size_t)n * 4096 * 4);
+  HIPCHK(hipMemcpyAsync(h->ex_in, h->pin_in.get(), (size_t)n * 4096 * 4, hipMemcpyHostToDevice, h->stream));
   if (int e = h->run_seq("encode", {&h->ops_enc})) return e;
-  HIPCHK(hipMemcpyAsync(h->pin_out, h->eout, (size_t)n * ed * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(h->pin_out.get(), h->eout, (size_t)n * ed * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
-  memcpy(out, h->pin_out, (size_t)n * ed * 4);
+  memcpy(out, h->pin_out.get(), (size_t)n * ed * 4);
   return GRL_OK;
 }
 

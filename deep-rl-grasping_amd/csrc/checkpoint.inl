@@ -158,7 +158,7 @@ int grl_state_import(grl_handle h, const void* host_buf, size_t n) {
   if (n != fixed + nl + np) return fail(GRL_ERR_INVALID, "state blob is truncated (observed rows)");
   HIPCHK(hipStreamSynchronize(h->stream));
   if (h->dp_on) {     // an exchange is in flight while some rank has announced one that this rank has not begun, or the reverse
-    if (h->dp_err_host && *h->dp_err_host) return fail(GRL_ERR_STATE, "an exchange timed out waiting for a peer (the replicas are no longer in step)");
+    if (h->dp_err_host.get() && *h->dp_err_host.get()) return fail(GRL_ERR_STATE, "an exchange timed out waiting for a peer (the replicas are no longer in step)");
     for (int k = 0; k < DP_CHANNELS; ++k) {
       DpCtl ctl;
       HIPCHK(hipMemcpy(&ctl, (char*)h->dp_flags + k * dp_ctl_stride(), sizeof(DpCtl), hipMemcpyDeviceToHost));

@@ -5,7 +5,7 @@
 //   plan_trpo.inl (TRPO: CG natural-gradient step, line search, value fit -- over plan_ppo.inl's policy and rollout)
 //   plan_bc.inl  (behaviour-cloning pretraining of a SAC handle's policy, built at grl_bc_begin)
 //   plan_gail.inl (GAIL session of a TRPO handle: discriminator update and its rewards, built at grl_gail_begin)
-//   capi.inl     (extern "C" entry points)
+//   capi.inl     (extern "C" entry points)      host_res.h (owning types of what a handle keeps outside the caller's arenas)
 // The element-wise, replay, prioritised-sampling and exchange kernels are compiled here; the GEMM and head kernels in
 // gemm_fwd.hip / gemm_bwd.hip / gemm_wgrad.hip / heads.hip behind the launchers of launch.h.
 //
@@ -55,6 +55,7 @@
 #include "bc_kernels.h"
 #define GRL_GAIL_TYPES_ONLY         // (the GAIL kernels in gail.hip)
 #include "gail_kernels.h"
+#include "host_res.h"
 
 namespace grl {
 
@@ -63,12 +64,14 @@ static int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-#define HIPCHK(expr)                                                                      \
+// (HIPCHK_AS: the message names `what` -- the HIP call behind an owning member of host_res.h -- instead of the expression)
+#define HIPCHK_AS(what, expr)                                                             \
   do {                                                                                    \
     hipError_t e_ = (expr);                                                               \
     if (e_ != hipSuccess)                                                                 \
-      return fail(GRL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
+      return fail(GRL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e_));         \
   } while (0)
+#define HIPCHK(expr) HIPCHK_AS(#expr, expr)
 
 static inline int64_t rup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
@@ -363,14 +366,14 @@ struct Session {
   std::vector<float> low, high;         // the action space's bounds
   Arena a;                              // the session buffer
   DevScalars* sc = nullptr;             // the optimiser's words of THIS session (adam_tick_device, adam_op)
-  std::vector<Launch*> launches;        // the GEMM launches of this plan, owned (the handle's own list is left as it was)
+  std::vector<std::unique_ptr<Launch>> launches;   // the GEMM launches of this plan, owned (the handle's own list is left as it was)
   std::vector<ReduceDesc> reduces;
   std::vector<std::string> dbg_names;
   std::vector<int32_t> idx_host;        // host copy of a call's index rows (checked before anything moves)
   int last_n = 0;                       // updates / batches the last call left
   explicit Session(const char* pre) : prefix(pre) {}
   Session(const Session&) = delete;
-  virtual ~Session() { for (auto* l : launches) delete l; }
+  virtual ~Session() = default;
   virtual int plan(grl_ctx& h) = 0;     // builds into `a` (a.base == nullptr: sizes only)
 };
 struct BcPlan;
@@ -414,11 +417,6 @@ struct grl_ctx {
   float *ob_latest = nullptr, *ob_prev = nullptr, *ob_term = nullptr;
   int64_t ob_elems = 0;
   int ob_n = 0, ob_n_prev = 0;     // rows held by ob_latest / ob_prev (0 = nothing observed yet)
-  float* pin_ob[2] = {nullptr, nullptr};            // page-locked staging of grl_observe / grl_replay_add_observed, alternating
-  hipEvent_t pin_ob_ev[2] = {nullptr, nullptr};
-  bool pin_ob_used[2] = {false, false};
-  size_t pin_ob_n = 0;
-  int pin_ob_next = 0;
   // replay
   float *rp_obs, *rp_next, *rp_dobs, *rp_dnext, *rp_act, *rp_rew, *rp_done;
   int64_t rp_pos = 0, rp_size = 0;
@@ -434,15 +432,9 @@ struct grl_ctx {
   float *act, *rew, *done;
   // act path
   float *afeat, *a_eps, *a_out;
-  float* act_io_host = nullptr;   // SAC: a_eps | a_out live in page-locked host memory (plan_sac.inl)
-  float* q_act_host = nullptr;         // DQN / BDQ: the Q-values of the act path in coherent host memory (plan_q.inl)
-  // DQN / BDQ, grl_act(GRL_ACT_GREEDY): observations [NA, obs_dim] | overrides [NA, D] | bins [NA, D] in coherent host memory
-  // (q_act.h); increments the greedy sequence leaves in the completion counter; whether the observations are read from there
-  float* q_io_host = nullptr;
-  unsigned q_greedy_wgs = 0;
+  unsigned q_greedy_wgs = 0;           // DQN / BDQ, GRL_ACT_GREEDY: increments the greedy sequence leaves in the completion counter
   bool q_act_fused = false;
   std::vector<Op> ops_act_greedy[4];   // [(observed by grl_observe) << 1 | (raw: VecNormalize applied on the device)], as ops_act_in
-  unsigned* act_done_host = nullptr;   // SAC: completion counter of the act path's last launch (coherent host memory), polled by grl_act
   unsigned act_done_wgs = 0, act_done_seen = 0;    // increments per call (0: no counter, synchronise the stream); expected value
   // encoder path
   float *enc_w[8];
@@ -451,7 +443,6 @@ struct grl_ctx {
 
   std::vector<Upload> uploads;
   std::vector<std::pair<void*, size_t>> zero_once;   // regions cleared once at creation
-  std::vector<Launch*> launches;
   std::vector<ReduceDesc> reduces;
   ReduceDesc* d_reduces = nullptr;
 
@@ -506,53 +497,51 @@ struct grl_ctx {
   std::vector<Op> dp_body;               // ops_grads without its final reduction (the exchange's first kernel forms the sums)
   std::vector<Op> dp_body_per;           // DQN / BDQ with prioritised replay: the same without the gather (the sampler gathers its rows)
   int dp_mode = 0;                       // 0 auto (one-shot for world <= 2), 1 two-shot, 2 one-shot
-  hipEvent_t copy_ev = nullptr;          // copy_from_caller: completion of a copy whose source is page-locked caller memory
-  uint32_t* dp_err_host = nullptr;       // page-locked mailbox: a kernel that gave up waiting for a peer sets it
   DpNormArgs dp_norm;                    // running-statistics merge over the ranks (grl_norm_update on a connected handle)
   std::vector<Op> ops_dp_overlap;        // the whole overlapped update: staged gradients, two exchanges (one on a side lane), Adam
   bool dp_overlap = false;
 
+  // What the handle owns outside the caller's arenas (host_res.h).  Members are destroyed in reverse order of declaration, so a
+  // member's POSITION decides: this block stands before `graphs`, and the captured graphs go before the page-locked memory,
+  // events and launches their nodes refer to (~grl_ctx has destroyed the graph objects themselves by then).
+  std::vector<std::unique_ptr<Launch>> launches;
+  // page-locked staging of the per-env-step calls (grl_act / grl_encode / grl_ppo_step): pageable copies cost more than the kernels
+  Pinned<float> pin_in, pin_out;
+  StagingRing<float> ob_ring;          // grl_replay_add_observed: actions, rewards, done flags, terminal rows of one env step
+  StagingRing<char> stats_ring;        // grl_set_obs_stats: mirrors of the VecNormalize statistics span
+  Pinned<float> act_io_host;           // SAC: a_eps | a_out live in page-locked host memory (plan_sac.inl)
+  Pinned<float> q_act_host;            // DQN / BDQ: the Q-values of the act path in coherent host memory (plan_q.inl)
+  Pinned<float> q_io_host;             // GRL_ACT_GREEDY: observations [NA, obs_dim] | overrides [NA, D] | bins [NA, D], coherent (q_act.h)
+  Pinned<unsigned> act_done_host;      // completion counter of the act path's last launch (coherent host memory), polled by grl_act
+  Pinned<uint32_t> dp_err_host;        // page-locked mailbox: a kernel that gave up waiting for a peer sets it
+  Event copy_ev;                       // copy_from_caller: completion of a copy whose source is page-locked caller memory
+  Stream side;                         // second capture lane (independent weight-gradient launches)
+  std::vector<Event> lane_ev;          // ... its fork / join events
+  std::vector<Event> ev;               // profiling: two timing events per op of the longest list run so far
+
   // graphs
   std::map<std::string, hipGraphExec_t> graphs;   // captured launch sequences, keyed by what they contain
-  hipStream_t side = nullptr;                     // second capture lane (independent weight-gradient launches)
-  std::vector<hipEvent_t> lane_ev;
   float apply_graph_scale = 0.f;
   bool use_graph = true;
 
   // profiling
   bool prof = false;
   std::map<std::string, ProfAcc> prof_acc;
-  std::vector<hipEvent_t> ev;
 
   std::map<std::string, std::pair<const float*, int64_t>> dbg;
 
   ~grl_ctx() {
     session_drop();
-    if (pin_in) hipHostFree(pin_in);
-    if (pin_out) hipHostFree(pin_out);
-    if (act_io_host) hipHostFree(act_io_host);
-    if (act_done_host) hipHostFree(act_done_host);
-    if (q_act_host) hipHostFree(q_act_host);
-    if (q_io_host) hipHostFree(q_io_host);
-    for (int k = 0; k < 2; ++k) {
-      if (pin_ob[k]) hipHostFree(pin_ob[k]);
-      if (pin_ob_ev[k]) hipEventDestroy(pin_ob_ev[k]);
-    }
-    for (int k = 0; k < 2; ++k) {
-      if (pin_stats[k]) hipHostFree(pin_stats[k]);
-      if (pin_stats_ev[k]) hipEventDestroy(pin_stats_ev[k]);
-    }
-    for (int p = 0; p < 2 * DP_MAX_WORLD; ++p)
-      if (dp_peer[p]) (void)hipIpcCloseMemHandle(dp_peer[p]);
+    dp_release();
+    drop_graphs();
+  }
+  // the exchange's allocations: the peers' IPC mappings (whichever a connect opened), this rank's data and flags
+  void dp_release() {
+    for (auto& p : dp_peer)
+      if (p) { (void)hipIpcCloseMemHandle(p); p = nullptr; }
     if (dp_buf) (void)hipFree(dp_buf);
     if (dp_flags) (void)hipFree(dp_flags);
-    if (dp_err_host) (void)hipHostFree(dp_err_host);
-    if (copy_ev) (void)hipEventDestroy(copy_ev);
-    for (auto* l : launches) delete l;
-    for (auto e : ev) hipEventDestroy(e);
-    for (auto e : lane_ev) hipEventDestroy(e);
-    if (side) hipStreamDestroy(side);
-    drop_graphs();
+    dp_buf = dp_flags = nullptr;
   }
   void drop_graphs() {
     for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
@@ -1113,9 +1102,9 @@ struct grl_ctx {
       }
       add_launch(tmp_a, tag, variant, probs);
       lpt_extra_tiles = 0; lpt_extra_w = 0;
-      Launch* la = launches.back();
+      Launch* la = launches.back().get();
       add_launch(tmp_b, ftag, fvariant, fprobs, "", 0, {}, 0);      // fillers keep the 64x64 shape of the merged launch
-      Launch* lb = launches.back();
+      Launch* lb = launches.back().get();
       if (tmp_a.size() == 1 && tmp_b.size() == 1 && pair_ok(la, lb)) {
         la->filler = lb;
         Op op = tmp_a[0];
@@ -1134,7 +1123,8 @@ struct grl_ctx {
       }
       return;
     }
-    Launch* l = new Launch();
+    launches.push_back(std::make_unique<Launch>());
+    Launch* l = launches.back().get();
     l->variant = variant;
     l->probs = std::move(probs);
     // addressing modes are compile-time in the kernels: derive them and insist they are uniform
@@ -1195,7 +1185,6 @@ struct grl_ctx {
       l->n_tiles = (int)work.size();
       l->d_probs = upload_vec(wk, per_tile_descs(l->probs, work));
       l->d_tiles = upload_vec(wk, work);
-      launches.push_back(l);
       plan_note("grl plan: %-14s streaming short-K kernel K %d  probs %zu  row tiles per workgroup %d  tiles %d\n", tag.c_str(), l->sk,
                 l->probs.size(), per, l->n_tiles);
       Op op;
@@ -1230,7 +1219,6 @@ struct grl_ctx {
       l->d_probs = upload_vec(wk, descs);
     }
     l->d_tiles = upload_vec(wk, tiles);
-    launches.push_back(l);
     Op op;
     op.tag = tag;
     op.flops = flops_alg;
@@ -1700,13 +1688,6 @@ struct grl_ctx {
   std::vector<Op> ops_grads_apply_per_r;        //     block sums current instead (updates 2 .. n of one call)
   int qD = 0, qN = 0;
   float *q_td = nullptr, *q_prio = nullptr, *q_aout = nullptr;
-  // pinned host staging of the per-env-step calls (grl_act / grl_encode): pageable copies cost more than the kernels
-  float *pin_in = nullptr, *pin_out = nullptr;
-  char* pin_stats[2] = {nullptr, nullptr};          // page-locked mirrors of the VecNormalize statistics span
-  hipEvent_t pin_stats_ev[2] = {nullptr, nullptr};
-  bool pin_stats_used[2] = {false, false};
-  int pin_stats_next = 0;
-  size_t pin_in_n = 0, pin_out_n = 0;
   int act_rows = 0;   // rows the act-path output kernel covers (the launches are sized for act_batch: one static graph)
   int64_t q_online_off = 0, q_online_n = 0;
   int run_ops(std::vector<Op>& ops);
@@ -1731,7 +1712,7 @@ int grl_ctx::plan_session(Session& s, Build build) {
   std::swap(reduces, s.reduces);
   const size_t n_launches = launches.size();
   build();
-  s.launches.assign(launches.begin() + n_launches, launches.end());
+  s.launches.assign(std::make_move_iterator(launches.begin() + n_launches), std::make_move_iterator(launches.end()));
   launches.resize(n_launches);
   std::swap(reduces, s.reduces);
   std::swap(wk, s.a);
@@ -1764,20 +1745,17 @@ int grl_ctx::run_ops(std::vector<Op>& ops) {
     for (auto& op : ops) op.run(stream);
     return GRL_OK;
   }
-  while (ev.size() < 2 * ops.size()) {
-    hipEvent_t e;
-    HIPCHK(hipEventCreate(&e));
-    ev.push_back(e);
-  }
+  if (ev.size() < 2 * ops.size()) ev.resize(2 * ops.size());
+  for (size_t i = 0; i < 2 * ops.size(); ++i) HIPCHK_AS("hipEventCreate(&e)", ev[i].create(0));     // (timing events: the default flags)
   for (size_t i = 0; i < ops.size(); ++i) {
-    HIPCHK(hipEventRecord(ev[2 * i], stream));
+    HIPCHK(hipEventRecord(ev[2 * i].raw(), stream));
     ops[i].run(stream);
-    HIPCHK(hipEventRecord(ev[2 * i + 1], stream));
+    HIPCHK(hipEventRecord(ev[2 * i + 1].raw(), stream));
   }
   HIPCHK(hipStreamSynchronize(stream));
   for (size_t i = 0; i < ops.size(); ++i) {
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]));
+    HIPCHK(hipEventElapsedTime(&ms, ev[2 * i].raw(), ev[2 * i + 1].raw()));
     ProfAcc& a = prof_acc[ops[i].tag];
     a.ms += ms; a.n += 1; a.flops += ops[i].flops; a.bytes += ops[i].bytes;
     a.flops_exec += ops[i].flops_exec > 0 ? ops[i].flops_exec : ops[i].flops;
@@ -1787,17 +1765,14 @@ int grl_ctx::run_ops(std::vector<Op>& ops) {
 
 int grl_ctx::capture(std::vector<std::vector<Op>*> seq, hipGraphExec_t* out) {
   hipGraph_t g;
-  if (!side) HIPCHK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+  hipStream_t lane1 = nullptr;
+  HIPCHK_AS("hipStreamCreateWithFlags(&side, hipStreamNonBlocking)", side.get(&lane1));
   size_t nev = 0;
   auto next_event = [&](hipEvent_t* e) -> hipError_t {
-    if (nev == lane_ev.size()) {
-      hipEvent_t x;
-      hipError_t r = hipEventCreateWithFlags(&x, hipEventDisableTiming);
-      if (r != hipSuccess) return r;
-      lane_ev.push_back(x);
-    }
-    *e = lane_ev[nev++];
-    return hipSuccess;
+    if (nev == lane_ev.size()) lane_ev.emplace_back();
+    const hipError_t r = lane_ev[nev].create();
+    *e = lane_ev[nev++].raw();
+    return r;
   };
   HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
   bool side_open = false;   // the side lane carries work that has not been joined yet
@@ -1808,15 +1783,15 @@ int grl_ctx::capture(std::vector<std::vector<Op>*> seq, hipGraphExec_t* out) {
           hipEvent_t e;
           HIPCHK(next_event(&e));
           HIPCHK(hipEventRecord(e, stream));
-          HIPCHK(hipStreamWaitEvent(side, e, 0));
+          HIPCHK(hipStreamWaitEvent(lane1, e, 0));
         }
-        op.run(side);
+        op.run(lane1);
         side_open = true;
       } else {
         if (op.join && side_open) {
           hipEvent_t e;
           HIPCHK(next_event(&e));
-          HIPCHK(hipEventRecord(e, side));
+          HIPCHK(hipEventRecord(e, lane1));
           HIPCHK(hipStreamWaitEvent(stream, e, 0));
           side_open = false;
         }
@@ -1826,7 +1801,7 @@ int grl_ctx::capture(std::vector<std::vector<Op>*> seq, hipGraphExec_t* out) {
   if (side_open) {   // every forked lane must be joined before the capture ends
     hipEvent_t e;
     HIPCHK(next_event(&e));
-    HIPCHK(hipEventRecord(e, side));
+    HIPCHK(hipEventRecord(e, lane1));
     HIPCHK(hipStreamWaitEvent(stream, e, 0));
   }
   HIPCHK(hipStreamEndCapture(stream, &g));

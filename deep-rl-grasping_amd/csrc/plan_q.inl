@@ -882,18 +882,12 @@ struct QPlanner {
     const float* adv = aact.adv; const float* vv = aact.v; float* qo = h.q_aout; const int rows = NA, Dq = D, nq = nb;
     // the last launch also writes the Q-values to coherent host memory and counts its workgroups there: grl_act polls the
     // counter instead of copying device -> host and synchronising the stream (GRL_TUNE act_poll=0 keeps that)
-    if (!h.dry && h.sw.get(Sw::act_poll) != 0 &&
-        hipHostMalloc((void**)&h.q_act_host, (size_t)NA * D * nb * 4, hipHostMallocCoherent) == hipSuccess) {
-      if (hipHostMalloc((void**)&h.act_done_host, 64, hipHostMallocCoherent) == hipSuccess) {
-        *h.act_done_host = 0u;
-        h.act_done_wgs = (unsigned)((rows * Dq + 255) / 256);
-      } else {
-        (void)hipHostFree(h.q_act_host);
-        h.q_act_host = nullptr; h.act_done_host = nullptr;
-      }
+    if (!h.dry && h.sw.get(Sw::act_poll) != 0 && h.q_act_host.reserve((size_t)NA * D * nb, hipHostMallocCoherent) == hipSuccess) {
+      if (h.act_done_host.reserve(16, hipHostMallocCoherent) == hipSuccess) h.act_done_wgs = (unsigned)((rows * Dq + 255) / 256);
+      else h.q_act_host.reset();
     }
-    float* qh = h.act_done_wgs ? h.q_act_host : nullptr;
-    unsigned* dn = h.act_done_wgs ? h.act_done_host : nullptr;
+    float* qh = h.act_done_wgs ? h.q_act_host.get() : nullptr;
+    unsigned* dn = h.act_done_wgs ? h.act_done_host.get() : nullptr;
     Op op2; op2.tag = "dueling";
     op2.run = [adv, vv, qo, rows, Dq, nq, qh, dn](hipStream_t s) {
       hipLaunchKernelGGL(dueling_kernel, dim3((rows * Dq + 255) / 256), dim3(256), 0, s, adv, vv, rows, Dq, nq, qo, qh, dn);
@@ -905,12 +899,9 @@ struct QPlanner {
   // cover; every other shape keeps the launch list of the Q-value path and gets the select kernel behind it (GRL_TUNE q_act=0: always)
   int act_greedy(unsigned* dn) {
     const size_t io_floats = (size_t)NA * c.obs_dim + 2 * (size_t)NA * D;
-    if (hipHostMalloc((void**)&h.q_io_host, io_floats * 4, hipHostMallocCoherent) != hipSuccess) {
-      h.q_io_host = nullptr;
+    if (h.q_io_host.reserve(io_floats, hipHostMallocCoherent) != hipSuccess)
       return fail(GRL_ERR_HIP, "no page-locked memory for the act path of the Q handle");
-    }
-    memset(h.q_io_host, 0, io_floats * 4);
-    float* io_obs = h.q_io_host; float* io_explore = io_obs + (size_t)NA * c.obs_dim; float* io_bins = io_explore + (size_t)NA * D;
+    float* io_obs = h.q_io_host.get(); float* io_explore = io_obs + (size_t)NA * c.obs_dim; float* io_bins = io_explore + (size_t)NA * D;
     for (int i = 0; i < NA * D; ++i) io_explore[i] = -1.f;
     h.q_act_fused = !r.ln && h.sw.get(Sw::q_act) != 0 && qa_shape_ok(c);
     plan_note("grl plan: q_act         epsilon-greedy act: %s\n",

@@ -1041,14 +1041,12 @@ struct SacPlanner {
     // noise in, actions out: page-locked HOST memory that the last launch of the act path reads and writes itself -- 320 bytes
     // each way for 16 environments, for which a copy-engine transfer in the stream costs more than the whole policy head
     if (!h.dry) {    // (grl_query_sizes plans without a device)
-      if (hipHostMalloc((void**)&h.act_io_host, (size_t)2 * NA * A * 4, 0) != hipSuccess) return fail(GRL_ERR_HIP, "hipHostMalloc failed");
-      memset(h.act_io_host, 0, (size_t)2 * NA * A * 4);
-      // (GRL_TUNE act_poll=0 keeps the stream synchronisation at the end of grl_act)
-      if (sw.get(Sw::act_poll) != 0 && hipHostMalloc((void**)&h.act_done_host, 64, hipHostMallocCoherent) == hipSuccess) *h.act_done_host = 0u;
-      else h.act_done_host = nullptr;
+      if (h.act_io_host.reserve((size_t)2 * NA * A) != hipSuccess) return fail(GRL_ERR_HIP, "hipHostMalloc failed");
+      // (GRL_TUNE act_poll=0 keeps the stream synchronisation at the end of grl_act; so does a counter that cannot be allocated)
+      if (sw.get(Sw::act_poll) != 0) (void)h.act_done_host.reserve(16, hipHostMallocCoherent);
     }
-    h.a_eps = h.act_io_host;
-    h.a_out = h.act_io_host + (size_t)NA * A;
+    h.a_eps = h.act_io_host.get();
+    h.a_out = h.a_eps + (size_t)NA * A;
     HeadAct ahPI{};
     h.alloc_head(ahPI, NA, 2, A);
     ActIngestArgs ia;
@@ -1131,8 +1129,8 @@ struct SacPlanner {
             ha.x_parts = fc_parts; ha.n_parts = fc_split; ha.part_stride = (long)NA * 512; ha.ld_parts = 512;
             ha.x_bias = P + h.ex[0].fb; ha.n_sum = 512;
           }
-          ha.done = h.act_done_host;
-          h.act_done_wgs = h.act_done_host ? (unsigned)((NA + HT_RB - 1) / HT_RB) : 0u;
+          ha.done = h.act_done_host.get();
+          h.act_done_wgs = h.act_done_host.get() ? (unsigned)((NA + HT_RB - 1) / HT_RB) : 0u;
           op.run = [ha](hipStream_t s) { launch_act_heads_mfma(ha, s); };
         } else {
           op.run = [ha](hipStream_t s) { hipLaunchKernelGGL(act_heads_kernel, dim3(ha.rows), dim3(256), 0, s, ha); };

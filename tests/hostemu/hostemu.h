@@ -59,16 +59,19 @@ static inline hipError_t hipGetLastError() { return 0; }
 struct hipPointerAttribute_t { int type; };
 enum { hipMemoryTypeHost = 1, hipMemoryTypeManaged = 3 };
 static inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t*, const void*) { return 1; }   // every pointer is pageable host memory here
-static inline hipError_t hipEventCreate(hipEvent_t*) { return 0; }
-static inline hipError_t hipEventDestroy(hipEvent_t) { return 0; }
-static inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return 0; }
-static inline hipError_t hipEventSynchronize(hipEvent_t) { return 0; }
-static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0; return 0; }
+// An event is a one-byte heap token that every use touches: under AddressSanitizer an event used after its destruction, destroyed
+// twice, never created (null) or leaked is a report.  (Streams stay null: a non-null emulated stream would switch graph capture on.)
+static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = malloc(1); if (*e) *(volatile char*)*e = 0; return *e ? 0 : 1; }
+static inline void hostemu_touch(hipEvent_t e) { *(volatile char*)e = (char)(*(volatile char*)e + 1); }
+static inline hipError_t hipEventDestroy(hipEvent_t e) { if (!e) return 1; hostemu_touch(e); free(e); return 0; }
+static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { hostemu_touch(e); return 0; }
+static inline hipError_t hipEventSynchronize(hipEvent_t e) { hostemu_touch(e); return 0; }
+static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) { hostemu_touch(a); hostemu_touch(b); *ms = 0; return 0; }
 enum { hipStreamNonBlocking = 1, hipEventDisableTiming = 2 };
 static inline hipError_t hipStreamCreateWithFlags(hipStream_t*, int) { return 0; }
 static inline hipError_t hipStreamDestroy(hipStream_t) { return 0; }
-static inline hipError_t hipEventCreateWithFlags(hipEvent_t*, int) { return 0; }
-static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, int) { return 0; }
+static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, int) { return hipEventCreate(e); }
+static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t e, int) { hostemu_touch(e); return 0; }
 static inline hipError_t hipStreamBeginCapture(hipStream_t, int) { return 1; }
 static inline hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t*) { return 1; }
 static inline hipError_t hipGraphInstantiate(hipGraphExec_t*, hipGraph_t, void*, void*, int) { return 1; }

@@ -17,10 +17,10 @@ SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 COMPILE_TIMEOUT = 10 * 23
 
 
-def compile_program(exe, obj_dir, extra):
-    """every csrc/*.hip and the program, compiled side by side and linked into `exe`"""
+def compile_program(exe, obj_dir, extra, program="session_lifetime_check"):
+    """every csrc/*.hip and tests/csrc/<program>.cpp, compiled side by side and linked into `exe`"""
     units = [(os.path.join(CSRC, f), f[:-4]) for f in sorted(os.listdir(CSRC)) if f.endswith(".hip")]
-    units.append((os.path.join(HERE, "csrc", "session_lifetime_check.cpp"), "session_lifetime_check"))
+    units.append((os.path.join(HERE, "csrc", program + ".cpp"), program))
     flags = ["-std=c++17", "-O1", "-g"] + extra + ["-DGRL_HOSTEMU", "-I", os.path.join(HERE, "hostemu"), "-I", os.path.join(ROOT, "include")]
     objs = [os.path.join(obj_dir, name + ".o") for _, name in units]
     procs = [subprocess.Popen(["g++"] + flags + ["-x", "c++", "-c", src, "-o", o]) for (src, _), o in zip(units, objs)]
