@@ -19,7 +19,16 @@
     if ((h) && !(h)->n_sd) NOT_ON_PPO(h, what);                                                                                   \
   } while (0)
 
-static int check_cfg(const grl_config* c, bool trpo_call = false) {
+// TD3 handles (plan_td3.inl) keep a SAC handle's replay ring and statistics but have one update form of their own: what they do
+// not define stops here, before anything moves
+#define NOT_ON_TD3(h, what)                                                                                                       \
+  do {                                                                                                                            \
+    if ((h) && (h)->cfg.algo == GRL_ALGO_TD3)                                                                                     \
+      return fail(GRL_ERR_STATE, what " is not defined on a TD3 handle (TD3 handles: grl_td3_train, grl_td3_get_metrics, grl_act, grl_replay_add, the statistics calls)"); \
+  } while (0)
+
+// `also`: the algorithm above 4 whose own create / query_sizes call is checking (GRL_ALGO_TRPO, GRL_ALGO_TD3), or -1
+static int check_cfg(const grl_config* c, int also = -1) {
   if (!c) return fail(GRL_ERR_INVALID, "null config");
   if (c->algo == GRL_ALGO_AE) {
     if (c->batch_size < 1 || c->batch_size > 4096) return fail(GRL_ERR_INVALID, "batch_size out of range");
@@ -36,8 +45,20 @@ static int check_cfg(const grl_config* c, bool trpo_call = false) {
   if (c->act_dim < 1 || c->act_dim > 64) return fail(GRL_ERR_INVALID, "act_dim out of range");
   if (c->replay_capacity < 1) return fail(GRL_ERR_INVALID, "replay_capacity must be >= 1");
   if (c->algo < 0 || c->algo > 4) {
-    if (!(trpo_call && c->algo == GRL_ALGO_TRPO))
-      return fail(GRL_ERR_INVALID, "algo must be 0..4 (5, GRL_ALGO_TRPO, needs a grl_trpo_config: grl_trpo_query_sizes / grl_trpo_create)");
+    if (!(also >= 0 && c->algo == also))
+      return fail(GRL_ERR_INVALID, "algo must be 0..4 (5, GRL_ALGO_TRPO, needs a grl_trpo_config: grl_trpo_query_sizes / grl_trpo_create; "
+                                   "6, GRL_ALGO_TD3, a grl_td3_config: grl_td3_query_sizes / grl_td3_create)");
+  }
+  if (c->algo == GRL_ALGO_TD3) {      // (read as a SAC handle's on vector observations)
+    if (c->extractor != GRL_EXTRACTOR_MLP) return fail(GRL_ERR_INVALID, "TD3: extractor must be GRL_EXTRACTOR_MLP (CNN extractors are not implemented)");
+    if (c->obs_dim < 1 || c->obs_dim > 64 * 64 * 5) return fail(GRL_ERR_INVALID, "TD3: obs_dim must be 1..20480");
+    if (c->normalize < 0 || c->normalize > 3) return fail(GRL_ERR_INVALID, "TD3: normalize must be 0..3");
+    if (c->act_batch < 0) return fail(GRL_ERR_INVALID, "TD3: act_batch must be >= 0");
+    if (c->q_branches || c->q_bins || c->q_n_common || c->q_n_branch || c->q_n_value || c->q_huber || c->q_double || c->q_grad_clip != 0.f ||
+        c->q_trunk_scale != 0.f || c->q_per || c->q_per_alpha != 0.f || c->q_per_eps != 0.f || c->q_per_stratified || c->q_per_alpha64 != 0.0 ||
+        c->q_loss_sum_branches || c->q_layer_norm || c->replay_rgb_u8)
+      return fail(GRL_ERR_INVALID, "TD3: every q_* field and replay_rgb_u8 must be 0");
+    return GRL_OK;
   }
   if (c->algo == GRL_ALGO_PPO || c->algo == GRL_ALGO_TRPO) {      // (a TRPO handle's grl_config is read as a PPO handle's)
     if (c->extractor != GRL_EXTRACTOR_MLP) return fail(GRL_ERR_INVALID, "PPO runs on flattened observations (MLP extractor)");
@@ -116,7 +137,7 @@ static int check_ppo(const grl_config* c, const grl_ppo_config* p) {
 }
 
 static int check_trpo(const grl_config* c, const grl_trpo_config* p) {
-  if (int e = check_cfg(c, true)) return e;
+  if (int e = check_cfg(c, GRL_ALGO_TRPO)) return e;
   if (c->algo != GRL_ALGO_TRPO) return fail(GRL_ERR_INVALID, "grl_trpo_query_sizes / grl_trpo_create take a grl_config with algo = GRL_ALGO_TRPO");
   if (!p) return fail(GRL_ERR_INVALID, "null TRPO config");
   if (p->n_steps < 1 || p->n_steps > 65536) return fail(GRL_ERR_INVALID, "TRPO: n_steps must be 1..65536");
@@ -136,12 +157,24 @@ static int check_trpo(const grl_config* c, const grl_trpo_config* p) {
   return GRL_OK;
 }
 
-static int query_sizes(const grl_config* cfg, const grl_ppo_config* ppo, grl_sizes* out, const grl_trpo_config* trpo = nullptr) {
+static int check_td3(const grl_config* c, const grl_td3_config* p) {
+  if (int e = check_cfg(c, GRL_ALGO_TD3)) return e;
+  if (c->algo != GRL_ALGO_TD3) return fail(GRL_ERR_INVALID, "grl_td3_query_sizes / grl_td3_create take a grl_config with algo = GRL_ALGO_TD3");
+  if (!p) return fail(GRL_ERR_INVALID, "null TD3 config");
+  if (p->policy_delay < 1) return fail(GRL_ERR_INVALID, "TD3: policy_delay must be >= 1");
+  if (!(p->target_policy_noise >= 0.f)) return fail(GRL_ERR_INVALID, "TD3: target_policy_noise must be >= 0");
+  if (!(p->target_noise_clip >= 0.f)) return fail(GRL_ERR_INVALID, "TD3: target_noise_clip must be >= 0");
+  return GRL_OK;
+}
+
+static int query_sizes(const grl_config* cfg, const grl_ppo_config* ppo, grl_sizes* out, const grl_trpo_config* trpo = nullptr,
+                       const grl_td3_config* td3 = nullptr) {
   if (!out) return fail(GRL_ERR_INVALID, "null out");
   grl_ctx ctx;
   ctx.cfg = *cfg;
   if (ppo) ctx.pcfg = *ppo;
   if (trpo) ctx.tcfg = *trpo;
+  if (td3) ctx.td3cfg = *td3;
   ctx.dry = true;
   if (int e = ctx.plan()) return e;
   out->state_bytes = ctx.st.off + 256;
@@ -166,6 +199,10 @@ int grl_trpo_query_sizes(const grl_config* cfg, const grl_trpo_config* trpo, grl
   if (int e = check_trpo(cfg, trpo)) return e;
   return query_sizes(cfg, nullptr, out, trpo);
 }
+int grl_td3_query_sizes(const grl_config* cfg, const grl_td3_config* td3, grl_sizes* out) {
+  if (int e = check_td3(cfg, td3)) return e;
+  return query_sizes(cfg, nullptr, out, nullptr, td3);
+}
 
 // Prioritised replay with an empty ring: all leaves 0, PerState at its starting values.  The block sums / minima (per.bsum,
 // per.bmin) need no reset: the first update of every prioritised call rebuilds ALL of them from the leaves below the ring's fill
@@ -186,7 +223,7 @@ static double ppo_norm_eps(const grl_ctx* h) { return h->pcfg.norm_eps64 != 0.0 
 static int ppo_load_stats(grl_ctx* h, const double* mean, const double* var);
 
 static int create_handle(const grl_config* cfg, const grl_ppo_config* ppo, const grl_buffers* bufs, grl_handle* out,
-                         const grl_trpo_config* trpo = nullptr) {
+                         const grl_trpo_config* trpo = nullptr, const grl_td3_config* td3 = nullptr) {
   if (!bufs || !out || !bufs->state || !bufs->grads || !bufs->work || !bufs->replay)
     return fail(GRL_ERR_INVALID, "null buffers");
   std::unique_ptr<grl_ctx> owner(new grl_ctx());      // released into *out on success: every refusal below destroys it
@@ -194,6 +231,7 @@ static int create_handle(const grl_config* cfg, const grl_ppo_config* ppo, const
   h->cfg = *cfg;
   if (ppo) h->pcfg = *ppo;
   if (trpo) h->tcfg = *trpo;
+  if (td3) h->td3cfg = *td3;
   h->st.base = (char*)bufs->state; h->gr.base = (char*)bufs->grads;
   h->wk.base = (char*)bufs->work; h->rp.base = (char*)bufs->replay;
   if (int e = h->plan()) return e;
@@ -214,6 +252,12 @@ static int create_handle(const grl_config* cfg, const grl_ppo_config* ppo, const
   s0.lr = cfg->lr;
   hipError_t e = hipMemcpy(h->sc, &s0, sizeof(s0), hipMemcpyHostToDevice);
   if (e != hipSuccess) return fail(GRL_ERR_HIP, std::string("scalar init: ") + hipGetErrorString(e));
+  if (h->sc2) {      // TD3: the policy's optimiser words, the update cursor
+    e = hipMemcpy(h->sc2, &s0, sizeof(s0), hipMemcpyHostToDevice);
+    const Td3Dev d0 = {-1, -1, 0.f, 0};
+    if (e == hipSuccess) e = hipMemcpy(h->td3_dev, &d0, sizeof(d0), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(GRL_ERR_HIP, std::string("td3 init: ") + hipGetErrorString(e));
+  }
   if (h->n_mean) {   // RunningMeanStd(): mean 0, var 1, count 1e-4
     std::vector<double> ones((size_t)h->n_elems, 1.0);
     const double c2[2] = {1e-4, 1e-4};
@@ -254,6 +298,10 @@ int grl_trpo_create(const grl_config* cfg, const grl_trpo_config* trpo, const gr
   if (int e = check_trpo(cfg, trpo)) return e;
   return create_handle(cfg, nullptr, bufs, out, trpo);
 }
+int grl_td3_create(const grl_config* cfg, const grl_td3_config* td3, const grl_buffers* bufs, grl_handle* out) {
+  if (int e = check_td3(cfg, td3)) return e;
+  return create_handle(cfg, nullptr, bufs, out, nullptr, td3);
+}
 
 int grl_destroy(grl_handle h) {
   if (!h) return GRL_OK;
@@ -292,6 +340,11 @@ int grl_reset_optimizer(grl_handle h) {
   HIPCHK(hipMemcpy(&s0, h->sc, sizeof(s0), hipMemcpyDeviceToHost));
   s0.beta1_power = 0.9f; s0.beta2_power = 0.999f;
   HIPCHK(hipMemcpy(h->sc, &s0, sizeof(s0), hipMemcpyHostToDevice));
+  if (h->sc2) {      // TD3: the policy's Adam too
+    HIPCHK(hipMemcpy(&s0, h->sc2, sizeof(s0), hipMemcpyDeviceToHost));
+    s0.beta1_power = 0.9f; s0.beta2_power = 0.999f;
+    HIPCHK(hipMemcpy(h->sc2, &s0, sizeof(s0), hipMemcpyHostToDevice));
+  }
   return GRL_OK;
 }
 
@@ -547,6 +600,7 @@ static int ppo_observe(grl_handle h, const float* obs, int n, int flags) {
 
 int grl_observe(grl_handle h, const float* obs, int n, int flags) {
   NOT_ON_PPO_WITHOUT_STATS(h, "grl_observe");
+  NOT_ON_TD3(h, "grl_observe");
   if (!h || !obs || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (h->n_sd) return ppo_observe(h, obs, n, flags);
   if (!h->ob_latest) return fail(GRL_ERR_STATE, "this handle keeps no observed observations (SAC / DQN / BDQ handles do)");
@@ -570,6 +624,7 @@ int grl_observe(grl_handle h, const float* obs, int n, int flags) {
 int grl_replay_add_observed(grl_handle h, const float* act, const float* rew, const float* done, int n,
                             const int32_t* term_rows, const float* term_obs, int n_term) {
   NOT_ON_PPO(h, "grl_replay_add_observed");
+  NOT_ON_TD3(h, "grl_replay_add_observed");
   if (!h || !act || !rew || !done || n < 1 || n_term < 0 || n_term > n) return fail(GRL_ERR_INVALID, "bad argument");
   if (n_term > 0 && (!term_rows || !term_obs)) return fail(GRL_ERR_INVALID, "terminal rows without their observations");
   if (!h->ob_latest) return fail(GRL_ERR_STATE, "this handle keeps no observed observations (SAC / DQN / BDQ handles do)");
@@ -612,6 +667,7 @@ static int stage_noise(grl_handle h, const int64_t* idx, const float* eps, int s
 
 int grl_compute_grads(grl_handle h, const int64_t* idx, const float* eps) {
   NOT_ON_PPO(h, "grl_compute_grads");
+  NOT_ON_TD3(h, "grl_compute_grads");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if ((idx == nullptr) != (eps == nullptr)) return fail(GRL_ERR_INVALID, "idx and eps must both be given or both be NULL");
   if (h->rp_size < 1) return fail(GRL_ERR_STATE, "replay buffer is empty");
@@ -627,6 +683,7 @@ int grl_compute_grads(grl_handle h, const int64_t* idx, const float* eps) {
 
 int grl_compute_grads_staged(grl_handle h, int stage, const int64_t* idx, const float* eps) {
   NOT_ON_PPO(h, "grl_compute_grads_staged");
+  NOT_ON_TD3(h, "grl_compute_grads_staged");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if (stage != 0 && stage != 1) return fail(GRL_ERR_INVALID, "stage must be 0 or 1");
   if (!h->staged_ok) {          // plans without a staged form: everything in stage 0, one bucket (grl_grad_ranges)
@@ -652,6 +709,7 @@ int grl_compute_grads_staged(grl_handle h, int stage, const int64_t* idx, const 
 
 int grl_grad_ranges(grl_handle h, int bucket, int cap, int64_t* offsets, int64_t* numels) {
   NOT_ON_PPO(h, "grl_grad_ranges");
+  NOT_ON_TD3(h, "grl_grad_ranges");
   if (!h || !offsets || !numels) return fail(GRL_ERR_INVALID, "null argument");
   if (bucket != 0 && bucket != 1) return fail(GRL_ERR_INVALID, "bucket must be 0 or 1");
   std::vector<std::pair<int64_t, int64_t>> r;
@@ -672,6 +730,7 @@ int grl_grad_ranges(grl_handle h, int bucket, int cap, int64_t* offsets, int64_t
 
 int grl_apply_grads(grl_handle h, float grad_scale) {
   NOT_ON_PPO(h, "grl_apply_grads");
+  NOT_ON_TD3(h, "grl_apply_grads");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if (grad_scale != h->apply_graph_scale) {   // the scale is baked into the captured kernel arguments
     auto it = h->graphs.find("apply");
@@ -686,6 +745,7 @@ int grl_apply_grads(grl_handle h, float grad_scale) {
 
 int grl_train_step(grl_handle h, int n_steps, const int64_t* idx, const float* eps) {
   NOT_ON_PPO(h, "grl_train_step");
+  NOT_ON_TD3(h, "grl_train_step");
   if (!h || n_steps < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (h->cfg.algo == GRL_ALGO_AE) return fail(GRL_ERR_STATE, "auto-encoder handles train with grl_ae_train_step");
   if ((idx == nullptr) != (eps == nullptr)) return fail(GRL_ERR_INVALID, "idx and eps must both be given or both be NULL");
@@ -709,6 +769,7 @@ int grl_train_step(grl_handle h, int n_steps, const int64_t* idx, const float* e
 
 int grl_train_step_per(grl_handle h, int n_steps, double beta, const double* u) {
   NOT_ON_PPO(h, "grl_train_step_per");
+  NOT_ON_TD3(h, "grl_train_step_per");
   if (!h || n_steps < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (!h->per_on) return fail(GRL_ERR_STATE, "prioritised replay is not enabled (grl_config.q_per)");
   if (h->rp_size < 1) return fail(GRL_ERR_STATE, "replay buffer is empty");
@@ -780,6 +841,7 @@ int grl_ae_reconstruct(grl_handle h, const float* imgs, float* out) {
 }
 
 int grl_get_metrics(grl_handle h, grl_metrics* out) {
+  NOT_ON_TD3(h, "grl_get_metrics");
   if (!h || !out) return fail(GRL_ERR_INVALID, "null argument");
   DevScalars s;
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1046,6 +1108,75 @@ int grl_trpo_debug_fvp(grl_handle h) {
   return GRL_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- TD3 (plan_td3.inl)
+#define TD3_ONLY(h, what)                                                                                        \
+  do {                                                                                                           \
+    if (!(h)) return fail(GRL_ERR_INVALID, "null handle");                                                       \
+    if ((h)->cfg.algo != GRL_ALGO_TD3) return fail(GRL_ERR_STATE, what " is defined for TD3 handles (grl_td3_create)"); \
+  } while (0)
+
+int grl_td3_train(grl_handle h, int n_updates, const int64_t* idx, const float* eps, int64_t first_step) {
+  TD3_ONLY(h, "grl_td3_train");
+  if (n_updates < 1 || n_updates > GRL_TD3_MAX_UPDATES) return fail(GRL_ERR_INVALID, "grl_td3_train takes 1.." + std::to_string(GRL_TD3_MAX_UPDATES) + " updates per call");
+  if (first_step < 0) return fail(GRL_ERR_INVALID, "first_step must be >= 0");
+  if (h->rp_size < 1) return fail(GRL_ERR_STATE, "replay buffer is empty");
+  const int64_t delay = h->td3cfg.policy_delay;
+  auto policy = [&](int u) { return (first_step + u) % delay == 0 ? 1 : 0; };
+  const int v = (idx ? 0 : 1) | (eps ? 0 : 2);
+  // cursor -1 (td3_smooth advances it in front of every loss launch); the last policy loss of the call before becomes the carried one
+  launch_td3_carry(h->td3_dev, h->td3_part, h->td3_nblk, h->cfg.batch_size, h->stream);
+  h->td3_last_n = n_updates;
+  h->td3_first_step = first_step;
+  const int64_t per = (int64_t)h->B * h->A;
+  if (v != 3 || h->prof) {      // something handed over (or profiling): update by update
+    for (int u = 0; u < n_updates; ++u) {
+      if (idx) HIPCHK(hipMemcpyAsync(h->idx_buf, idx + (int64_t)u * h->B, (size_t)h->B * 8, hipMemcpyDeviceToDevice, h->stream));
+      if (eps) HIPCHK(hipMemcpyAsync(h->eps_buf, eps + (int64_t)u * per, (size_t)per * 4, hipMemcpyDeviceToDevice, h->stream));
+      const int p = policy(u);
+      if (int e = h->run_seq(std::string("td3_v") + char('0' + v) + (p ? "_policy" : "_critic"), {&h->ops_td3[p][v]})) return e;
+    }
+  } else {
+    // everything drawn on the device: groups of up to `graph_updates` updates (powers of two) go out as ONE linear graph, keyed
+    // by the phase of its first update in the policy_delay cycle
+    const int limit = h->graphs_on() ? grl_ctx::max_group() : 1;
+    for (int u = 0; u < n_updates;) {
+      int group = 1;
+      while (2 * group <= limit && 2 * group <= n_updates - u) group *= 2;
+      std::vector<std::vector<Op>*> seq;
+      for (int g = 0; g < group; ++g) seq.push_back(&h->ops_td3[policy(u + g)][3]);
+      const std::string key = "td3_rng_ph" + std::to_string((first_step + u) % delay) + (group > 1 ? "_x" + std::to_string(group) : "");
+      if (int e = h->run_seq(key, seq)) return e;
+      u += group;
+    }
+  }
+  HIPCHK(hipGetLastError());
+  return GRL_OK;
+}
+
+int grl_td3_get_metrics(grl_handle h, float* out, int cap) {
+  TD3_ONLY(h, "grl_td3_get_metrics");
+  if (!out) return fail(GRL_ERR_INVALID, "null argument");
+  const int nu = h->td3_last_n, nb = h->td3_nblk;
+  if (cap < nu * GRL_TD3_METRICS) return fail(GRL_ERR_INVALID, "metrics buffer too small");
+  std::vector<float> part((size_t)std::max(1, nu * nb * TD3_DIAG));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (nu) HIPCHK(hipMemcpy(part.data(), h->td3_part, (size_t)nu * nb * TD3_DIAG * 4, hipMemcpyDeviceToHost));
+  Td3Dev dev;
+  HIPCHK(hipMemcpy(&dev, h->td3_dev, sizeof(dev), hipMemcpyDeviceToHost));
+  const float B = (float)h->cfg.batch_size;
+  float pl = dev.pl_carry;      // the handle's last policy update before this call, whether or not its metrics were fetched
+  for (int u = 0; u < nu; ++u) {
+    float s[TD3_DIAG] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < nb; ++b)      // the per-block sums of the loss launch, in index order
+      for (int k = 0; k < TD3_DIAG; ++k) s[k] += part[((size_t)u * nb + b) * TD3_DIAG + k];
+    const bool policy = (h->td3_first_step + u) % h->td3cfg.policy_delay == 0;
+    if (policy) pl = s[2] / B;
+    float* o = out + (size_t)u * GRL_TD3_METRICS;
+    o[0] = s[0] / B; o[1] = s[1] / B; o[2] = pl; o[3] = s[3] / B; o[4] = s[4] / B; o[5] = policy ? 1.f : 0.f;
+  }
+  return nu;
+}
+
 int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps, float* out) {
   if (!h || !out || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (flags & ~(GRL_ACT_DETERMINISTIC | GRL_ACT_RAW_OBS | GRL_ACT_OBSERVED | GRL_ACT_GREEDY)) return fail(GRL_ERR_INVALID, "unknown flag bits");
@@ -1053,7 +1184,9 @@ int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps, 
   const int deterministic = flags & GRL_ACT_DETERMINISTIC;
   const bool raw = (flags & GRL_ACT_RAW_OBS) != 0;        // raw observations: VecNormalize applied on the device (grl_norm_update statistics)
   const bool observed = (flags & GRL_ACT_OBSERVED) != 0;  // act on what grl_observe uploaded: no second upload
-  const bool q = h->cfg.algo != GRL_ALGO_SAC;   // DQN / BDQ: Q-values [n, D*bins]
+  const bool td3 = h->cfg.algo == GRL_ALGO_TD3;            // pi(obs): no noise is read, both flag values give the same action
+  const bool q = h->cfg.algo != GRL_ALGO_SAC && !td3;   // DQN / BDQ: Q-values [n, D*bins]
+  if (td3 && observed) return fail(GRL_ERR_STATE, "GRL_ACT_OBSERVED is not defined on a TD3 handle (grl_observe is not)");
   if (!observed && !obs) return fail(GRL_ERR_INVALID, "bad argument");
   if (q && (raw || observed) && !(flags & GRL_ACT_GREEDY))
     return fail(GRL_ERR_STATE, "the Q-value form of grl_act takes normalised observations handed to it (GRL_ACT_GREEDY accepts GRL_ACT_RAW_OBS / GRL_ACT_OBSERVED)");
@@ -1064,9 +1197,9 @@ int grl_act(grl_handle h, const float* obs, int n, int flags, const float* eps, 
     if (!q) return fail(GRL_ERR_STATE, "GRL_ACT_GREEDY is defined for DQN / BDQ handles");
     return act_greedy(h, obs, n, eps, out, raw, observed);
   }
-  if (!q && !deterministic && !eps) return fail(GRL_ERR_INVALID, "stochastic action needs eps");
+  if (!q && !td3 && !deterministic && !eps) return fail(GRL_ERR_INVALID, "stochastic action needs eps");
   const int64_t oe = (!q && h->cnn) ? (int64_t)h->hw * h->hw * h->cfg.obs_channels : h->cfg.obs_dim;
-  const size_t n_in = observed ? 0 : (size_t)n * oe, n_eps = (!q && !deterministic) ? (size_t)n * h->A : 0;
+  const size_t n_in = observed ? 0 : (size_t)n * oe, n_eps = (!q && !td3 && !deterministic) ? (size_t)n * h->A : 0;
   const size_t n_out = q ? (size_t)n * h->qD * h->qN : (size_t)n * h->A;
   if (int e = pin_reserve(h, n_in, q ? n_out : 0)) return e;
   if (n_in) memcpy(h->pin_in.get(), obs, n_in * 4);
@@ -1098,6 +1231,7 @@ static size_t dp_mom_bytes(int64_t elems) { return (size_t)rup((2 * elems + 4) *
 
 int grl_allreduce_init(grl_handle h, int rank, int world, void* handle_out) {
   NOT_ON_PPO(h, "grl_allreduce_init");
+  NOT_ON_TD3(h, "grl_allreduce_init");
   if (!h || !handle_out) return fail(GRL_ERR_INVALID, "null argument");
   if (h->cfg.algo == GRL_ALGO_AE) return fail(GRL_ERR_STATE, "the exchange step is defined for SAC / DQN / BDQ handles");
   if (world < 1 || world > DP_MAX_WORLD || rank < 0 || rank >= world) return fail(GRL_ERR_INVALID, "bad rank / world size");
@@ -1233,6 +1367,7 @@ static void close_with_exchange(grl_ctx* h, const DpArgs& d, bool ride, CallPlan
 
 int grl_allreduce_connect(grl_handle h, const void* handles) {
   NOT_ON_PPO(h, "grl_allreduce_connect");
+  NOT_ON_TD3(h, "grl_allreduce_connect");
   if (!h || !handles) return fail(GRL_ERR_INVALID, "null argument");
   if (!h->dp_buf) return fail(GRL_ERR_STATE, "call grl_allreduce_init first");
   if (h->dp_on) return fail(GRL_ERR_STATE, "already connected");
@@ -1368,6 +1503,7 @@ int grl_allreduce_connect(grl_handle h, const void* handles) {
 
 int grl_allreduce_disconnect(grl_handle h) {
   NOT_ON_PPO(h, "grl_allreduce_disconnect");
+  NOT_ON_TD3(h, "grl_allreduce_disconnect");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if (!h->dp_buf && !h->dp_flags) return GRL_OK;          // never initialised (or already released): nothing to do
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1386,6 +1522,7 @@ int grl_allreduce_disconnect(grl_handle h) {
 
 int grl_allreduce_set_overlap(grl_handle h, int on) {
   NOT_ON_PPO(h, "grl_allreduce_set_overlap");
+  NOT_ON_TD3(h, "grl_allreduce_set_overlap");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if (!h->dp_on) return fail(GRL_ERR_STATE, "call grl_allreduce_init / grl_allreduce_connect first");
   if (on && h->ops_dp_overlap.empty()) return fail(GRL_ERR_STATE, "this configuration has no staged plan: the exchange cannot be overlapped");
@@ -1395,6 +1532,7 @@ int grl_allreduce_set_overlap(grl_handle h, int on) {
 
 int grl_allreduce_set_mode(grl_handle h, int mode) {
   NOT_ON_PPO(h, "grl_allreduce_set_mode");
+  NOT_ON_TD3(h, "grl_allreduce_set_mode");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if (!h->dp_on) return fail(GRL_ERR_STATE, "call grl_allreduce_init / grl_allreduce_connect first");
   if (mode < 0 || mode > 2) return fail(GRL_ERR_INVALID, "mode: 0 auto, 1 two-shot, 2 one-shot");
@@ -1405,6 +1543,7 @@ int grl_allreduce_set_mode(grl_handle h, int mode) {
 
 int grl_allreduce_set_timeout(grl_handle h, int ms) {
   NOT_ON_PPO(h, "grl_allreduce_set_timeout");
+  NOT_ON_TD3(h, "grl_allreduce_set_timeout");
   if (!h || ms < 0) return fail(GRL_ERR_INVALID, "bad argument");
   if (!h->dp_err_host.get()) return fail(GRL_ERR_STATE, "call grl_allreduce_init first");
   __atomic_store_n(h->dp_err_host.get() + 1, (uint32_t)ms, __ATOMIC_RELEASE);     // read by the waiting kernels (dp_wait_all)
@@ -1413,6 +1552,7 @@ int grl_allreduce_set_timeout(grl_handle h, int ms) {
 
 int grl_train_step_allreduce(grl_handle h, int n_steps, const int64_t* idx, const float* eps) {
   NOT_ON_PPO(h, "grl_train_step_allreduce");
+  NOT_ON_TD3(h, "grl_train_step_allreduce");
   if (!h || n_steps < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (!h->dp_on) return fail(GRL_ERR_STATE, "call grl_allreduce_init / grl_allreduce_connect first");
   if ((idx == nullptr) != (eps == nullptr)) return fail(GRL_ERR_INVALID, "idx and eps must both be given or both be NULL");
@@ -1449,6 +1589,7 @@ int grl_train_step_allreduce(grl_handle h, int n_steps, const int64_t* idx, cons
 
 int grl_allreduce_status(grl_handle h, int64_t* exchanges, int* error) {
   NOT_ON_PPO(h, "grl_allreduce_status");
+  NOT_ON_TD3(h, "grl_allreduce_status");
   if (!h || !h->dp_flags) return fail(GRL_ERR_STATE, "no exchange buffer");
   HIPCHK(hipStreamSynchronize(h->stream));
   DpCtl c[DP_CHANNELS];
@@ -1471,6 +1612,7 @@ int grl_allreduce_status(grl_handle h, int64_t* exchanges, int* error) {
 
 int grl_q_update_target(grl_handle h) {
   NOT_ON_PPO(h, "grl_q_update_target");
+  NOT_ON_TD3(h, "grl_q_update_target");
   if (!h) return fail(GRL_ERR_INVALID, "null handle");
   if (h->cfg.algo == GRL_ALGO_SAC) return fail(GRL_ERR_STATE, "SAC has no hard target update");
   HIPCHK(hipMemcpyAsync(h->params + h->tgt_off, h->params + h->q_online_off, (size_t)h->q_online_n * 4,
@@ -1480,6 +1622,7 @@ int grl_q_update_target(grl_handle h) {
 
 int grl_encoder_load(grl_handle h, const float* const* w, const int64_t* numels, int n_arrays) {
   NOT_ON_PPO(h, "grl_encoder_load");
+  NOT_ON_TD3(h, "grl_encoder_load");
   if (!h || !w || !numels || n_arrays != 8) return fail(GRL_ERR_INVALID, "expected 8 weight arrays");
   if (h->cfg.algo != GRL_ALGO_SAC) return fail(GRL_ERR_STATE, "grl_encoder_load is for SAC handles (auto-encoder handles encode with their own parameters)");
   const int64_t wn[8] = {7 * 7 * 32, 32, 5 * 5 * 32 * 32, 32, 3 * 3 * 32 * 32, 32, 2048 * 100, 100};
@@ -1493,6 +1636,7 @@ int grl_encoder_load(grl_handle h, const float* const* w, const int64_t* numels,
 
 int grl_encode(grl_handle h, const float* depth, int n, float* out) {
   NOT_ON_PPO(h, "grl_encode");
+  NOT_ON_TD3(h, "grl_encode");
   if (!h || !depth || !out || n < 1) return fail(GRL_ERR_INVALID, "bad argument");
   if (!h->enc_loaded) return fail(GRL_ERR_STATE, "grl_encoder_load has not been called");
   if (n > h->NA) return fail(GRL_ERR_INVALID, "n exceeds act_batch");

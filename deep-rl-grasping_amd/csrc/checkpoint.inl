@@ -114,6 +114,7 @@ static size_t state_bytes_now(const grl_ctx* h) {
 
 int grl_state_size(grl_handle h, size_t* bytes) {
   NOT_ON_PPO(h, "grl_state_size");
+  NOT_ON_TD3(h, "grl_state_size");
   if (!h || !bytes) return fail(GRL_ERR_INVALID, "null argument");
   *bytes = state_bytes_now(h);
   return GRL_OK;
@@ -121,6 +122,7 @@ int grl_state_size(grl_handle h, size_t* bytes) {
 
 int64_t grl_state_export(grl_handle h, void* host_buf, size_t cap) {
   NOT_ON_PPO(h, "grl_state_export");
+  NOT_ON_TD3(h, "grl_state_export");
   if (!h || !host_buf) return fail(GRL_ERR_INVALID, "null argument");
   const size_t total = state_bytes_now(h);
   if (cap < total) return fail(GRL_ERR_INVALID, "state buffer too small: " + std::to_string(total) + " bytes needed");
@@ -139,6 +141,7 @@ int64_t grl_state_export(grl_handle h, void* host_buf, size_t cap) {
 
 int grl_state_import(grl_handle h, const void* host_buf, size_t n) {
   NOT_ON_PPO(h, "grl_state_import");
+  NOT_ON_TD3(h, "grl_state_import");
   if (!h || !host_buf) return fail(GRL_ERR_INVALID, "null argument");
   const char* p = (const char*)host_buf;
   grl_state_header hd;
@@ -179,6 +182,7 @@ int grl_state_import(grl_handle h, const void* host_buf, size_t n) {
 
 int grl_replay_segments(grl_handle h, int cap, grl_segment* out) {
   NOT_ON_PPO(h, "grl_replay_segments");
+  NOT_ON_TD3(h, "grl_replay_segments");
   if (!h || (cap > 0 && !out)) return fail(GRL_ERR_INVALID, "null argument");
   std::vector<grl_segment> s;
   if (h->cfg.algo != GRL_ALGO_AE) {

@@ -5,6 +5,7 @@
 //   plan_trpo.inl (TRPO: CG natural-gradient step, line search, value fit -- over plan_ppo.inl's policy and rollout)
 //   plan_bc.inl  (behaviour-cloning pretraining of a SAC handle's policy, built at grl_bc_begin)
 //   plan_gail.inl (GAIL session of a TRPO handle: discriminator update and its rewards, built at grl_gail_begin)
+//   plan_td3.inl (TD3: twin critics, smoothed targets, delayed policy -- over a SAC handle's replay ring and gather)
 //   capi.inl     (extern "C" entry points)      host_res.h (owning types of what a handle keeps outside the caller's arenas)
 // The element-wise, replay, prioritised-sampling and exchange kernels are compiled here; the GEMM and head kernels in
 // gemm_fwd.hip / gemm_bwd.hip / gemm_wgrad.hip / heads.hip behind the launchers of launch.h.
@@ -55,6 +56,8 @@
 #include "bc_kernels.h"
 #define GRL_GAIL_TYPES_ONLY         // (the GAIL kernels in gail.hip)
 #include "gail_kernels.h"
+#define GRL_TD3_TYPES_ONLY          // (the TD3 kernels in td3.hip)
+#include "td3_kernels.h"
 #include "host_res.h"
 
 namespace grl {
@@ -1671,6 +1674,18 @@ struct grl_ctx {
   // Host words of the rollout beside a GAIL session, no part of any exported state: a finished full rollout is still in the replay
   // arena (grl_ppo_finish .. the next grl_ppo_step); the rewards of the rollout being closed are already the discriminator's
   bool ppo_held = false, gail_rewritten = false;
+  int plan_td3();      // TD3 (MlpPolicy, Box actions): critic-only and policy updates over a SAC handle's replay ring
+  // TD3 state (plan_td3.inl): its configuration block, the policy's optimiser words (`sc`: the critics'), the update cursor, the
+  // per-block diagnostics of a training call; the launch lists [policy update][bit 0: indices drawn | bit 1: normals drawn]; what
+  // the last call ran (grl_td3_get_metrics; the carried policy loss lives in Td3Dev)
+  grl_td3_config td3cfg = {};
+  DevScalars* sc2 = nullptr;
+  Td3Dev* td3_dev = nullptr;
+  float* td3_part = nullptr;
+  int td3_nblk = 0;
+  std::vector<Op> ops_td3[2][4];
+  int td3_last_n = 0;
+  int64_t td3_first_step = 0;
   int plan_ae_general(const AeNet& net);   // ... of any supported network but the shipped one (GRL_TUNE ae_general=1: that one too)
   int enc_dim = 100;   // floats per image grl_encode returns (auto-encoder handles: their encoding_dim)
   float* ae_x = nullptr;            // [B, 4096] minibatch of depth images (staged per step)
@@ -1696,7 +1711,7 @@ struct grl_ctx {
 
 // --------------------------------------------------------------------------------------------------
 int grl_ctx::plan() {
-  const int e = cfg.algo == GRL_ALGO_SAC ? plan_sac() : (cfg.algo == GRL_ALGO_AE ? plan_ae() : (cfg.algo == GRL_ALGO_PPO ? plan_ppo() : (cfg.algo == GRL_ALGO_TRPO ? plan_trpo() : plan_q())));
+  const int e = cfg.algo == GRL_ALGO_SAC ? plan_sac() : (cfg.algo == GRL_ALGO_AE ? plan_ae() : (cfg.algo == GRL_ALGO_PPO ? plan_ppo() : (cfg.algo == GRL_ALGO_TRPO ? plan_trpo() : (cfg.algo == GRL_ALGO_TD3 ? plan_td3() : plan_q()))));
   sw.note();
   return e;
 }
@@ -1739,6 +1754,7 @@ void grl_ctx::session_drop() {
 #include "plan_trpo.inl"
 #include "plan_bc.inl"
 #include "plan_gail.inl"
+#include "plan_td3.inl"
 
 int grl_ctx::run_ops(std::vector<Op>& ops) {
   if (!prof) {

@@ -59,6 +59,16 @@ class GrlTrpoConfig(C.Structure):
 TRPO_METRICS = 11        # GRL_TRPO_METRICS
 
 
+class GrlTd3Config(C.Structure):
+    """include/grl.h: grl_td3_config -- what a TD3 handle needs beside its GrlConfig."""
+    _fields_ = [("policy_delay", C.c_int32), ("target_policy_noise", C.c_float), ("target_noise_clip", C.c_float)]
+
+
+ALGO_TD3 = 6             # GRL_ALGO_TD3
+TD3_MAX_UPDATES = 1024   # GRL_TD3_MAX_UPDATES
+TD3_METRICS = 6          # GRL_TD3_METRICS
+
+
 class GrlBcConfig(C.Structure):
     """include/grl.h: grl_bc_config -- a behaviour-cloning session on a SAC handle."""
     _fields_ = [("batch", C.c_int32), ("lr", C.c_float), ("adam_eps", C.c_float),
@@ -108,6 +118,7 @@ EXPORTS = [
     "grl_ppo_query_sizes", "grl_ppo_create", "grl_ppo_step", "grl_ppo_rewards", "grl_ppo_finish", "grl_ppo_train",
     "grl_ppo_get_metrics",
     "grl_trpo_query_sizes", "grl_trpo_create", "grl_trpo_update", "grl_trpo_get_metrics", "grl_trpo_debug_fvp",
+    "grl_td3_query_sizes", "grl_td3_create", "grl_td3_train", "grl_td3_get_metrics",
     "grl_bc_query_sizes", "grl_bc_begin", "grl_bc_train", "grl_bc_eval", "grl_bc_get_losses", "grl_bc_end",
     "grl_gail_query_sizes", "grl_gail_begin", "grl_gail_param_info", "grl_gail_rewards", "grl_gail_update", "grl_gail_get_losses",
     "grl_gail_get_stats", "grl_gail_set_stats", "grl_gail_end",
@@ -215,6 +226,10 @@ def load_library(path=None):
     lib.grl_trpo_update.argtypes = [vp, vp, i32]
     lib.grl_trpo_get_metrics.argtypes = [vp, f32p, i32]
     lib.grl_trpo_debug_fvp.argtypes = [vp]
+    lib.grl_td3_query_sizes.argtypes = [C.POINTER(GrlConfig), C.POINTER(GrlTd3Config), C.POINTER(GrlSizes)]
+    lib.grl_td3_create.argtypes = [C.POINTER(GrlConfig), C.POINTER(GrlTd3Config), C.POINTER(GrlBuffers), C.POINTER(vp)]
+    lib.grl_td3_train.argtypes = [vp, i32, vp, vp, i64]
+    lib.grl_td3_get_metrics.argtypes = [vp, f32p, i32]
     lib.grl_bc_query_sizes.argtypes = [vp, C.POINTER(GrlBcConfig), C.POINTER(C.c_size_t)]
     lib.grl_bc_begin.argtypes = [vp, C.POINTER(GrlBcConfig), vp]
     lib.grl_bc_train.argtypes = [vp, f32p, f32p, i64, vp, i32]
@@ -399,4 +414,19 @@ def make_trpo_config(obs_dim, act_dim, timesteps_per_batch=1024, pi_layers=(64, 
         t.vf_layers[i] = int(h)
     t.cg_iters, t.ls_steps, t.fvp_stride, t.vf_batch = int(cg_iters), int(ls_steps), int(fvp_stride), int(vf_batch)
     t.lam, t.max_kl, t.cg_damping, t.ent_coef, t.adam_eps = lam, max_kl, cg_damping, entcoeff, adam_eps
+    return cfg, t
+
+
+def make_td3_config(obs_dim, act_dim, layers=(64, 64), batch_size=128, act_batch=1, replay_capacity=50000, normalize=False, gamma=0.99,
+                    lr=3e-4, tau=0.005, policy_delay=2, target_policy_noise=0.2, target_noise_clip=0.5, clip_obs=10.0, clip_reward=10.0,
+                    norm_eps=1e-8, seed=0):
+    """(GrlConfig, GrlTd3Config) of a TD3 handle (stable-baselines 2.10.1 TD3 + MlpPolicy, Box actions): the GrlConfig of a SAC
+    handle on vector observations with algo = GRL_ALGO_TD3 (target_entropy is not read)."""
+    cfg = make_config("mlp", obs_dim=int(obs_dim), act_dim=int(act_dim), layers=tuple(layers), batch_size=int(batch_size),
+                      act_batch=int(act_batch), replay_capacity=int(replay_capacity), normalize=normalize, gamma=gamma, lr=lr, tau=tau,
+                      clip_obs=clip_obs, clip_reward=clip_reward, norm_eps=norm_eps, target_entropy=0.0, seed=seed)
+    cfg.algo = ALGO_TD3
+    cfg.obs_channels = cfg.n_direct = cfg.img_hw = 0
+    t = GrlTd3Config()
+    t.policy_delay, t.target_policy_noise, t.target_noise_clip = int(policy_delay), float(target_policy_noise), float(target_noise_clip)
     return cfg, t

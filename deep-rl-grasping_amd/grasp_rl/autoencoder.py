@@ -124,7 +124,9 @@ def defer_in_this_process():
 
 
 def deferred_records():
-    return [dict(r) for r in _DEFERRED]
+    """What the DeferredEncoders built in THIS process recorded.  A forked worker inherits the module state of its parent: records
+    another process left there (the parent's own, from before the fork) are not this worker's and are not reported."""
+    return [{"config": r["config"], "model_dir": r["model_dir"]} for r in _DEFERRED if r.get("pid") == os.getpid()]
 
 
 def find_live_encoder(model_dir):
@@ -300,7 +302,7 @@ class DeferredEncoder:
         # configuration fails here, in the worker, as it would in `SimpleAutoEncoder`
         self.encoded_shape = (net_of_config(self.config)[2],) if self.config else (SHIPPED_NET[2],)
         self.model_dir = None
-        self._record = {"config": self.config, "model_dir": None}
+        self._record = {"config": self.config, "model_dir": None, "pid": os.getpid()}
         _DEFERRED.append(self._record)
 
     def load_weights(self, model_dir):

@@ -742,6 +742,63 @@ class SacEngine:
         return out
 
 
+class Td3Engine(SacEngine):
+    """TD3 handle (``_capi.make_td3_config``): arenas, replay ring, statistics calls, parameters, ``set_learning_rate``,
+    ``reset_optimizer`` (both Adams), ``fetch`` / ``store`` and profiling as on a SAC handle on vector observations; ``train``
+    runs twin-critic updates with the delayed policy update, ``act`` returns pi(obs)."""
+
+    METRIC_NAMES = ("qf1_loss", "qf2_loss", "policy_loss", "mean_q1", "mean_q2", "policy_updated")
+
+    def __init__(self, cfg, td3, backend=None, lib_path=None, device="cuda:0"):
+        self.td3 = td3
+        super().__init__(cfg, backend=backend, lib_path=lib_path, device=device)
+        self.obs_dim = cfg.obs_dim
+        self.ldq = (cfg.obs_dim + cfg.act_dim + 3) // 4 * 4      # row stride of the critics' input rows ("td3_xs", "td3_xn")
+
+    def _query_sizes(self, cfg, sizes):
+        return self.lib.grl_td3_query_sizes(C.byref(cfg), C.byref(self.td3), C.byref(sizes))
+
+    def _create(self, cfg, bufs, h):
+        return self.lib.grl_td3_create(C.byref(cfg), C.byref(self.td3), C.byref(bufs), C.byref(h))
+
+    def train(self, n_updates=1, idx=None, eps=None, first_step=0):
+        """n_updates updates in one call; update u is a policy update iff (first_step + u) % policy_delay == 0.  idx
+        [n_updates, B] replay rows / eps [n_updates, B, A] standard normals of the target smoothing (host arrays): either may be
+        None for device draws."""
+        di = de = None
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(n_updates, self.B)
+            if idx.min() < 0 or idx.max() >= self.replay_size():
+                raise GrlError("replay index out of range")
+            di = self.be.to_device(idx)
+        if eps is not None:
+            de = self.be.to_device(np.ascontiguousarray(eps, dtype=np.float32).reshape(n_updates, self.B, self.A))
+        pi = C.c_void_p(self.be.ptr(di)) if di is not None else None
+        pe = C.c_void_p(self.be.ptr(de)) if de is not None else None
+        check(self.lib, self.lib.grl_td3_train(self.h, int(n_updates), pi, pe, int(first_step)))
+        self._keep = [(di, de)]   # keep the staged tensors alive until the stream has consumed them
+
+    def metrics(self):
+        """[n_updates, 6] of the last ``train``: columns METRIC_NAMES (synchronises)."""
+        out = np.empty((_capi.TD3_MAX_UPDATES, _capi.TD3_METRICS), np.float32)
+        n = check(self.lib, self.lib.grl_td3_get_metrics(self.h, out.ctypes.data, out.size))
+        return out[:n].copy()
+
+    def act(self, obs, deterministic=True, eps=None, raw=False, observed=False):
+        """pi(obs) of n <= act_batch observations (exploration noise is the caller's: `deterministic` and `eps` change nothing).
+        raw=True: un-normalised observations, VecNormalize applied on the device."""
+        if observed:
+            raise GrlError("TD3: observe / act(observed=True) is not implemented")
+        obs = np.ascontiguousarray(obs, dtype=np.float32).reshape(-1, self.obs_dim)
+        out = np.empty((obs.shape[0], self.A), np.float32)
+        check(self.lib, self.lib.grl_act(self.h, obs.ctypes.data, obs.shape[0], 1 | (2 if raw else 0), None, out.ctypes.data))
+        return out
+
+    def adam_steps(self):
+        """(critic steps, policy steps) the two Adams have taken, from their beta1 powers."""
+        return tuple(int(round(np.log(float(self.fetch(n, (2,))[0])) / np.log(0.9))) - 1 for n in ("td3_beta_c", "td3_beta_pi"))
+
+
 class QEngine(SacEngine):
     """DQN / BDQ handle (``_capi.make_q_config``): same arenas and calls -- ``norm_update``, ``set_running_stats``,
     ``get_obs_stats``, ``observe`` / ``observe_rows`` and ``replay_add_observed`` (action columns: the bins [n, branches]) as

@@ -27,6 +27,23 @@ class SacLnCnnPolicy(SacCnnPolicy):
     layer_norm = True
 
 
+class Td3MlpPolicy(BasePolicy):
+    family = "td3"
+
+
+class Td3LnMlpPolicy(Td3MlpPolicy):
+    layer_norm = True
+
+
+class Td3CnnPolicy(BasePolicy):
+    family = "td3"
+    feature_extraction = "cnn"
+
+
+class Td3LnCnnPolicy(Td3CnnPolicy):
+    layer_norm = True
+
+
 class DqnMlpPolicy(BasePolicy):
     family = "deepq"
 

@@ -295,7 +295,7 @@ def evaluate_success(model, kind="depth", action="box", episodes=200, seed=10_00
 
 def learn_reach(algo="sac", kind="depth", total_timesteps=30_000, n_envs=16, device="cuda:0", seed=0, engine_factory=None,
                 eval_episodes=200, q_envs=1, **model_kwargs):
-    """Train `algo` ('sac' | 'dqn' | 'bdq') on ReachGraspEnv through the stable-baselines surface the reference drives
+    """Train `algo` ('sac' | 'td3' | 'dqn' | 'bdq') on ReachGraspEnv through the stable-baselines surface the reference drives
     (sb_helper.py:104-128 / 159-165 / 210-224: VecNormalize(norm_obs, norm_reward, clip_obs 10) + model.learn), then run the
     reference's evaluation.  Returns dict(train_success = mean is_success of the last 200 TRAINING episodes (the
     reference's monitor column `s`, trained_models/*/log_file.monitor.csv), eval_success, eval_distance, updates, seconds)."""
@@ -318,7 +318,7 @@ def learn_reach(algo="sac", kind="depth", total_timesteps=30_000, n_envs=16, dev
             return True
 
     action = "discrete" if algo == "dqn" else "box"
-    N = n_envs if algo == "sac" else q_envs       # (DQN / BDQ: one environment unless q_envs asks for more)
+    N = n_envs if algo in ("sac", "td3") else q_envs       # (DQN / BDQ: one environment unless q_envs asks for more)
     venv = DummyVecEnv([(lambda s=s: ReachGraspEnv(kind, seed=seed * 1000 + s, action=action)) for s in range(N)])
     env = VecNormalize(venv, norm_obs=True, norm_reward=True, clip_obs=10.0)
     if algo == "sac":
@@ -331,6 +331,17 @@ def learn_reach(algo="sac", kind="depth", total_timesteps=30_000, n_envs=16, dev
         cls = SAC
         args = (policy, env)
         kw["policy_kwargs"] = pk
+    elif algo == "td3":     # vector observations, Box actions; one update per environment step, Gaussian exploration noise
+        from .sb.td3 import TD3
+        from stable_baselines.common.noise import NormalActionNoise
+        if kind != "vector":
+            raise NotImplementedError("TD3: CnnPolicy is not implemented (learn_reach('td3', ...) runs on kind='vector')")
+        n_act = int(np.prod(venv.action_space.shape))
+        kw = dict(buffer_size=100_000, batch_size=256, learning_starts=max(256, N), train_freq=1, gradient_steps=N,
+                  action_noise=NormalActionNoise(np.zeros((N, n_act)), 0.1 * np.ones((N, n_act))),      # (a draw per environment)
+                  policy_kwargs={"layers": [64, 64]}, seed=seed)
+        kw.update(model_kwargs)
+        cls, args = TD3, ("MlpPolicy", env)
     elif algo == "dqn":     # config/gripper_grasp.yaml DQN block: lr 1e-3, batch 32, prioritized_replay
         kw = dict(learning_rate=1e-3, batch_size=32, prioritized_replay=True, seed=seed)
         kw.update(model_kwargs)
@@ -362,5 +373,10 @@ def learn_reach(algo="sac", kind="depth", total_timesteps=30_000, n_envs=16, dev
     out = {"algo": algo, "kind": kind, "env_steps": int(model.num_timesteps), "updates": int(model.n_updates),
            "episodes": len(cb.s), "train_success": float(np.mean(cb.s[-200:])) if cb.s else 0.0,
            "eval_success": ev, "eval_distance": dist, "seconds": round(secs, 2), "metrics": model.engine.metrics()}
+    if algo == "td3":       # the target networks start as copies of the initial model: how many of their tensors the Polyak updates moved
+        from .init import init_parameters
+        first, last = init_parameters(model.engine.table, seed=seed), model.get_parameters()
+        out["targets_moved"] = sum(not np.array_equal(first[n], last[n]) for n in last if n.startswith("target/"))
+        out["targets"] = sum(n.startswith("target/") for n in last)
     model.engine.close()
     return out

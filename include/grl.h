@@ -479,6 +479,50 @@ int grl_trpo_debug_fvp(grl_handle h);
    old policy's means).  The grl_gail_* calls (below) open a GAIL session on a TRPO handle.  Every other entry point returns
    GRL_ERR_STATE on a TRPO handle before anything moves. */
 
+/* ---------------------------------------------------------------------------------------------------------------------
+   TD3 (GRL_ALGO_TD3): stable-baselines 2.10.1 TD3 (td3/td3.py, td3/policies.py) with MlpPolicy on a Box action space: a
+   deterministic policy pi = tanh(dense(relu-MLP(obs))), twin critics on [obs, action], target copies of all three.  The handle
+   is described by a grl_config AND a grl_td3_config.  The grl_config is read as on a SAC handle with GRL_EXTRACTOR_MLP: obs_dim,
+   act_dim, layers, batch_size, act_batch, replay_capacity, normalize, gamma, lr, tau, clip_obs / clip_reward / norm_eps and seed
+   (target_entropy is ignored; every q_* field and replay_rgb_u8 must be 0).  Parameters, in TF creation order:
+   model/pi/fc{l}, model/pi/dense, model/values_fn/qf1/fc{l}, model/values_fn/qf1/qf1, the same for qf2 (all trainable), then the
+   same tree under target/.
+   One update on minibatch rows s, a, r, s', d (gathered and normalised as on a SAC handle):
+     a' = clip(pi_target(s') + clip(sigma eps, -c, c), -1, 1);   y = r + (1 - d) gamma min(q1_target(s', a'), q2_target(s', a'))
+     qf1_loss = mean((y - q1(s, a))^2), qf2_loss likewise; the critics step on their sum with an Adam of their own (epsilon 1e-8)
+   and, on a policy update only: policy_loss = -mean(q1(s, pi(s))) steps model/pi with a second Adam whose step count advances
+   on policy updates only, then target <- (1 - tau) target + tau online over every model/ variable.  Every gradient and metric is
+   formed at the parameters the update began with; both Adam steps follow; the Polyak average reads the stepped parameters. */
+#define GRL_ALGO_TD3 6   /* created through grl_td3_create (grl_td3_config) */
+typedef struct grl_td3_config {
+  int32_t policy_delay;                    /* >= 1: update u of a call is a policy update iff (first_step + u) % policy_delay == 0 */
+  float target_policy_noise;               /* sigma >= 0 */
+  float target_noise_clip;                 /* c >= 0 */
+} grl_td3_config;
+int grl_td3_query_sizes(const grl_config* cfg, const grl_td3_config* td3, grl_sizes* out);
+int grl_td3_create(const grl_config* cfg, const grl_td3_config* td3, const grl_buffers* bufs, grl_handle* out);
+/* n_updates (1 .. GRL_TD3_MAX_UPDATES) updates, stream-ordered.  idx: DEVICE int64 [n_updates, batch_size] replay rows, or NULL:
+   drawn on the device (Philox: cfg.seed, one counter per update); eps: DEVICE float32 [n_updates, batch_size, act_dim] standard
+   normals of the target smoothing, or NULL: drawn on the device with the same counter.  Either may be NULL.  With both NULL the
+   updates go out in hipGraphs of up to `graph_updates` updates (GRL_TUNE); one call of n updates equals n calls of one update,
+   bit for bit.  first_step >= 0: the learner's step count at update 0 (TD3._train_step's `step + grad_step`). */
+#define GRL_TD3_MAX_UPDATES 1024
+int grl_td3_train(grl_handle h, int n_updates, const int64_t* idx_or_null, const float* eps_or_null, int64_t first_step);
+/* host, synchronises: [n, 6] floats of the last grl_td3_train call, one row per update: qf1_loss, qf2_loss, policy_loss (the last
+   policy update's value on a critic-only update -- of this call or of any call before it, fetched or not: the value is kept on
+   the device; 0 before the handle's first policy update), mean q1(s, a), mean q2(s, a), 1 if the update was a policy update else 0.
+   Returns n. */
+#define GRL_TD3_METRICS 6
+int grl_td3_get_metrics(grl_handle h, float* out, int cap);
+/* On a TD3 handle grl_replay_add / _add_device / _size, grl_set_obs_stats, grl_set_running_stats, grl_set_ret_var,
+   grl_norm_update, grl_get_obs_stats, grl_param_count / _info, grl_reset_optimizer (both Adams), grl_set_learning_rate (one value
+   for both), grl_set_stream, grl_profile_* and grl_debug_fetch / _store work as on a SAC handle; grl_act returns pi(obs) for
+   n <= act_batch rows (GRL_ACT_DETERMINISTIC changes nothing, eps is not read: exploration noise is the host's).  Debug names:
+   "td3_a_next" [B, A], "td3_noise" [B, A] (the standard normals as drawn or handed over), "td3_backup" [B], "td3_q" [5, B]
+   (q1, q2, q1_target, q2_target, q1(s, pi(s))), "td3_pi" [B, A], "td3_da" [B, A], "td3_xs" / "td3_xn" [B, ld] (the critics'
+   input rows [obs | action | padding] of s and s'), "rew", "done", "td3_beta_c" / "td3_beta_pi" (the beta powers of the two
+   Adams), "grads", "adam_m", "adam_v".  Every other entry point returns GRL_ERR_STATE on a TD3 handle before anything moves. */
+
 /* ---- Behaviour-cloning pretraining of a SAC handle's policy from recorded (observation, action) pairs: stable-baselines
    2.10.1 BaseRLModel.pretrain with SAC._get_pretrain_placeholders.  One update on a minibatch of n present rows:
      det = tanh(mu(obs));  a_env = low + 0.5 (det + 1)(high - low);  loss = mean over the n * act_dim elements of (a_exp - a_env)^2
